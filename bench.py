@@ -22,9 +22,14 @@ Multi-GPU: one process per GPU (torchrun), each rank works on its own shard; inf
 have no data-path collective -- RCCL is used only for the timing barrier and the max-over-ranks
 reduction; the training step all-reduces the gradient.  Scaling is weak (per-GPU batch fixed).
 
-Extra objects on the JSON line: `roofline` for the dominant kernel, measured with HIP events on the launch stream in an
-instrumented repeat of the same K steps right after the timed region; and `cpu_baseline` = the CPU restatement under
-oracle/ ("port") timed on the host cores on a bounded sample (rank 0, N=1 only).
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.  `--full` adds the extra objects
+on the JSON line: `roofline` for the dominant kernel, measured with HIP events on the launch stream in an instrumented
+repeat of the same K steps right after the timed region; `cpu_baseline` = the CPU restatement under oracle/ ("port")
+timed on the host cores on a bounded sample (rank 0, N=1 only); and, for config c2, `extra` = the config-3 training step.
+
+`--dump-outputs DIR` writes what the last timed step computed (the arrays a caller of the timed path receives; a fixed
+sample of the 1000x256x256 config-4 volume) as DIR/<name>.npy, float32 / float64, from rank 0.  Inputs, weights and
+noise seeds are fixed, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -260,6 +265,7 @@ def spawn_ranks(args):
 
 def setup_dist(args):
     c = Ctx()
+    c.outputs = None
     c.world = int(os.environ.get("WORLD_SIZE", "1"))
     c.rank = int(os.environ.get("RANK", "0"))
     c.local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -291,26 +297,59 @@ def setup_dist(args):
     return c
 
 
-def timed(c, args, step_fn):
-    """W warm-up steps, then exactly K steps between barrier + synchronize; max over ranks."""
+def timed(c, args, step_fn, renew=None):
+    """W warm-up steps, then exactly K steps between barrier + synchronize; max over ranks.  `renew` = (due, run): before a step
+    for which due() holds, run() restarts the workload's state -- a reverse chain that has taken all T steps starts again from
+    x_T -- with the clock stopped, so that any K times steps only."""
     def barrier():
         torch.cuda.synchronize()
         if c.dist is not None:
             c.dist.barrier()
     for _ in range(args.warmup):
+        if renew is not None and renew[0]():
+            renew[1]()
         step_fn()
     barrier()
+    elapsed = 0.0
     t0 = time.perf_counter()
     for _ in range(args.steps):
+        if renew is not None and renew[0]():
+            torch.cuda.synchronize()
+            elapsed += time.perf_counter() - t0
+            renew[1]()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
         step_fn()
     torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    elapsed += time.perf_counter() - t0
     if c.dist is not None:
         c.dist.barrier()
         el = torch.tensor([elapsed], device=("cpu" if c.shared else c.dev), dtype=torch.float64)
         c.dist.all_reduce(el, op=c.dist.ReduceOp.MAX)
         elapsed = el.item()
     return elapsed
+
+
+OUTPUT_LIMIT_BYTES = 64 << 20
+
+
+def keep_outputs(c, args, arrays_fn):
+    """--dump-outputs: host copies of what the last timed step computed (rank 0), taken right after the timed region, before
+    any --full leg moves the state on; main() writes them as soon as the workload returns."""
+    if args.dump_outputs and c.rank == 0:
+        c.outputs = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in arrays_fn().items()}
+
+
+def write_outputs(path, outputs):
+    """One DIR/<name>.npy per array: float64 stays float64 (as do 64-bit integers), everything else is written as float32."""
+    os.makedirs(path, exist_ok=True)
+    conv = {k: np.ascontiguousarray(a, dtype=np.float64 if a.dtype in (np.float64, np.int64) else np.float32)
+            for k, a in outputs.items()}
+    total = sum(a.nbytes for a in conv.values())
+    if total > OUTPUT_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs exceed the {OUTPUT_LIMIT_BYTES} byte limit")
+    for k, a in conv.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def committed_traffic(config_name, batch, kernel_prefixes, cls=None):
@@ -513,8 +552,15 @@ def run_reverse(c, args, cfg):
     x_T = diff.sample_q(x0, t_T, diff.noise_fn(x0, t_T).float())
     chain = diff.reverse_chain(model, x_T, T_STEPS, noise_fn)
     table_setup_ms = getattr(chain, "table_setup_ms", 0.0)             # all T steps' newSeed() tables, drawn before the timed region
-    assert (args.warmup + args.steps) * 2 + 2 <= T_STEPS
-    elapsed = timed(c, args, chain.step)
+    # a chain has T steps: more warm-up + timed (+ instrumented) steps than that restart it from x_T on the same buffers and graph
+    renew = (lambda: chain.remaining == 0, lambda: chain.reset(x_T, T_STEPS))
+
+    def advance():
+        if renew[0]():
+            renew[1]()
+        chain.step()
+    elapsed = timed(c, args, chain.step, renew)
+    keep_outputs(c, args, lambda: {"sample": chain.x})
     if args.dump_plan and c.rank == 0:
         with open(args.dump_plan, "w") as f:
             json.dump(next(iter(model._plans.values())).igemm_log, f)
@@ -535,7 +581,7 @@ def run_reverse(c, args, cfg):
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(args.steps):
-            chain.step()
+            advance()
         torch.cuda.synchronize()
         prof_ms_per_step = 1000.0 * (time.perf_counter() - t1) / args.steps
         ms = (ctypes.c_double * _lib.OP_MAX)()
@@ -653,8 +699,17 @@ def run_train(c, args, cfg):
     last = {}
 
     def step():
-        last["loss"], _ = train_step(model, diff, x, targs, flat, reducer, opt)
+        last["loss"], last["estimates"] = train_step(model, diff, x, targs, flat, reducer, opt)
     elapsed = timed(c, args, step)
+
+    def outputs():
+        # the step's returns (loss; p_loss's x_t and model output) and a fixed sample of the updated parameters, the EMA copy
+        # and the reduced gradient (the flat buffers hold ~130 M values each at base 128)
+        _, x_t, eps = last["estimates"]
+        idx = torch.from_numpy(np.unique(np.random.RandomState(0).randint(0, flat.numel, 1 << 20))).to(c.dev)
+        return {"loss": last["loss"].reshape(1), "x_t": x_t, "estimate_noise": eps, "params_sample": flat.flat_param[idx],
+                "ema_params_sample": flat_ema.flat_param[idx], "grad_sample": flat.flat_grad[idx]}
+    keep_outputs(c, args, outputs)
     ms_per_step = 1000.0 * elapsed / args.steps
     value = B * c.world / (ms_per_step / 1000.0)
     finite = bool(torch.isfinite(last["loss"]).item())
@@ -751,7 +806,7 @@ def run_train(c, args, cfg):
                       "parallelism": (f"data-parallel x{c.world}, bucketed RCCL all-reduce of the flat gradient" if c.dist is not None
                                       else "single GPU (no collective)"),
                       "loss_finite": finite, "peak_mem_GB": torch.cuda.max_memory_allocated() / 1e9}}
-    if reducer is not None and reducer.active:
+    if args.full and reducer is not None and reducer.active:
         # one more step with the stream synchronised inside finish(): where the buckets' all-reduces were enqueued in the
         # backward (host clock, ms after the first) and how long the step then waited for them -- the EXPOSED part of the
         # collective.  No 8-GPU node was available to the build: ANODDPM_BUCKET_MB (default 64) and the cut positions are untuned,
@@ -785,6 +840,12 @@ def run_simplex(c, args, cfg):
     def step():
         check(lib().anoddpm_simplex3_octaves_f64(ctypes.byref(a), current_stream()), "simplex3_octaves_f64")
     elapsed = timed(c, args, step)
+
+    def outputs():
+        # the volume is 8 B x Z x S x S (524 MB at config 4): a fixed sample of 2^20 voxels, plus its first and last z-slice whole
+        idx = torch.from_numpy(np.unique(np.random.RandomState(0).randint(0, out_t.numel(), 1 << 20))).to(c.dev)
+        return {"volume_sample": out_t.reshape(-1)[idx], "volume_first_slice": out_t[0], "volume_last_slice": out_t[-1]}
+    keep_outputs(c, args, outputs)
     ms_per_step = 1000.0 * elapsed / args.steps
     voxels = Z * S * S
     value = voxels * c.world / (ms_per_step / 1000.0)
@@ -842,6 +903,10 @@ def run_detect(c, args, cfg):
     def step():
         diff.detection_B(model, x0, dargs, ("bench", "image"), mask, denoise_fn="octave", total_avg=navg)
     elapsed = timed(c, args, step)
+    # per setting (upstream's loop order) what detection_B leaves in last_detection: the averaged chains' outputs, the mean /
+    # mse / threshold maps and the segmentation counts
+    keep_outputs(c, args, lambda: {k: torch.stack([r[k] for r in diff.last_detection])
+                                   for k in ("output", "mean", "mse", "threshold", "counts")})
     ms_per_step = 1000.0 * elapsed / args.steps
     sched = diff.last_chain_schedule
     settings = [r["t_distance"] for r in diff.last_detection]
@@ -909,6 +974,11 @@ def main():
                     help="bf16split3: OPT-IN side line -- the large F(4x4,3x3) layers on split-bf16 products (csrc/winograd43b.hip); "
                          "not the reference's arithmetic class, never the default, reported with its own dtype / arith fields")
     ap.add_argument("--no-extra", action="store_true", help="c2 only: skip the config-3 training step measured after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the HIP-event instrumented pass (`roofline`), the CPU baseline and, for c2, the "
+                         "config-3 training step (`extra`); --no-prof / --no-cpu-baseline / --no-extra drop single legs of it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -916,6 +986,13 @@ def main():
         args.steps = 2 if args.config == "det" else 20
     if args.warmup is None:
         args.warmup = 1 if args.config == "det" else 3
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run: set up, warm up, time the K steps, write the outputs, print the line -- nothing else
+        if args.dump_layers:
+            raise SystemExit("bench.py: --dump-layers reads the instrumented pass, which runs with --full only")
+        args.no_prof = args.no_cpu_baseline = args.no_extra = True
     if args.arith != "fp32":
         os.environ["ANODDPM_ARITH"] = args.arith              # read by the inference plan when it is built
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -924,6 +1001,8 @@ def main():
     cfg = dict(CONFIGS[args.config])
     run = {"reverse": run_reverse, "train": run_train, "simplex": run_simplex, "detect": run_detect}[cfg["kind"]]
     out, roofline, cpu_fn = run(c, args, cfg)
+    if c.outputs is not None:
+        write_outputs(args.dump_outputs, c.outputs)
     line = {"metric": out.pop("metric"), "value": out.pop("value"), "unit": out.pop("unit"), "n_gpus": c.world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": out.pop("ms_per_step"), "higher_is_better": True,
             "scaling": out.pop("scaling"), "vs_baseline": None, "dtype": out.pop("dtype"), "data": "synthetic",
@@ -973,7 +1052,7 @@ def extra_c3(c, args, line):
     th.start()
     try:
         a3 = argparse.Namespace(**vars(args))
-        a3.steps, a3.warmup, a3.no_prof, a3.batch, a3.config = 3, 2, True, 0, "c3"
+        a3.steps, a3.warmup, a3.no_prof, a3.batch, a3.config, a3.dump_outputs = 3, 2, True, 0, "c3", ""
         out, _, _ = run_train(c, a3, dict(CONFIGS["c3"]))
         res = {"c3_ms_per_step": out["ms_per_step"], "c3_images_per_s": out["value"], "c3_steps": a3.steps, "c3_warmup": a3.warmup,
                "c3_config": out["config"], "note": "measured after the timed region of this line's metric; not part of `value`"}

@@ -22,6 +22,8 @@ recipe from SURVEY.md 8c).  Outputs are DATA (inputs + expected outputs), never 
                          tensor upstream plots (x_0, chains, mean, mse, threshold, mask), keyed randn_like draws (keyed.py)
     mri_loader.npz       MRIDataset normalisation + slice (dataset.py:585-594, 621-625) and the deterministic part of
                          its transform (centre-crop 235, bilinear resize, scale; torchvision -> PIL) on a synthetic volume
+    simplex_crosscheck_kat.npz  Simplex_CLASS at seed 424242: permutation table, noise3 on 500 random points
+    boundary_names.json  the names the reference's callers take from the six shadowed module names (ast scan, names only)
 """
 import os
 import sys
@@ -680,9 +682,114 @@ def gen_simplex2():
     print("simplex2_kat.npz:", len(out), "arrays")
 
 
+def gen_simplex_crosscheck():
+    """The reference Simplex_CLASS at a seed none of the other fixtures use: its permutation table and noise3 on 500 uniform
+    points of [-9, 9)^3 (test_oracle_simplex.py:test_live_reference_crosscheck)."""
+    seed = 424242
+    R = ref_simplex.Simplex_CLASS()
+    R.newSeed(seed)
+    pts = np.random.RandomState(1).uniform(-9, 9, (500, 3))
+    out = {"seed": np.array(seed, dtype=np.int64), "perm": np.asarray(R._perm), "points": pts,
+           "values": np.array([R.noise3(*p) for p in pts], dtype=np.float64)}
+    np.savez_compressed(os.path.join(HERE, "simplex_crosscheck_kat.npz"), **out)
+    print("simplex_crosscheck_kat.npz:", len(out), "arrays")
+
+
+BOUNDARY_MODS = ("helpers", "evaluation", "dataset", "GaussianDiffusion", "UNet", "simplex")
+BOUNDARY_CALLERS = ("detection.py", "diffusion_training.py", "evaluation.py", "generate_images.py", "GaussianDiffusion.py")
+
+
+def _module_bindings(tree):
+    """Names a module binds anywhere (imports, defs, classes, assignments, loop / with / except targets, arguments)."""
+    import ast
+    bound = set()
+    for n in ast.walk(tree):
+        if isinstance(n, (ast.Import, ast.ImportFrom)):
+            for a in n.names:
+                if a.name != "*":
+                    bound.add((a.asname or a.name).split(".")[0])
+        elif isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef, ast.ClassDef)):
+            bound.add(n.name)
+        elif isinstance(n, ast.Name) and isinstance(n.ctx, (ast.Store, ast.Del)):
+            bound.add(n.id)
+        elif isinstance(n, ast.arg):
+            bound.add(n.arg)
+        elif isinstance(n, ast.ExceptHandler) and n.name:
+            bound.add(n.name)
+    return bound
+
+
+def _public_namespace(path):
+    """Top-level names of a reference module, as `import *` would hand them on (no `__all__` upstream)."""
+    import ast
+    tree = ast.parse(open(path).read())
+    names = set()
+    for n in tree.body:
+        if isinstance(n, (ast.Import, ast.ImportFrom)):
+            for a in n.names:
+                names.add((a.asname or a.name).split(".")[0])
+        elif isinstance(n, (ast.FunctionDef, ast.ClassDef)):
+            names.add(n.name)
+        elif isinstance(n, ast.Assign):
+            for t in n.targets:
+                if isinstance(t, ast.Name):
+                    names.add(t.id)
+    return {x for x in names if not x.startswith("_")}
+
+
+def gen_boundary_names():
+    """The names the reference's CALLERS take from the six module names this repo shadows (test_boundary_names.py), collected
+    by parsing the callers with `ast` (never importing them):
+      * `from M import a, b`                   -> (M, a), (M, b)
+      * `M.attr` after `import M`              -> (M, attr)
+      * `from helpers import *` + a free name  -> (helpers, name) for every name of the reference helpers' namespace the
+                                                  importer loads without binding it itself
+    plus the reference helpers' public namespace and the members the callers reach on the diffusion / UNet instances
+    (variable names as upstream spells them).  A list of names, no reference code."""
+    import ast
+    import json
+    import re
+    ref = _refimport.REF
+    uses = {}
+    helpers_ns = _public_namespace(os.path.join(ref, "helpers.py"))
+    for fn in BOUNDARY_CALLERS:
+        path = os.path.join(ref, fn)
+        if not os.path.exists(path):
+            continue
+        tree = ast.parse(open(path).read())
+        star = set()
+        for n in ast.walk(tree):
+            if isinstance(n, ast.ImportFrom) and n.module in BOUNDARY_MODS:
+                for a in n.names:
+                    if a.name == "*":
+                        star.add(n.module)
+                    else:
+                        uses.setdefault((n.module, a.name), []).append(fn)
+            elif isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id in BOUNDARY_MODS:
+                uses.setdefault((n.value.id, n.attr), []).append(fn)
+        if "helpers" in star:
+            bound = _module_bindings(tree)
+            for n in ast.walk(tree):
+                if isinstance(n, ast.Name) and isinstance(n.ctx, ast.Load) and n.id in helpers_ns and n.id not in bound:
+                    uses.setdefault(("helpers", n.id), []).append(fn)
+        assert star <= {"helpers"}, f"{fn}: star import of {star} not modelled"
+    diff_names, unet_names = set(), set()
+    for fn in BOUNDARY_CALLERS[:4]:
+        src = open(os.path.join(ref, fn)).read()
+        diff_names |= set(re.findall(r"\b(?:diff|diffusion)\.([A-Za-z_][A-Za-z_0-9]*)", src))
+        unet_names |= set(re.findall(r"\b(?:unet|ema|model)\.([A-Za-z_][A-Za-z_0-9]*)", src))
+    out = {"callers": list(BOUNDARY_CALLERS),
+           "uses": [[m, n, sorted(set(c))] for (m, n), c in sorted(uses.items())],
+           "helpers_namespace": sorted(helpers_ns), "diff_names": sorted(diff_names), "unet_names": sorted(unet_names)}
+    with open(os.path.join(HERE, "boundary_names.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("boundary_names.json:", len(out["uses"]), "uses")
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["simplex", "diffusion", "unet", "metrics", "vlb", "vlb_total", "loss", "simplex2", "unet_c5", "unet_c2_batch4", "training",
-                             "detection", "loader", "detection_loops"]
+                             "detection", "loader", "detection_loops", "simplex_crosscheck", "boundary_names"]
     torch.set_num_threads(8)
     if "simplex" in which:
         gen_simplex()
@@ -716,3 +823,7 @@ if __name__ == "__main__":
         gen_loader()
     if "detection_loops" in which:
         gen_detection_loops()
+    if "simplex_crosscheck" in which:
+        gen_simplex_crosscheck()
+    if "boundary_names" in which:
+        gen_boundary_names()

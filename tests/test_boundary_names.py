@@ -2,28 +2,27 @@
 this repo shadows (`helpers`, `evaluation`, `dataset`, `GaussianDiffusion`, `UNet`, `simplex`) is exported by the shim of
 that name at the repo root -- or sits on the committed allow-list of names SURVEY section 2 puts out of scope.
 
-The callers (`detection.py`, `diffusion_training.py`, `evaluation.py`, `generate_images.py`, and `GaussianDiffusion.py` for
-what it takes from `simplex` / `evaluation` / `helpers`) are parsed with `ast`, never imported or executed; the test is
-skipped where `/root/reference` does not exist (the GPU box).  Three kinds of use are collected:
+The names come from tests/golden/boundary_names.json, recorded by tests/golden/make_golden.py (gen_boundary_names), which
+parses the callers (`detection.py`, `diffusion_training.py`, `evaluation.py`, `generate_images.py`, and `GaussianDiffusion.py`
+for what it takes from `simplex` / `evaluation` / `helpers`) with `ast`, never importing or executing them.  Three kinds of
+use are recorded:
   * `from M import a, b`                         -> (M, a), (M, b)
   * `M.attr` after `import M`                    -> (M, attr)
   * `from helpers import *` + a free name        -> (helpers, name) for every name of the reference helpers' namespace the
                                                     importer loads without binding it itself (the leaked torch / os / json /
                                                     defaultdict included -- GaussianDiffusion.py:8 relies on them)
-and, for the two classes behind the boundary, the methods / attributes the callers reach through their instances
-(`diff.detection_B`, `unet.load_state_dict`, ...).
+together with the reference helpers' public namespace and, for the two classes behind the boundary, the methods / attributes
+the callers reach through their instances (`diff.detection_B`, `unet.load_state_dict`, ...).
 """
-import ast
 import importlib
+import json
 import os
 import sys
 
-import pytest
+from conftest import GOLDEN
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODS = ("helpers", "evaluation", "dataset", "GaussianDiffusion", "UNet", "simplex")
-CALLERS = ("detection.py", "diffusion_training.py", "evaluation.py", "generate_images.py", "GaussianDiffusion.py")
 
 # Names deliberately NOT provided, each with the SURVEY row that scopes it out.  Anything else missing is a failure.
 ALLOW = {
@@ -35,70 +34,14 @@ ALLOW = {
     ("helpers", "torchvision"): "SURVEY 2 row 5: plotting dependency (make_grid); leaked by `import torchvision.utils`, used by no caller",
 }
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
-
-
-def _module_bindings(tree):
-    """Names a module binds anywhere (imports, defs, classes, assignments, loop / with / except targets, arguments)."""
-    bound = set()
-    for n in ast.walk(tree):
-        if isinstance(n, (ast.Import, ast.ImportFrom)):
-            for a in n.names:
-                if a.name != "*":
-                    bound.add((a.asname or a.name).split(".")[0])
-        elif isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef, ast.ClassDef)):
-            bound.add(n.name)
-        elif isinstance(n, ast.Name) and isinstance(n.ctx, (ast.Store, ast.Del)):
-            bound.add(n.id)
-        elif isinstance(n, ast.arg):
-            bound.add(n.arg)
-        elif isinstance(n, ast.ExceptHandler) and n.name:
-            bound.add(n.name)
-    return bound
-
-
-def _public_namespace(path):
-    """Top-level names of a reference module, as `import *` would hand them on (no `__all__` upstream)."""
-    tree = ast.parse(open(path).read())
-    names = set()
-    for n in tree.body:
-        if isinstance(n, (ast.Import, ast.ImportFrom)):
-            for a in n.names:
-                names.add((a.asname or a.name).split(".")[0])
-        elif isinstance(n, (ast.FunctionDef, ast.ClassDef)):
-            names.add(n.name)
-        elif isinstance(n, ast.Assign):
-            for t in n.targets:
-                if isinstance(t, ast.Name):
-                    names.add(t.id)
-    return {x for x in names if not x.startswith("_")}
+with open(os.path.join(GOLDEN, "boundary_names.json")) as _f:
+    NAMES = json.load(_f)
 
 
 def collect_uses():
     """-> {(module, name): [caller, ...]}"""
-    uses = {}
-    helpers_ns = _public_namespace(os.path.join(REF, "helpers.py"))
-    for fn in CALLERS:
-        path = os.path.join(REF, fn)
-        if not os.path.exists(path):
-            continue
-        tree = ast.parse(open(path).read())
-        star = set()
-        for n in ast.walk(tree):
-            if isinstance(n, ast.ImportFrom) and n.module in MODS:
-                for a in n.names:
-                    if a.name == "*":
-                        star.add(n.module)
-                    else:
-                        uses.setdefault((n.module, a.name), []).append(fn)
-            elif isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id in MODS:
-                uses.setdefault((n.value.id, n.attr), []).append(fn)
-        if "helpers" in star:
-            bound = _module_bindings(tree)
-            for n in ast.walk(tree):
-                if isinstance(n, ast.Name) and isinstance(n.ctx, ast.Load) and n.id in helpers_ns and n.id not in bound:
-                    uses.setdefault(("helpers", n.id), []).append(fn)
-        assert star <= {"helpers"}, f"{fn}: star import of {star} not modelled"
+    uses = {(m, n): list(callers) for m, n, callers in NAMES["uses"]}
+    assert all(m in MODS for m, _ in uses), "fixture names a module this repo does not shadow"
     return uses
 
 
@@ -136,7 +79,7 @@ def test_every_name_the_reference_callers_import_is_exported():
 def test_star_import_of_helpers_hands_on_the_same_names():
     """`from helpers import *` must leak what upstream leaks (minus the allow-list): the shim's `__all__` covers the
     reference helpers' whole public namespace except its `main` stub."""
-    ns = _public_namespace(os.path.join(REF, "helpers.py")) - {"main"}
+    ns = set(NAMES["helpers_namespace"]) - {"main"}
     shim = _shim("helpers")
     exported = set(getattr(shim, "__all__"))
     lost = {n for n in ns if n not in exported and ("helpers", n) not in ALLOW}
@@ -149,12 +92,7 @@ def test_star_import_of_helpers_hands_on_the_same_names():
 
 def test_instance_members_the_callers_reach_exist():
     """Methods / attributes the callers use on the objects behind the boundary (variable names as upstream spells them)."""
-    import re
-    diff_names, unet_names = set(), set()
-    for fn in CALLERS[:4]:
-        src = open(os.path.join(REF, fn)).read()
-        diff_names |= set(re.findall(r"\b(?:diff|diffusion)\.([A-Za-z_][A-Za-z_0-9]*)", src))
-        unet_names |= set(re.findall(r"\b(?:unet|ema|model)\.([A-Za-z_][A-Za-z_0-9]*)", src))
+    diff_names, unet_names = set(NAMES["diff_names"]), set(NAMES["unet_names"])
     assert {"forward_backward", "detection_B", "p_loss", "calc_total_vlb", "num_timesteps"} <= diff_names
     import numpy as np
     GD, UN = _shim("GaussianDiffusion"), _shim("UNet")

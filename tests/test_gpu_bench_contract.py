@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ def run_bench(*extra):
 
 
 def test_bench_line_small_config():
-    d = run_bench("--config", "c1", "--no-cpu-baseline")
+    d = run_bench("--config", "c1", "--no-cpu-baseline", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
@@ -46,7 +47,7 @@ def test_bench_line_small_config():
 
 
 def test_bench_cpu_baseline_object():
-    d = run_bench("--config", "c1")
+    d = run_bench("--config", "c1", "--full")
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["unit"] == "images/s" and c["value"] > 0 and "sample" in c
     assert d["value"] > c["value"]
@@ -57,11 +58,11 @@ def test_bench_cpu_baseline_object():
 
 
 def test_bench_line_simplex_and_training_configs():
-    d = run_bench("--config", "c4", "--no-cpu-baseline")
+    d = run_bench("--config", "c4", "--no-cpu-baseline", "--full")
     assert d["unit"] == "voxels/s" and d["dtype"] == "f64" and d["value"] > 1e9
     r = d["roofline"]
     assert r["bound"] == "fp64-alu" and 0 < r["frac"] <= 1.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
-    d = run_bench("--config", "c3", "--batch", "1", "--no-cpu-baseline")
+    d = run_bench("--config", "c3", "--batch", "1", "--no-cpu-baseline", "--full")
     assert d["unit"] == "images/s" and d["config"]["loss_finite"] is True and d["value"] > 0
     r = d["roofline"]
     # the dominant contraction class of the training step (forward + data-gradient F(4x4,3x3), or one of the weight-gradient
@@ -75,7 +76,7 @@ def test_bench_line_simplex_and_training_configs():
 def test_bench_line_detection_sweep():
     """`--config det`: one image's detection_B sweep end to end (every (t_distance, avg) chain slot-batched + on-device anomaly
     maps), a side line.  Shortened sweep here: range(50, 150, 50) x 5 chains."""
-    d = run_bench("--config", "det", "--no-cpu-baseline", "--det-end", "150")
+    d = run_bench("--config", "det", "--no-cpu-baseline", "--det-end", "150", "--full")
     assert d["unit"] == "chain-steps/s" and d["value"] > 0 and d["config"]["output_finite"] is True
     cf = d["config"]
     assert cf["chains_per_setting"] == 5 and cf["settings"] == [50, 100] and cf["chains"] == 10 and cf["chain_steps_per_image"] == 750
@@ -86,8 +87,28 @@ def test_bench_line_detection_sweep():
     r = d["roofline"]
     assert r["bound"] == "mfma" and r["batch"] == cf["slots"] and 0 < r["frac"] <= 1.0 and cf["metric_version"] == 2
     assert r["class_ms_per_step"]["winograd_f43"] > 0 and "peak_at_sustained_clock" in r
-    d = run_bench("--config", "c4", "--no-cpu-baseline", "--steps", "3", "--warmup", "1")
+    d = run_bench("--config", "c4", "--no-cpu-baseline", "--steps", "3", "--warmup", "1", "--full")
     assert abs(d["roofline"]["peak_no_fma"] - d["roofline"]["peak"] / 2) < 1e-9 and 0 < d["roofline"]["frac_of_peak_no_fma"] <= 1.0
+
+
+def test_plain_bench_line_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline only (no instrumented pass, CPU baseline or extra leg); --dump-outputs writes
+    the chain state of the last timed step; --steps sets the timed steps even past the T = 1000 steps of one chain (the chain
+    restarts from x_T outside the clock); two runs with the same arguments compute the same outputs."""
+    lines = []
+    for run in ("a", "b"):
+        lines.append(run_bench("--config", "c1", "--dump-outputs", str(tmp_path / run)))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert not any(k in d for k in ("roofline", "cpu_baseline", "extra"))
+    a, b = (np.load(tmp_path / run / "sample.npy") for run in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (1, 1, 64, 64) and np.isfinite(a).all()
+    assert np.array_equal(a, b)
+    d = run_bench("--config", "c1", "--steps", "1010", "--warmup", "2", "--dump-outputs", str(tmp_path / "long"))
+    assert d["steps"] == 1010 and d["warmup"] == 2 and d["config"]["output_finite"] is True
+    assert np.isfinite(np.load(tmp_path / "long" / "sample.npy")).all()
 
 
 def test_bench_under_torchrun_one_rank_uses_rccl():
@@ -96,7 +117,7 @@ def test_bench_under_torchrun_one_rank_uses_rccl():
     env = dict(os.environ, ANODDPM_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", "29544", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "c1", "--no-prof"],
+                          "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "c1", "--no-prof", "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]

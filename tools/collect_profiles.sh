@@ -17,7 +17,7 @@ rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU
 unset ANODDPM_NO_GRAPH
 cd $GRAFT_REPO_ROOT
 # per-layer profile from the executor's own HIP events (round 4: bench.py --dump-layers; split-K tails are inside their layer's time)
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra --dump-layers $OUT/c2_igemm_by_layer.csv > /dev/null 2> $OUT/by_layer.err
+python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra --dump-layers $OUT/c2_igemm_by_layer.csv > /dev/null 2> $OUT/by_layer.err
 # one step as a timeline (kernel, start, duration) from the eager trace
 python tools/timeline.py $(find $OUT/c2_stats -name "*kernel_trace.csv" | head -1) -2 $OUT/c2_step_timeline.csv > $OUT/c2_step_timeline_summary.txt 2>> $OUT/by_layer.err
 # keep what is small: summaries only (the raw traces can be hundreds of MB)
@@ -35,9 +35,9 @@ done
 python tools/traffic_from_pmc.py traffic profiles/r3_hbm_calibration.json $OUT/c2_fetch_by_kernel.csv $OUT/c2_write_by_kernel.csv 4 "${2:-}" > $OUT/traffic_c2.json
 # the bench lines last: roofline.traffic of the c2 line reads the traffic file of THIS build (committed later under the same name)
 cp $OUT/traffic_c2.json profiles/${1:-prof}_traffic_c2.json
-python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err
-python bench.py --config c3 --steps 5 --warmup 2 > $OUT/bench_c3.json 2> $OUT/bench_c3.err
-python bench.py --config c4 --steps 10 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
-python bench.py --config c5 --steps 10 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
-python bench.py --config det --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_det.json 2> $OUT/bench_det.err   # a step = one image's whole sweep (~35 s)
+python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+python bench.py --full --config c3 --steps 5 --warmup 2 > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+python bench.py --full --config c4 --steps 10 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+python bench.py --full --config c5 --steps 10 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+python bench.py --full --config det --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_det.json 2> $OUT/bench_det.err   # a step = one image's whole sweep (~35 s)
 ls -la $OUT
