@@ -32,6 +32,7 @@ SOURCES = {
     "executor.hip": [],
     "optim.hip": [],
     "metrics.hip": ["-ffp-contract=off"],
+    "roc.hip": ["-ffp-contract=off"],
     "wgrad.hip": [],
     "wgrad43.hip": [],
     "gn_backward.hip": [],

@@ -93,7 +93,7 @@ extern "C" int anoddpm_ablate_build(void)
 #endif
 }
 
-extern "C" int anoddpm_abi_version(void) { return 24; }
+extern "C" int anoddpm_abi_version(void) { return 25; }
 
 extern "C" const char *anoddpm_last_error(void) { return g_err; }
 
@@ -230,6 +230,7 @@ extern "C" int anoddpm_struct_size(int32_t which)
         case 31: return (int)sizeof(anoddpm_linear_bwd_batch_args);
         case 32: return (int)sizeof(anoddpm_loss_args);
         case 33: return (int)sizeof(anoddpm_dropout_args);
+        case 34: return (int)sizeof(anoddpm_roc_args);
         default: return -1;
     }
 }

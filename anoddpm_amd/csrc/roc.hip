@@ -1,0 +1,295 @@
+// ROC curve and AUC of batched anomaly maps -- replaces, per segment (one flattened map, or a whole concatenated data set),
+//   sklearn.metrics.roc_curve(mask, sqerr)                evaluation.py:79-82; detection.py:230, 553, 569, 583
+//   sklearn.metrics.auc(fpr, tpr)                         evaluation.py:85-87; detection.py:231, 554, 570, 584
+// One workgroup of 16 waves per segment, one launch, no cross-workgroup ordering of any kind:
+//   1. key = (bits(score + 0.0f) << 1) | (mask != 0): for finite score >= 0 the bit pattern is monotone and the sign bit is free,
+//      so one 32-bit word sorts by score and keeps the label (negatives before positives inside equal scores)
+//   2. LSD radix sort, 8 bits per pass, global ping-pong buffers (a 256^2 segment is 256 KB of keys: L2-resident).  Every wave owns
+//      a contiguous chunk of the segment and a private LDS histogram row, so the scatter is stable without a barrier inside the
+//      loops: the rank of a key among the equal digits of its 64-lane group comes from eight ballots.  A pass whose histogram
+//      has a single non-empty bin is skipped
+//   3. runs of equal score: their start position and the number of positives below them, compacted in ascending order
+//   4. twoU = sum_v P_v * (2 * N_below(v) + N_v) in uint64 (the tie-corrected Mann-Whitney statistic = the trapezoid area under
+//      sklearn's curve, independent of summation order), AUC = twoU / (2 P N) in fp64
+//   5. optionally the curve points sklearn keeps (drop_intermediate: first, last, and every point where the second difference of
+//      fps or tps is non-zero, i.e. where the next lower run has other counts), written compactly from the highest score down
+// All counters are integers: the result is deterministic.  Compiled with -ffp-contract=off like the other metric kernels.
+#include "common.h"
+
+namespace {
+
+constexpr int THREADS = 1024, WAVES = THREADS / 64, RADIX = 256, UNROLL = 4;
+
+__device__ __forceinline__ void wave_sync()
+{
+    // same-wave LDS hand-off (one lane writes what other lanes of the wave read): the hardware runs a wave's LDS operations in
+    // order; this only keeps the compiler from moving them across the point or into divergent branches
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// exclusive prefix of v over the workgroup in thread order (two barriers; wsum: WAVES words of LDS)
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *wsum)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(incl, off);
+        if (lane >= off) incl += t;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int w = 0; w < wave; ++w) base += wsum[w];
+    __syncthreads();
+    return base + incl - v;
+}
+
+// sum of the per-wave totals below `wave`, and of all of them
+__device__ __forceinline__ void wave_carry(const uint32_t *wtot, int wave, uint32_t &below, uint32_t &total)
+{
+    below = 0;
+    total = 0;
+    for (int w = 0; w < WAVES; ++w) {
+        const uint32_t t = wtot[w];
+        if (w < wave) below += t;
+        total += t;
+    }
+}
+
+// run r (ascending score) of the compacted run list: does sklearn's drop_intermediate keep its curve point?
+__device__ __forceinline__ bool keep_point(const uint32_t *runpos, const uint32_t *runtp, uint32_t r, uint32_t R)
+{
+    if (r == 0 || r == R - 1) return true;                       // last / first point of the curve
+    const uint32_t rsm = runpos[r - 1], rs = runpos[r], rs1 = runpos[r + 1];
+    const uint32_t tpm = runtp[r - 1], tp = runtp[r], tp1 = runtp[r + 1];
+    // second difference at this point = counts of the next lower run minus the counts of this run
+    return (tp1 - tp) != (tp - tpm) || (rs1 - rs) != (rs - rsm);
+}
+
+__global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, int64_t seg_words)
+{
+    __shared__ uint32_t hist[WAVES * RADIX];                     // wave-private rows: digit counts, then scatter offsets
+    __shared__ uint32_t wsum[WAVES], wtot_p[WAVES], wtot_b[WAVES];
+    __shared__ unsigned long long wacc[WAVES];
+    __shared__ uint32_t s_status, s_skip;
+
+    const int seg = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t n = (uint32_t)a.n;
+    const float *__restrict__ score = a.score + (int64_t)seg * a.score_stride;
+    const float *__restrict__ mask = a.mask + (int64_t)seg * a.mask_stride;
+    uint32_t *ws = static_cast<uint32_t *>(a.workspace) + (int64_t)seg * 3 * seg_words;
+    uint32_t *src = ws, *dst = ws + seg_words, *third = ws + 2 * seg_words;
+    const uint64_t lt = (1ull << lane) - 1ull;
+
+    // contiguous chunk of this wave, a multiple of 64 long (n < 2^31: no 32-bit overflow below)
+    const uint32_t chunk = ((n + WAVES - 1) / WAVES + 63u) & ~63u;
+    const uint32_t c0 = min((uint32_t)wave * chunk, n), c1 = min(c0 + chunk, n);
+
+    // ---- 1. keys + precondition check
+    if (tid == 0) s_status = 0;
+    __syncthreads();
+    {
+        uint32_t st = 0;
+        for (uint32_t i = tid; i < n; i += THREADS) {
+            const float s = score[i], m = mask[i];
+            if (s != s) st |= ANODDPM_ROC_NAN;
+            else if (s == INFINITY || s == -INFINITY) st |= ANODDPM_ROC_INF;
+            if (s < 0.0f) st |= ANODDPM_ROC_NEGATIVE;
+            if (!(m == 0.0f || m == 1.0f)) st |= ANODDPM_ROC_BAD_MASK;
+            src[i] = (__float_as_uint(s + 0.0f) << 1) | (m != 0.0f ? 1u : 0u);     // -0.0 + 0.0 = +0.0
+        }
+        if (st) atomicOr(&s_status, st);
+    }
+    __syncthreads();
+
+    // ---- 2. LSD radix sort of src[0..n)
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = pass * 8;
+        for (int i = tid; i < WAVES * RADIX; i += THREADS) hist[i] = 0;
+        if (tid == 0) s_skip = 0;
+        __syncthreads();
+        uint32_t *wh = hist + wave * RADIX;
+        for (uint32_t i = c0 + lane; i < c1; i += 64) atomicAdd(&wh[(src[i] >> shift) & 255u], 1u);
+        __syncthreads();
+        // exclusive scan in (digit, wave) order: thread t owns digit t / 4 and the four waves (t % 4) * 4 ...
+        {
+            const int d = tid >> 2, w0 = (tid & 3) * 4;
+            uint32_t h[4], sum = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { h[k] = hist[(w0 + k) * RADIX + d]; sum += h[k]; }
+            uint32_t dt = sum;
+            dt += __shfl_xor(dt, 1);
+            dt += __shfl_xor(dt, 2);
+            if (dt == n && (tid & 3) == 0) s_skip = 1;           // every key has this digit: the pass would move nothing
+            uint32_t ex = block_exclusive_scan(sum, wsum);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { hist[(w0 + k) * RADIX + d] = ex; ex += h[k]; }
+        }
+        __syncthreads();
+        const bool skip = s_skip != 0;
+        if (!skip) {
+            for (uint32_t base = c0; base < c1; base += 64 * UNROLL) {
+                uint32_t key[UNROLL];
+                bool valid[UNROLL];
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) {
+                    const uint32_t i = base + u * 64 + lane;
+                    valid[u] = i < c1;
+                    key[u] = valid[u] ? src[i] : 0u;
+                }
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) {
+                    if (base + u * 64 >= c1) break;              // wave-uniform
+                    const uint32_t dg = (key[u] >> shift) & 255u;
+                    uint64_t m = __ballot(valid[u]);
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) {
+                        const bool bit = (dg >> b) & 1u;
+                        const uint64_t bal = __ballot(valid[u] && bit);
+                        m &= bit ? bal : ~bal;
+                    }                                            // m: the valid lanes of this group with my digit
+                    const uint32_t rank = __popcll(m & lt), cnt = __popcll(m);
+                    uint32_t pos = 0;
+                    if (valid[u]) pos = wh[dg] + rank;
+                    wave_sync();
+                    if (valid[u] && rank == cnt - 1) wh[dg] = pos + 1;
+                    wave_sync();
+                    if (valid[u] && pos < n) dst[pos] = key[u];   // pos < n always; the guard keeps a bad offset inside the buffer
+                }
+            }
+            uint32_t *t = src;
+            src = dst;
+            dst = t;
+        }
+        __syncthreads();                                         // the scattered keys are visible to every wave; hist is free
+    }
+    uint32_t *runpos = dst, *runtp = third;                      // seg_words >= n + 1 each
+
+    // ---- 3. runs of equal score, ascending: runpos[r] = first position, runtp[r] = positives below it
+    uint32_t P, R;
+    {
+        uint32_t cp = 0, cb = 0;
+        for (uint32_t base = c0; base < c1; base += 64) {
+            const uint32_t i = base + lane;
+            const bool valid = i < c1;
+            const uint32_t k = valid ? src[i] : 0u, kp = (valid && i > 0) ? src[i - 1] : 0u;
+            cp += __popcll(__ballot(valid && (k & 1u)));
+            cb += __popcll(__ballot(valid && (i == 0 || (k >> 1) != (kp >> 1))));
+        }
+        if (lane == 0) { wtot_p[wave] = cp; wtot_b[wave] = cb; }
+        __syncthreads();
+        uint32_t carry_p, carry_b;
+        wave_carry(wtot_p, wave, carry_p, P);
+        wave_carry(wtot_b, wave, carry_b, R);
+        for (uint32_t base = c0; base < c1; base += 64) {
+            const uint32_t i = base + lane;
+            const bool valid = i < c1;
+            const uint32_t k = valid ? src[i] : 0u, kp = (valid && i > 0) ? src[i - 1] : 0u;
+            const bool bnd = valid && (i == 0 || (k >> 1) != (kp >> 1));
+            const uint64_t bp = __ballot(valid && (k & 1u)), bb = __ballot(bnd);
+            if (bnd) {
+                const uint32_t r = carry_b + __popcll(bb & lt);
+                runpos[r] = i;
+                runtp[r] = carry_p + __popcll(bp & lt);
+            }
+            carry_p += __popcll(bp);
+            carry_b += __popcll(bb);
+        }
+        if (tid == 0) { runpos[R] = n; runtp[R] = P; }           // sentinel: the end of the last run
+        __syncthreads();
+    }
+
+    // ---- 4. + 5. per run, from the highest score down (q = R - 1 - r): its term of twoU, and its curve point if kept
+    const bool want_curve = a.curve_fps != nullptr;
+    const uint32_t qchunk = ((R + WAVES - 1) / WAVES + 63u) & ~63u;
+    const uint32_t q0 = min((uint32_t)wave * qchunk, R), q1 = min(q0 + qchunk, R);
+    uint32_t carry_k = 0, K = 0;
+    if (want_curve) {
+        uint32_t ck = 0;
+        for (uint32_t base = q0; base < q1; base += 64) {
+            const uint32_t q = base + lane;
+            const bool keep = q < q1 && keep_point(runpos, runtp, R - 1 - q, R);
+            ck += __popcll(__ballot(keep));
+        }
+        if (lane == 0) wtot_p[wave] = ck;                        // free since the barrier that ended step 3
+        __syncthreads();
+        wave_carry(wtot_p, wave, carry_k, K);
+    }
+    unsigned long long acc = 0;
+    for (uint32_t base = q0; base < q1; base += 64) {
+        const uint32_t q = base + lane;
+        const bool valid = q < q1;
+        uint32_t rs = 0, tp = 0;
+        bool keep = false;
+        if (valid) {
+            const uint32_t r = R - 1 - q;
+            rs = runpos[r];
+            tp = runtp[r];
+            const uint32_t pr = runtp[r + 1] - tp, nr = (runpos[r + 1] - rs) - pr;
+            acc += (unsigned long long)pr * (2ull * (rs - tp) + nr);     // rs - tp = negatives with a lower score
+            keep = want_curve && keep_point(runpos, runtp, r, R);
+        }
+        if (want_curve) {
+            const uint64_t bk = __ballot(keep);
+            const uint64_t idx = (uint64_t)carry_k + __popcll(bk & lt);
+            if (keep && (int64_t)idx < a.curve_cap) {
+                const int64_t o = (int64_t)seg * a.curve_cap + (int64_t)idx;
+                const uint32_t tps = P - tp;
+                a.curve_tps[o] = (int32_t)tps;
+                a.curve_fps[o] = (int32_t)((n - rs) - tps);
+                a.curve_thr[o] = __uint_as_float(src[rs] >> 1);
+            }
+            carry_k += __popcll(bk);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if (lane == 0) wacc[wave] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long two_u = 0;
+        for (int w = 0; w < WAVES; ++w) two_u += wacc[w];
+        const uint32_t N = n - P;
+        a.auc[seg] = (P == 0 || N == 0) ? (double)NAN : (double)two_u / (2.0 * (double)P * (double)N);
+        int64_t *c = a.counts + (int64_t)seg * 4;
+        c[0] = P;
+        c[1] = N;
+        c[2] = (int64_t)two_u;
+        c[3] = R;
+        a.status[seg] = (int32_t)(s_status | ((want_curve && (int64_t)K > a.curve_cap) ? ANODDPM_ROC_CURVE_TRUNCATED : 0u));
+        if (want_curve) a.curve_len[seg] = (int32_t)K;
+    }
+}
+
+int64_t seg_words_of(int64_t n) { return (n + 1 + 63) / 64 * 64; }
+
+}  // namespace
+
+extern "C" int64_t anoddpm_roc_workspace_bytes(int32_t S, int64_t n)
+{
+    if (S < 1 || n < 1 || n >= ((int64_t)1 << 31)) return -1;
+    return (int64_t)S * 3 * seg_words_of(n) * (int64_t)sizeof(uint32_t);
+}
+
+extern "C" int anoddpm_roc_auc(const anoddpm_roc_args *a, void *stream)
+{
+    using namespace anoddpm;
+    ANODDPM_REQUIRE(a != nullptr, "roc_auc: null args");
+    ANODDPM_REQUIRE(a->score && a->mask && a->workspace && a->auc && a->counts && a->status, "roc_auc: null pointer");
+    ANODDPM_REQUIRE(a->S >= 1, "roc_auc: S must be >= 1");
+    ANODDPM_REQUIRE(a->n >= 1, "roc_auc: n must be >= 1");
+    ANODDPM_REQUIRE(a->n < ((int64_t)1 << 31), "roc_auc: n must be below 2^31 (32-bit positions, uint64 twoU)");
+    ANODDPM_REQUIRE(a->S == 1 || a->score_stride >= a->n, "roc_auc: score segments overlap (score_stride < n)");
+    ANODDPM_REQUIRE(a->S == 1 || a->mask_stride == 0 || a->mask_stride >= a->n, "roc_auc: mask_stride must be 0 (shared mask) or >= n");
+    ANODDPM_REQUIRE(a->workspace_bytes >= anoddpm_roc_workspace_bytes(a->S, a->n), "roc_auc: workspace too small");
+    const bool any_curve = a->curve_fps || a->curve_tps || a->curve_thr || a->curve_len;
+    if (any_curve) {
+        ANODDPM_REQUIRE(a->curve_fps && a->curve_tps && a->curve_thr && a->curve_len, "roc_auc: curve output needs curve_fps, curve_tps, curve_thr and curve_len");
+        ANODDPM_REQUIRE(a->curve_cap >= 2, "roc_auc: curve capacity must be >= 2 points per segment");
+    }
+    hipLaunchKernelGGL(roc_auc_kernel, dim3(a->S), dim3(THREADS), 0, as_stream(stream), *a, seg_words_of(a->n));
+    return check_launch("roc_auc");
+}

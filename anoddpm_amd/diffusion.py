@@ -983,13 +983,25 @@ class GaussianDiffusionModel:
         rec = dict(extra)
         rec.update(output=output, mean=maps["mean"], mse=maps["mse_img"], threshold=maps["thr_img"],
                    counts=counts)
+        rec["auc"] = rec["auc_status"] = None                       # filled by _attach_auc when there is a mask
         return rec, maps
+
+    @staticmethod
+    def _attach_auc(records, sqerrs, mask):
+        """detection.py:230-231 for every setting of a sweep in ONE batched launch: `auc` (fp64 device scalar; NaN when the mask has
+        one class only or when `auc_status`, the kernel's status word, is non-zero) per record.  Never raises, never synchronises."""
+        if mask is None or not records:
+            return
+        from . import metrics
+        auc, status = metrics.roc_auc(mask, torch.stack([s.reshape(-1) for s in sqerrs]), batched=True, return_status=True)
+        for j, rec in enumerate(records):
+            rec["auc"], rec["auc_status"] = auc[j], status[j]
 
     def detection_A(self, model, x_0, args, file, mask, total_avg=2):
         """GaussianDiffusion.py:480-529: simplex frequencies 2^7..2^1 x t_distance 50..0.6T step 50, `total_avg` chains each -- all
         of them one batched reverse loop (`_run_chains`).  Returns None as upstream; the per-setting results upstream only plots
         (the figure files are file / plot I/O, out of scope) are kept in `self.last_detection`, in upstream's loop order: mean /
-        mse / threshold images and the segmentation counts, on the device."""
+        mse / threshold images, the segmentation counts and (with a mask) the ROC AUC of the squared-error map, on the device."""
         settings, dists, noise = [], [], []
         for i in range(7, 0, -1):
             freq = 2 ** i
@@ -999,10 +1011,12 @@ class GaussianDiffusionModel:
                 dists += [t_distance] * total_avg
                 noise += self._forward_noise(x_0, t_distance, total_avg)
         outputs = self._run_chains(model, x_0, dists, torch.cat(noise) if noise else None)
-        self.last_detection = []
+        self.last_detection, sqerrs = [], []
         for j, extra in enumerate(settings):
-            rec, _ = self._detection_record(x_0, outputs[j * total_avg:(j + 1) * total_avg].clone(), mask, extra)
+            rec, maps = self._detection_record(x_0, outputs[j * total_avg:(j + 1) * total_avg].clone(), mask, extra)
             self.last_detection.append(rec)
+            sqerrs.append(maps["sqerr"])
+        self._attach_auc(self.last_detection, sqerrs, mask)
 
     def detection_B(self, model, x_0, args, file, mask, denoise_fn="gauss", total_avg=5):
         """GaussianDiffusion.py:531-594: t_distance 50..end step 50 with gaussian or 6-octave simplex forward noise,
@@ -1023,9 +1037,11 @@ class GaussianDiffusionModel:
             noise += self._forward_noise(x_0, t_distance, total_avg)
         outputs = self._run_chains(model, x_0, dists, torch.cat(noise) if noise else None)
         dice_coeff = []
-        self.last_detection = []
+        self.last_detection, sqerrs = [], []
         for j, t_distance in enumerate(settings):
-            rec, _ = self._detection_record(x_0, outputs[j * total_avg:(j + 1) * total_avg].clone(), mask, {"t_distance": t_distance})
+            rec, maps = self._detection_record(x_0, outputs[j * total_avg:(j + 1) * total_avg].clone(), mask, {"t_distance": t_distance})
             self.last_detection.append(rec)
+            sqerrs.append(maps["sqerr"])
             dice_coeff.append(None)                                 # evaluation.heatmap() returns None (evaluation.py:12-22)
+        self._attach_auc(self.last_detection, sqerrs, mask)
         return dice_coeff

@@ -4,9 +4,20 @@
 
 Reference call sites: detection.py:229-250 (per test image: squared error -> threshold 0.5 -> dice / precision /
 recall / IoU / FPR), GaussianDiffusion.py:517-520, 572-583 (mean of the averaged chains, `mse` / threshold images).
-ROC / AUC (sklearn) and SSIM (skimage) stay on the host as upstream (evaluation.py:46-47, 78-87).
+SSIM (skimage) stays on the host as upstream (evaluation.py:46-47).
 
-`anomaly_metrics` is the native entry: everything the metric loop needs from one launch and one 96-byte D2H copy.
+ROC / AUC (evaluation.py:78-87: sklearn's `roc_curve` + `auc` on the flattened mask and squared error) run on the device
+(`anoddpm_roc_auc`, csrc/roc.hip): per segment one workgroup sorts 32-bit keys `(bits(score) << 1) | label`, walks the runs of equal
+score and forms the AUC as the integer Mann-Whitney statistic `twoU / (2 P N)` -- exactly the trapezoid area under sklearn's curve,
+deterministic, no host sort.  `roc_auc` returns the `[S]` AUCs of a batch without a host synchronisation, `roc_points` the curve
+points sklearn keeps (`drop_intermediate`), `ROC_AUC` on device tensors sklearn's `(fpr, tpr, thresholds)` triple bit for bit
+(the host only prepends `(0, 0, inf)` and divides the integer counts in fp64).  Scores must be finite and >= 0 (squared errors
+are; -0.0 is reported as +0.0) and masks 0 / 1: anything else sets a status word, which `ROC_AUC` / `roc_points` turn into
+`ValueError` and `roc_auc` / `anomaly_metrics` / the detection records into `NaN` beside the status.  Host (numpy / CPU tensor)
+arguments of `ROC_AUC` and `AUC_score` go through sklearn as upstream; sklearn's UndefinedMetricWarning for an empty class is not
+re-issued by the native path (the arrays are NaN as sklearn's are).
+
+`anomaly_metrics` is the native entry: everything the metric loop needs from one launch and one 96-byte D2H copy (plus the AUC launch).
 The individual functions accept the reference's arguments; they use the fused pass when handed device tensors of
 the shapes the reference passes and raise `AnoddpmError` otherwise (no CPU path)."""
 import ctypes
@@ -14,9 +25,9 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import AnomalyArgs, check, current_stream, lib
+from ._lib import AnomalyArgs, RocArgs, check, current_stream, lib
 
-__all__ = ["anomaly_maps", "anomaly_metrics", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
+__all__ = ["anomaly_maps", "anomaly_metrics", "roc_auc", "roc_points", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
 
 NC = _lib.ANOMALY_NCOUNTS
@@ -79,16 +90,118 @@ def _ratios(c, smooth=0.000001):
     return out
 
 
+# ---------------------------------------------------------------------------------- ROC / AUC on the device
+_ROC_STATUS_TEXT = ((_lib.ROC_NAN, "NaN score"), (_lib.ROC_INF, "infinite score"), (_lib.ROC_NEGATIVE, "negative score"),
+                    (_lib.ROC_BAD_MASK, "mask value other than 0 and 1"), (_lib.ROC_CURVE_TRUNCATED, "curve buffer too small"))
+
+
+def _roc_status_text(status):
+    return ", ".join(t for bit, t in _ROC_STATUS_TEXT if status & bit)
+
+
+def _segments(x, S, name):
+    """x as fp32 rows of a [S, n] view with unit element stride: (tensor that owns the memory, n, row stride in elements)."""
+    _lib.require_cuda(x, name)
+    if x.dtype != torch.float32:
+        x = x.float()
+    x = x.reshape(S, -1)
+    n = x.shape[1]
+    if S == 1 or n == 1 or x.stride(1) != 1 or x.stride(0) < n:
+        x = x.contiguous()
+        return x, n, n
+    return x, n, x.stride(0)
+
+
+def _roc_launch(mask, score, batched, curve):
+    """One `anoddpm_roc_auc` launch.  score: [S, ...] when batched, else one segment; mask: like score, or the shape of one
+    segment (one mask shared by every segment).  Returns a dict of device tensors; nothing is copied to the host."""
+    if not isinstance(score, torch.Tensor) or not isinstance(mask, torch.Tensor):
+        raise TypeError("roc: mask and score must be device tensors")
+    S = score.shape[0] if batched else 1
+    if score.numel() == 0 or S < 1:
+        raise ValueError("roc: empty score")
+    sc, n, s_stride = _segments(score, S, "roc(score)")
+    if mask.numel() == S * n:
+        mk, _, m_stride = _segments(mask, S, "roc(mask)")
+    elif mask.numel() == n:
+        mk, _, _ = _segments(mask, 1, "roc(mask)")
+        m_stride = 0
+    else:
+        raise ValueError(f"roc: mask of {mask.numel()} elements does not match score {tuple(score.shape)}")
+    if mk.device != sc.device:
+        raise ValueError("roc: mask and score are on different devices")
+    dev = sc.device
+    nbytes = lib().anoddpm_roc_workspace_bytes(S, n)
+    if nbytes < 0:
+        raise ValueError(f"roc: segment length {n} is outside [1, 2^31)")
+    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    out = {"auc": torch.empty((S,), dtype=torch.float64, device=dev),
+           "counts": torch.empty((S, 4), dtype=torch.int64, device=dev),
+           "status": torch.empty((S,), dtype=torch.int32, device=dev), "n": n}
+    a = RocArgs()
+    a.score, a.mask, a.workspace, a.workspace_bytes = sc.data_ptr(), mk.data_ptr(), ws.data_ptr(), nbytes
+    a.auc, a.counts, a.status = out["auc"].data_ptr(), out["counts"].data_ptr(), out["status"].data_ptr()
+    a.n, a.score_stride, a.mask_stride, a.S = n, s_stride, m_stride, S
+    if curve:
+        cap = max(n, 2)                                              # a segment has at most n distinct scores
+        out["fps"] = torch.empty((S, cap), dtype=torch.int32, device=dev)
+        out["tps"] = torch.empty((S, cap), dtype=torch.int32, device=dev)
+        out["thresholds"] = torch.empty((S, cap), dtype=torch.float32, device=dev)
+        out["len"] = torch.empty((S,), dtype=torch.int32, device=dev)
+        a.curve_fps, a.curve_tps, a.curve_thr = out["fps"].data_ptr(), out["tps"].data_ptr(), out["thresholds"].data_ptr()
+        a.curve_len, a.curve_cap = out["len"].data_ptr(), cap
+    with torch.cuda.device(dev):
+        check(lib().anoddpm_roc_auc(ctypes.byref(a), current_stream()), "roc_auc")
+    return out
+
+
+def _is_batched(score, batched):
+    return score.dim() >= 3 if batched is None else bool(batched)
+
+
+def roc_auc(mask, score, batched=None, return_status=False):
+    """AUC of the ROC curve of every segment: score [S, ...] (`batched`; the default takes tensors of three or more dimensions
+    as batches and anything smaller as one map), mask of the same shape or of one segment's shape (shared by all).  Returns an
+    [S] fp64 device tensor -- `auc(*roc_curve(mask_s.flatten(), score_s.flatten())[:2])` per segment -- without a host
+    synchronisation: NaN where a class is empty, and NaN where the inputs break the precondition (`return_status=True` also
+    returns the [S] int32 status words)."""
+    o = _roc_launch(mask, score, _is_batched(score, batched), curve=False)
+    auc = torch.where(o["status"] != 0, torch.full_like(o["auc"], float("nan")), o["auc"])
+    return (auc, o["status"]) if return_status else auc
+
+
+def roc_points(mask, score, batched=None):
+    """The ROC points sklearn's `roc_curve` keeps (`drop_intermediate=True`), per segment, from the highest threshold down and
+    without the `(0, 0, inf)` point it prepends: a list of dicts with `fps`, `tps` (int64 counts), `thresholds` (fp32), `auc`,
+    `P`, `N`, `twoU` (Python numbers).  Copies to the host; raises ValueError for inputs outside the precondition."""
+    o = _roc_launch(mask, score, _is_batched(score, batched), curve=True)
+    status, lens, counts, auc = o["status"].cpu(), o["len"].cpu(), o["counts"].cpu(), o["auc"].cpu()
+    for s, st in enumerate(status.tolist()):
+        if st:
+            raise ValueError(f"roc: segment {s}: {_roc_status_text(st)} (scores must be finite and >= 0, masks 0 or 1)")
+    res = []
+    for s, L in enumerate(lens.tolist()):
+        res.append({"fps": o["fps"][s, :L].cpu().numpy().astype("int64"), "tps": o["tps"][s, :L].cpu().numpy().astype("int64"),
+                    "thresholds": o["thresholds"][s, :L].cpu().numpy(), "auc": float(auc[s]),
+                    "P": int(counts[s, 0]), "N": int(counts[s, 1]), "twoU": int(counts[s, 2])})
+    return res
+
+
 def anomaly_metrics(real, recon, mask, threshold=0.5):
-    """dice / IoU / precision / recall / FPR / mse / PSNR of detection.py:229-250 from one launch.
-    Returns a dict of Python floats plus the maps (device tensors)."""
+    """dice / IoU / precision / recall / FPR / mse / PSNR of detection.py:229-250 from one launch, and the AUC of
+    detection.py:230-231 (the whole batch flattened into one curve, evaluation.py:81) from a second one.
+    Returns a dict of Python floats plus the maps (device tensors).  `AUC` is NaN when a class is empty or when `AUC_status`
+    (the status word of the ROC kernel) is non-zero; without a mask there is no AUC (NaN, status 0)."""
     maps, counts = anomaly_maps(real, recon, mask, threshold)
+    roc = _roc_launch(mask, maps["sqerr"], batched=False, curve=False) if mask is not None else None
     c = counts.cpu()
     r = {k: float(v) for k, v in _ratios(c).items() if k != "dice_per_image"}
     n_total = real.numel()
     mse = float(c[:, 9].sum()) / n_total
     r["mse"] = mse
     r["PSNR"] = float(20.0 * torch.log10(torch.tensor(float(c[:, 10].max())) / torch.sqrt(torch.tensor(mse)))) if mse > 0 else float("inf")
+    r["AUC_status"] = int(roc["status"].cpu()[0]) if roc is not None else 0
+    r["AUC"] = float(roc["auc"].cpu()[0]) if roc is not None and r["AUC_status"] == 0 else float("nan")
     r["maps"] = maps
     return r
 
@@ -162,7 +275,18 @@ def FPR(real_mask, recon_mask):
 
 
 def ROC_AUC(real_mask, square_error):
-    """evaluation.py:78-82 -- host-side (sklearn) as upstream."""
+    """evaluation.py:78-82.  Device tensors: the native sort (`roc_points` of the flattened inputs); the host prepends the
+    `(0, 0, inf)` point and divides the integer counts in fp64, which gives sklearn's `(fpr, tpr, thresholds)` bit for bit
+    (NaN arrays when a class is empty).  Host inputs (numpy arrays, CPU tensors): sklearn, as upstream."""
+    if isinstance(real_mask, torch.Tensor) and isinstance(square_error, torch.Tensor) and real_mask.is_cuda and square_error.is_cuda:
+        import numpy as np
+        p = roc_points(real_mask, square_error, batched=False)[0]
+        fps = np.r_[0.0, p["fps"].astype(np.float64)]
+        tps = np.r_[0.0, p["tps"].astype(np.float64)]
+        thresholds = np.r_[np.float32(np.inf), p["thresholds"]].astype(np.float32)
+        fpr = fps / fps[-1] if fps[-1] > 0 else np.repeat(np.nan, fps.shape)
+        tpr = tps / tps[-1] if tps[-1] > 0 else np.repeat(np.nan, tps.shape)
+        return fpr, tpr, thresholds
     from sklearn.metrics import roc_curve
     if isinstance(real_mask, torch.Tensor):
         return roc_curve(real_mask.detach().cpu().numpy().flatten(), square_error.detach().cpu().numpy().flatten())

@@ -531,6 +531,47 @@ typedef struct anoddpm_anomaly_args {
 
 int anoddpm_anomaly_map(const anoddpm_anomaly_args *a, void *stream);
 
+/* ------------------------------------------------------------------ ROC curve + AUC of anomaly maps
+ * Replaces sklearn.metrics.roc_curve / auc as the reference calls them on a flattened mask and squared-error map
+ * (evaluation.py:79-87 ROC_AUC / AUC_score; detection.py:230-231 and :553-554, :569-570, :583-584 per test image, :640-643
+ * for the concatenated data set).  S segments of n elements; one workgroup sorts one segment, one launch, deterministic.
+ *   score  fp32, finite and >= 0 (-0.0 counts as +0.0); mask fp32, 0 or 1.  Elements that break this set bits of status[s]
+ *          (ANODDPM_ROC_*); the other outputs of such a segment are not meaningful.
+ *   score_stride / mask_stride: elements between consecutive segments (>= n; mask_stride 0 = one mask for every segment)
+ *   auc[s]     twoU / (2 P N) in fp64, NaN when P == 0 or N == 0 (sklearn: NaN after a warning)
+ *   counts[s]  {P, N, twoU, number of distinct scores}; twoU = sum over distinct scores v of P_v * (2 * N_below(v) + N_v):
+ *              the tie-corrected Mann-Whitney statistic, exactly twice P N times the trapezoid area under sklearn's curve
+ *   curve_*    optional (all four or none): the points roc_curve keeps with drop_intermediate=True, from the highest score
+ *              down, WITHOUT the (0, 0, inf) point it prepends: curve_fps / curve_tps [S][curve_cap] counts, curve_thr
+ *              [S][curve_cap] thresholds, curve_len[s] = points of segment s.  A segment with more than curve_cap points
+ *              gets its first curve_cap points, its full count in curve_len and ANODDPM_ROC_CURVE_TRUNCATED; curve_cap = n
+ *              (at least 2) always suffices.
+ *   workspace  [dev] anoddpm_roc_workspace_bytes(S, n) bytes (three uint32 buffers of n + 1 words per segment)
+ * n < 2^31.  twoU is exact in uint64; its conversion to fp64 is exact up to 2^53 (n <= 2^26 always is). */
+#define ANODDPM_ROC_NAN 1
+#define ANODDPM_ROC_INF 2
+#define ANODDPM_ROC_NEGATIVE 4
+#define ANODDPM_ROC_BAD_MASK 8
+#define ANODDPM_ROC_CURVE_TRUNCATED 16
+typedef struct anoddpm_roc_args {
+    const float *score;             /* [dev] */
+    const float *mask;              /* [dev] */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    double *auc;                    /* [dev] [S] */
+    int64_t *counts;                /* [dev] [S][4] */
+    int32_t *status;                /* [dev] [S] */
+    int32_t *curve_fps, *curve_tps; /* [dev] [S][curve_cap] or NULL */
+    float *curve_thr;               /* [dev] [S][curve_cap] or NULL */
+    int32_t *curve_len;             /* [dev] [S] or NULL */
+    int64_t curve_cap;
+    int64_t n, score_stride, mask_stride;
+    int32_t S;
+} anoddpm_roc_args;
+
+int anoddpm_roc_auc(const anoddpm_roc_args *a, void *stream);
+int64_t anoddpm_roc_workspace_bytes(int32_t S, int64_t n);   /* HOST function; -1 for S < 1, n < 1 or n >= 2^31 */
+
 /* Variational-bound terms of one reverse step (GaussianDiffusion.py:384-397 calc_vlb_xt, and the two MSE curves of
  * calc_total_vlb :445-478): per sample b
  *   out[0*B + b] = mean_flat( t==0 ? -discretised_gaussian_log_likelihood(x_0; mean, 0.5*logvar)
