@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ANODDPM_LIB_TAG=<tag>: load lib/libanoddpm_hip_<tag>.so instead -- a second build of the same sources with other compiler flags
 # (ANODDPM_BUILD_TAG / ANODDPM_EXTRA_FLAGS of anoddpm_amd.build), for A/B measurements of one gpurun session.  Same ABI, same checks.
 SO_PATH = os.path.join(_HERE, "lib", "libanoddpm_hip%s.so" % ("_" + os.environ["ANODDPM_LIB_TAG"] if os.environ.get("ANODDPM_LIB_TAG") else ""))
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 OP_IGEMM, OP_GN_STATS, OP_SOFTMAX, OP_RESAMPLE, OP_LINEAR, OP_POSEMB, OP_STEM, OP_LAYOUT, OP_CHAN_STATS, OP_GN_FINALIZE, OP_HEAD = range(1, 12)
 (OP_WGRAD3, OP_WGRAD1, OP_GN_BWD, OP_PACK, OP_SOFTMAX_BWD, OP_TRANSPOSE, OP_LINEAR_BWD, OP_STEM_BWD, OP_HEAD_BWD,
@@ -254,14 +254,23 @@ class RocArgs(Structure):
                 ("curve_cap", c_int64), ("n", c_int64), ("score_stride", c_int64), ("mask_stride", c_int64), ("S", c_int32)]
 
 
+class SsimArgs(Structure):
+    _fields_ = [("real", c_void_p), ("recon", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64),
+                ("mssim", c_void_p), ("map", c_void_p), ("real_stride", c_int64), ("recon_stride", c_int64),
+                ("cn", c_double), ("data_range", c_double), ("K1", c_double), ("K2", c_double),
+                ("S", c_int32), ("C", c_int32), ("H", c_int32), ("W", c_int32), ("win", c_int32), ("mode", c_int32)]
+
+
 ANOMALY_NCOUNTS = 12
 ANOMALY_BLOCKS = 64
 ROC_NAN, ROC_INF, ROC_NEGATIVE, ROC_BAD_MASK, ROC_CURVE_TRUNCATED = 1, 2, 4, 8, 16      # bits of anoddpm_roc_args.status
+SSIM_UNIFORM, SSIM_GAUSSIAN = 0, 1                                                      # anoddpm_ssim_args.mode
+SSIM_MAX_WIN = 15
 
 _STRUCTS = [SimplexArgs, PUpdateArgs, IgemmArgs, GnArgs, SoftmaxArgs, ResampleArgs, LinearArgs,
             PosembArgs, StemArgs, LayoutArgs, Op, AdamwArgs, ChanStatsArgs, GnFinalizeArgs, HeadArgs, AnomalyArgs, VlbArgs, WgradArgs, GnBwdArgs,
             Wgrad1Args, PackArgs, SoftmaxBwdArgs, TransposeArgs, LinearBwdArgs, StemBwdArgs, HeadBwdArgs, ColsumFoldArgs,
-            MriSliceArgs, ResizeArgs, AttentionArgs, PackBatchArgs, LinearBwdBatchArgs, LossArgs, DropoutArgs, RocArgs]
+            MriSliceArgs, ResizeArgs, AttentionArgs, PackBatchArgs, LinearBwdBatchArgs, LossArgs, DropoutArgs, RocArgs, SsimArgs]
 
 # every symbol include/anoddpm_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -277,6 +286,7 @@ SYMBOLS = [
     "anoddpm_linear_small_backward", "anoddpm_conv_stem_backward", "anoddpm_conv_head_backward", "anoddpm_colsum_fold",
     "anoddpm_volume_normalise", "anoddpm_mri_slice_prepare", "anoddpm_resize_bilinear_pil", "anoddpm_attention", "anoddpm_wgrad43_groups", "anoddpm_wgrad43_colsum_items", "anoddpm_pack_batch", "anoddpm_pack_job_blocks", "anoddpm_linear_small_backward_batch",
     "anoddpm_loss_forward", "anoddpm_loss_backward", "anoddpm_dropout", "anoddpm_roc_auc", "anoddpm_roc_workspace_bytes",
+    "anoddpm_ssim", "anoddpm_ssim_workspace_bytes",
 ]
 
 _lib = None
@@ -359,6 +369,9 @@ def lib():
     L.anoddpm_roc_auc.argtypes = [POINTER(RocArgs), c_void_p]
     L.anoddpm_roc_workspace_bytes.argtypes = [c_int32, c_int64]
     L.anoddpm_roc_workspace_bytes.restype = c_int64
+    L.anoddpm_ssim.argtypes = [POINTER(SsimArgs), c_void_p]
+    L.anoddpm_ssim_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
+    L.anoddpm_ssim_workspace_bytes.restype = c_int64
     L.anoddpm_vlb_terms.argtypes = [POINTER(VlbArgs), c_void_p]
     L.anoddpm_dropout.argtypes = [POINTER(DropoutArgs), c_void_p]
     L.anoddpm_loss_forward.argtypes = [POINTER(LossArgs), c_void_p]

@@ -93,7 +93,7 @@ extern "C" int anoddpm_ablate_build(void)
 #endif
 }
 
-extern "C" int anoddpm_abi_version(void) { return 25; }
+extern "C" int anoddpm_abi_version(void) { return 26; }
 
 extern "C" const char *anoddpm_last_error(void) { return g_err; }
 
@@ -231,6 +231,7 @@ extern "C" int anoddpm_struct_size(int32_t which)
         case 32: return (int)sizeof(anoddpm_loss_args);
         case 33: return (int)sizeof(anoddpm_dropout_args);
         case 34: return (int)sizeof(anoddpm_roc_args);
+        case 35: return (int)sizeof(anoddpm_ssim_args);
         default: return -1;
     }
 }

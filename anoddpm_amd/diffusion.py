@@ -984,6 +984,7 @@ class GaussianDiffusionModel:
         rec.update(output=output, mean=maps["mean"], mse=maps["mse_img"], threshold=maps["thr_img"],
                    counts=counts)
         rec["auc"] = rec["auc_status"] = None                       # filled by _attach_auc when there is a mask
+        rec["ssim"] = None                                          # filled by _attach_ssim
         return rec, maps
 
     @staticmethod
@@ -996,6 +997,21 @@ class GaussianDiffusionModel:
         auc, status = metrics.roc_auc(mask, torch.stack([s.reshape(-1) for s in sqerrs]), batched=True, return_status=True)
         for j, rec in enumerate(records):
             rec["auc"], rec["auc_status"] = auc[j], status[j]
+
+    @staticmethod
+    def _attach_ssim(records, x_0):
+        """detection.py:241-246 for every setting of a sweep in ONE launch: `ssim`, an fp64 device tensor `[B]`, the SSIM of every
+        image of `x_0` against the record's `mean` image (7 x 7 uniform window, data_range 2.0).  `x_0` is read in place by every
+        setting when B == 1 (segment stride 0).  Stays None for images smaller than the window.  Never synchronises."""
+        if not records or x_0.dim() != 4 or min(x_0.shape[-2:]) < 7:
+            return
+        from . import metrics
+        B = x_0.shape[0]
+        means = torch.stack([rec["mean"] for rec in records])       # [R, B, C, H, W]
+        real = x_0[0] if B == 1 else x_0.unsqueeze(0).expand_as(means)
+        val = metrics.ssim(real, means).reshape(len(records), B)
+        for j, rec in enumerate(records):
+            rec["ssim"] = val[j]
 
     def detection_A(self, model, x_0, args, file, mask, total_avg=2):
         """GaussianDiffusion.py:480-529: simplex frequencies 2^7..2^1 x t_distance 50..0.6T step 50, `total_avg` chains each -- all
@@ -1017,6 +1033,7 @@ class GaussianDiffusionModel:
             self.last_detection.append(rec)
             sqerrs.append(maps["sqerr"])
         self._attach_auc(self.last_detection, sqerrs, mask)
+        self._attach_ssim(self.last_detection, x_0)
 
     def detection_B(self, model, x_0, args, file, mask, denoise_fn="gauss", total_avg=5):
         """GaussianDiffusion.py:531-594: t_distance 50..end step 50 with gaussian or 6-octave simplex forward noise,
@@ -1044,4 +1061,5 @@ class GaussianDiffusionModel:
             sqerrs.append(maps["sqerr"])
             dice_coeff.append(None)                                 # evaluation.heatmap() returns None (evaluation.py:12-22)
         self._attach_auc(self.last_detection, sqerrs, mask)
+        self._attach_ssim(self.last_detection, x_0)
         return dice_coeff

@@ -4,7 +4,14 @@
 
 Reference call sites: detection.py:229-250 (per test image: squared error -> threshold 0.5 -> dice / precision /
 recall / IoU / FPR), GaussianDiffusion.py:517-520, 572-583 (mean of the averaged chains, `mse` / threshold images).
-SSIM (skimage) stays on the host as upstream (evaluation.py:46-47).
+
+SSIM (evaluation.py:46-47: skimage's `structural_similarity`) runs on the device too (`anoddpm_ssim`, csrc/ssim.hip): a workgroup
+stages a tile and its window halo of both images in LDS, forms the five window means in fp64 with separable passes in a fixed
+order and sums the interior of the similarity map; a second tiny launch folds the per-tile sums.  `ssim` returns the `[S]` fp64
+means of a batch (one `real` may be shared by all reconstructions) without a host synchronisation, deterministic, within 1e-10 of
+skimage on fp64 copies of the same images; `SSIM` on device tensors returns a Python float as skimage does.  `data_range`
+defaults to 2.0: the images live in [-1, 1], and that is what older skimage releases took from the float dtype for the
+upstream call (current releases refuse float images without it).  Host arguments of `SSIM` go through skimage as upstream.
 
 ROC / AUC (evaluation.py:78-87: sklearn's `roc_curve` + `auc` on the flattened mask and squared error) run on the device
 (`anoddpm_roc_auc`, csrc/roc.hip): per segment one workgroup sorts 32-bit keys `(bits(score) << 1) | label`, walks the runs of equal
@@ -25,9 +32,9 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import AnomalyArgs, RocArgs, check, current_stream, lib
+from ._lib import AnomalyArgs, RocArgs, SsimArgs, check, current_stream, lib
 
-__all__ = ["anomaly_maps", "anomaly_metrics", "roc_auc", "roc_points", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
+__all__ = ["anomaly_maps", "anomaly_metrics", "roc_auc", "roc_points", "ssim", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
 
 NC = _lib.ANOMALY_NCOUNTS
@@ -187,13 +194,92 @@ def roc_points(mask, score, batched=None):
     return res
 
 
+# ---------------------------------------------------------------------------------- SSIM on the device
+SSIM_K1, SSIM_K2 = 0.01, 0.03                                            # skimage's constants
+
+
+def _ssim_window(win_size, gaussian_weights):
+    """(win, mode, cn) as skimage derives them: gaussian weights fix the window at 2 * int(3.5 * 1.5 + 0.5) + 1 = 11 and use the
+    population covariance; the uniform window uses the sample covariance."""
+    if gaussian_weights:
+        return 11, _lib.SSIM_GAUSSIAN, 1.0
+    win = int(win_size)
+    if win != win_size or win < 3 or win > _lib.SSIM_MAX_WIN or win % 2 == 0:
+        raise ValueError(f"ssim: win_size must be odd and in 3 ... {_lib.SSIM_MAX_WIN}, got {win_size!r}")
+    return win, _lib.SSIM_UNIFORM, win * win / (win * win - 1.0)
+
+
+def _ssim_images(x, lead):
+    """x as [*lead dims][C][H][W] -> (S, C, H, W); a 2-D image is one channel."""
+    shape = tuple(x.shape)
+    if len(shape) - lead == 2:
+        return shape[:lead], 1, shape[-2], shape[-1]
+    if len(shape) - lead == 3:
+        return shape[:lead], shape[-3], shape[-2], shape[-1]
+    raise ValueError(f"ssim: an image is [H, W] or [C, H, W], got shape {shape} with {lead} leading batch dimension(s)")
+
+
+def ssim(real, recon, batched=None, data_range=2.0, win_size=7, gaussian_weights=False, full=False):
+    """Mean structural similarity of every reconstruction with its image, as `skimage.metrics.structural_similarity(real_s,
+    recon_s, channel_axis=0, data_range=..., win_size=..., gaussian_weights=...)` on fp64 copies: recon `[S, C, H, W]` (`batched`;
+    the default takes tensors of four or more dimensions as batches of `[C, H, W]` images -- all leading dimensions flattened
+    -- and `[C, H, W]` / `[H, W]` tensors as one image), real of the same shape or one image shared by every reconstruction.
+    Returns an `[S]` fp64 device tensor, with `full=True` also the fp32 similarity map shaped like recon, without a host
+    synchronisation.  NaN / inf in an image make that segment's value NaN.  ValueError for images smaller than the window."""
+    if not isinstance(real, torch.Tensor) or not isinstance(recon, torch.Tensor):
+        raise TypeError("ssim: real and recon must be device tensors")
+    if batched is None:
+        lead = max(recon.dim() - 3, 0)
+    else:
+        lead = 1 if batched else 0
+    lead_shape, C, H, W = _ssim_images(recon, lead)
+    S = 1
+    for d in lead_shape:
+        S *= d
+    if S < 1 or C < 1 or H < 1 or W < 1:
+        raise ValueError(f"ssim: empty input {tuple(recon.shape)}")
+    win, mode, cn = _ssim_window(win_size, gaussian_weights)
+    if min(H, W) < win:
+        raise ValueError(f"ssim: window of {win} exceeds the {H} x {W} image")
+    n = C * H * W
+    rc = _f32c(recon, "ssim(recon)")
+    rl = _f32c(real, "ssim(real)")
+    if rl.device != rc.device:
+        raise ValueError("ssim: real and recon are on different devices")
+    if rl.numel() == S * n:
+        real_stride = n
+    elif rl.numel() == n:
+        real_stride = 0
+    else:
+        raise ValueError(f"ssim: real {tuple(real.shape)} does not match recon {tuple(recon.shape)}")
+    dev = rc.device
+    nbytes = lib().anoddpm_ssim_workspace_bytes(S, C, H, W)
+    if nbytes < 0:
+        raise ValueError(f"ssim: {S} x {C} x {H} x {W} is too large for one launch")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    out = torch.empty((S,), dtype=torch.float64, device=dev)
+    smap = torch.empty(tuple(recon.shape), dtype=torch.float32, device=dev) if full else None
+    a = SsimArgs()
+    a.real, a.recon, a.workspace, a.workspace_bytes = rl.data_ptr(), rc.data_ptr(), ws.data_ptr(), nbytes
+    a.mssim, a.map = out.data_ptr(), (smap.data_ptr() if full else None)
+    a.real_stride, a.recon_stride = real_stride, n
+    a.cn, a.data_range, a.K1, a.K2 = cn, float(data_range), SSIM_K1, SSIM_K2
+    a.S, a.C, a.H, a.W, a.win, a.mode = S, C, H, W, win, mode
+    with torch.cuda.device(dev):
+        check(lib().anoddpm_ssim(ctypes.byref(a), current_stream()), "ssim")
+    return (out, smap) if full else out
+
+
 def anomaly_metrics(real, recon, mask, threshold=0.5):
-    """dice / IoU / precision / recall / FPR / mse / PSNR of detection.py:229-250 from one launch, and the AUC of
-    detection.py:230-231 (the whole batch flattened into one curve, evaluation.py:81) from a second one.
-    Returns a dict of Python floats plus the maps (device tensors).  `AUC` is NaN when a class is empty or when `AUC_status`
-    (the status word of the ROC kernel) is non-zero; without a mask there is no AUC (NaN, status 0)."""
+    """dice / IoU / precision / recall / FPR / mse / PSNR of detection.py:229-250 from one launch, the AUC of
+    detection.py:230-231 (the whole batch flattened into one curve, evaluation.py:81) from a second one and the SSIM of
+    detection.py:241-246 (mean over the batch of the per-image SSIM of `real` against the `mean` map, i.e. the reconstruction
+    averaged over `navg`) from a third.  Returns a dict of Python floats plus the maps (device tensors).  `AUC` is NaN when a
+    class is empty or when `AUC_status` (the status word of the ROC kernel) is non-zero; without a mask there is no AUC (NaN,
+    status 0).  `SSIM` is NaN when the inputs are not `[B, C, H, W]` or are smaller than the 7 x 7 window."""
     maps, counts = anomaly_maps(real, recon, mask, threshold)
     roc = _roc_launch(mask, maps["sqerr"], batched=False, curve=False) if mask is not None else None
+    ss = ssim(real, maps["mean"]) if real.dim() == 4 and min(real.shape[-2:]) >= 7 and real.numel() > 0 else None
     c = counts.cpu()
     r = {k: float(v) for k, v in _ratios(c).items() if k != "dice_per_image"}
     n_total = real.numel()
@@ -202,6 +288,7 @@ def anomaly_metrics(real, recon, mask, threshold=0.5):
     r["PSNR"] = float(20.0 * torch.log10(torch.tensor(float(c[:, 10].max())) / torch.sqrt(torch.tensor(mse)))) if mse > 0 else float("inf")
     r["AUC_status"] = int(roc["status"].cpu()[0]) if roc is not None else 0
     r["AUC"] = float(roc["auc"].cpu()[0]) if roc is not None and r["AUC_status"] == 0 else float("nan")
+    r["SSIM"] = float(ss.mean().cpu()) if ss is not None else float("nan")
     r["maps"] = maps
     return r
 
@@ -236,9 +323,20 @@ def PSNR(recon, real):
 
 
 def SSIM(real, recon):
-    """evaluation.py:46-47 -- host-side (skimage) as upstream."""
-    from skimage.metrics import structural_similarity as ssim       # raises ImportError when skimage is absent
-    return ssim(real.detach().cpu().numpy(), recon.detach().cpu().numpy(), channel_axis=2)
+    """evaluation.py:46-47.  Device tensors: the native kernel (`ssim`, 7 x 7 uniform window, data_range 2.0) on `(H, W, C)`
+    images as detection.py:241-246 passes them (channels last, upstream's `channel_axis=2`) and on `(H, W)` images as
+    detection.py:361, 767 pass them, read as ONE single-channel image; returns a Python float like skimage.  Host inputs (numpy
+    arrays, CPU tensors): skimage, as upstream."""
+    if isinstance(real, torch.Tensor) and isinstance(recon, torch.Tensor) and real.is_cuda and recon.is_cuda:
+        if real.shape != recon.shape or real.dim() not in (2, 3):
+            raise ValueError(f"SSIM: expected two (H, W, C) or two (H, W) images, got {tuple(real.shape)} and {tuple(recon.shape)}")
+        if real.dim() == 3:
+            real, recon = real.permute(2, 0, 1), recon.permute(2, 0, 1)
+        return float(ssim(real, recon, batched=False)[0])
+    from skimage.metrics import structural_similarity               # raises ImportError when skimage is absent
+    if isinstance(real, torch.Tensor):
+        real, recon = real.detach().cpu().numpy(), recon.detach().cpu().numpy()
+    return structural_similarity(real, recon, channel_axis=2)
 
 
 def _mask_counts(real_mask, recon_mask):

@@ -572,6 +572,42 @@ typedef struct anoddpm_roc_args {
 int anoddpm_roc_auc(const anoddpm_roc_args *a, void *stream);
 int64_t anoddpm_roc_workspace_bytes(int32_t S, int64_t n);   /* HOST function; -1 for S < 1, n < 1 or n >= 2^31 */
 
+/* ------------------------------------------------------------------ mean structural similarity (SSIM) of image pairs
+ * Replaces skimage.metrics.structural_similarity as the reference calls it (evaluation.py:46-47 SSIM; detection.py:241-246,
+ * 360-362, 765-768, 855-858).  S segments, each one pair x = real, y = recon of [C][H][W] fp32; every operation after the load
+ * is fp64 in a fixed order (deterministic):
+ *   separable window w of odd length win (weights sum to 1) along W, then along H, boundary rule "reflect"
+ *   (d c b a | a b c d | d c b a, scipy.ndimage mode "reflect");
+ *   ux = F(x), uy = F(y), uxx = F(x*x), uyy = F(y*y), uxy = F(x*y)
+ *   vx = cn*(uxx - ux*ux), vy = cn*(uyy - uy*uy), vxy = cn*(uxy - ux*uy)
+ *   C1 = (K1*data_range)^2, C2 = (K2*data_range)^2            (skimage: K1 0.01, K2 0.03)
+ *   S = ((2*ux*uy + C1) * (2*vxy + C2)) / ((ux*ux + uy*uy + C1) * (vx + vy + C2))
+ *   mssim[s] = mean of S over all channels and the interior p <= i < H-p, p <= j < W-p, p = (win-1)/2
+ * mode ANODDPM_SSIM_UNIFORM: w = 1/win, win odd in 3 ... 15 (skimage's default 7; cn = win^2/(win^2-1) is its sample covariance);
+ * mode ANODDPM_SSIM_GAUSSIAN: w = exp(-k^2/(2*1.5^2)) normalised, k = -5 ... 5, win 11 (gaussian_weights=True; cn = 1).
+ *   real_stride / recon_stride: elements between consecutive segments (>= C*H*W; real_stride 0 = one real for every segment)
+ *   map        optional [S][C][H][W] fp32: S at every pixel, boundary included (skimage's full=True image)
+ *   workspace  [dev] anoddpm_ssim_workspace_bytes(S, C, H, W) bytes (one fp64 partial sum per 16 x 32 tile)
+ * win <= min(H, W).  NaN / inf in a segment's images propagate into that segment's mssim only; there is no status word.
+ * Two launches (tiles, then a fixed-order fold), no atomics, no host synchronisation, no allocation: capturable in a hipGraph. */
+#define ANODDPM_SSIM_UNIFORM 0
+#define ANODDPM_SSIM_GAUSSIAN 1
+typedef struct anoddpm_ssim_args {
+    const float *real;              /* [dev] */
+    const float *recon;             /* [dev] */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    double *mssim;                  /* [dev] [S] */
+    float *map;                     /* [dev] [S][C][H][W] or NULL */
+    int64_t real_stride, recon_stride;
+    double cn, data_range, K1, K2;
+    int32_t S, C, H, W;
+    int32_t win, mode;
+} anoddpm_ssim_args;
+
+int anoddpm_ssim(const anoddpm_ssim_args *a, void *stream);
+int64_t anoddpm_ssim_workspace_bytes(int32_t S, int32_t C, int32_t H, int32_t W);   /* HOST function; -1 for a dimension < 1 or S*C*tiles >= 2^31 */
+
 /* Variational-bound terms of one reverse step (GaussianDiffusion.py:384-397 calc_vlb_xt, and the two MSE curves of
  * calc_total_vlb :445-478): per sample b
  *   out[0*B + b] = mean_flat( t==0 ? -discretised_gaussian_log_likelihood(x_0; mean, 0.5*logvar)
