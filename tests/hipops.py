@@ -352,11 +352,12 @@ def conv_wgrad(srcs, dy, *, gn=None, act=0, a_mode=0, band=None, accumulate_into
     TW = next(t for t in (32, 16, 8, 4, 2) if W % t == 0)
     band = band or max(1, H // 4)
     nitems = B * (W // TW) * (-(-H // band))
+    # the workspace starts as NaN: a slab that no workgroup writes shows up in dw
     if algo == 1:                       # Winograd-domain weight gradient: PG slabs of [36][K][N]; column sums per 16x8 output patch
-        ws = torch.empty(lib().anoddpm_wgrad43_groups(K, N, B, H, W) * 9 * K * N, device=dev)
+        ws = torch.full((lib().anoddpm_wgrad43_groups(K, N, B, H, W) * 9 * K * N,), float("nan"), device=dev)
         nitems = B * lib().anoddpm_wgrad43_colsum_items(K, N, B, H, W)
     else:
-        ws = torch.empty(nitems * 9 * K * N, device=dev)
+        ws = torch.full((nitems * 9 * K * N,), float("nan"), device=dev)
     dw = accumulate_into if accumulate_into is not None else torch.full((N, K, 3, 3), float("nan"), device=dev)
     st = WgradArgs()
     st.a0, st.a1 = srcs[0].data_ptr(), srcs[1].data_ptr() if c1 else None
