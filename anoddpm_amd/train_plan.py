@@ -28,10 +28,9 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (ChanStatsArgs, ColsumFoldArgs, DropoutArgs, GnBwdArgs, GnFinalizeArgs, HeadArgs, HeadBwdArgs, LinearArgs, LinearBwdArgs,
-                   LinearBwdBatchArgs, Op, PackArgs, PackBatchArgs, PosembArgs, ResampleArgs, SoftmaxArgs, SoftmaxBwdArgs, StemArgs, StemBwdArgs, TransposeArgs,
-                   Wgrad1Args, WgradArgs, check, lib)
-from .unet import _Plan, _posemb_freqs
+from ._lib import (ColsumFoldArgs, DropoutArgs, GnBwdArgs, HeadBwdArgs, LinearBwdArgs, LinearBwdBatchArgs, Op, PackArgs, SoftmaxBwdArgs,
+                   StemBwdArgs, TransposeArgs, Wgrad1Args, WgradArgs, check, lib)
+from .unet import _Plan, _op_array, _pack_table, pack_floats, pack_kind
 
 __all__ = ["TrainPlan", "TrainPlanFunction", "eligible"]
 
@@ -45,16 +44,10 @@ def eligible(model, B, S):
     return head_ok and 1 <= B <= 16 and model.model_channels % 4 == 0 and model.model_channels <= 256
 
 
-def _op_array(ops):
-    arr = (Op * len(ops))()
-    for i, (code, st) in enumerate(ops):
-        arr[i].code = code
-        arr[i].flags = 0
-        arr[i].args = ctypes.addressof(st)
-    return arr
-
-
 class TrainPlan(_Plan):
+    honours_arith = False        # fp32 only: the split-bf16 side configuration has no backward
+    honours_csum = False         # statistics rows + finalize launches everywhere: the backward needs mean / rstd as tensors
+
     def __init__(self, model, B, S, device, want_dx=False, p_drop=0.0):
         self.want_dx = want_dx
         self.p_drop = float(p_drop)  # nn.Dropout of ResBlock.out_layers (UNet.py:192), training mode only
@@ -79,15 +72,7 @@ class TrainPlan(_Plan):
         its job by bisection); ANODDPM_PACK_BATCH=0 keeps one launch per weight."""
         if os.environ.get("ANODDPM_PACK_BATCH", "1") == "0" or not self.pack_ops:
             return list(self.pack_ops)
-        jobs = (PackArgs * len(self.pack_ops))()
-        block0 = [0]
-        for i, (_, st) in enumerate(self.pack_ops):
-            ctypes.memmove(ctypes.addressof(jobs[i]), ctypes.addressof(st), ctypes.sizeof(PackArgs))
-            block0.append(block0[-1] + int(lib().anoddpm_pack_job_blocks(ctypes.byref(st))))
-        raw = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(self.device)
-        b0 = torch.tensor(block0, dtype=torch.int32, device=self.device)
-        pb = PackBatchArgs()
-        pb.jobs, pb.block0, pb.njobs, pb.nblocks = raw.data_ptr(), b0.data_ptr(), len(self.pack_ops), block0[-1]
+        pb, raw, b0 = _pack_table([st for _, st in self.pack_ops], self.device)
         self.keep += [raw, b0, pb]
         return [(_lib.OP_PACK_BATCH, pb)]
 
@@ -134,21 +119,25 @@ class TrainPlan(_Plan):
         return self.gptr[key]
 
     def pack(self, key, kind, bwd=0, k0=0, kc=0):
-        """Packed copy of a weight, refreshed by an OP_PACK at the head of every forward."""
+        """Packed copy of a weight in the layout `kind` names (unet.PACK_KINDS, or "conv"), refreshed by an OP_PACK at the head of
+        every forward; bwd=1: the data-gradient twin (flipped / transposed; pointwise: input channels k0 .. k0 + kc)."""
+        w = self.named[key]
+        kind = pack_kind(kind, w.shape)
         ck = (key, kind, bwd, k0, kc)
         hit = self._packs.get(ck)
         if hit is not None:
             return hit
-        w = self.named[key]
         N, K = w.shape[0], w.shape[1]
-        n = {0: 9 * N * K, 1: 16 * N * K, 2: (N * kc if bwd else N * K), 3: 9 * N * K, 4: N * K, 5: 36 * N * K}[kind]
-        out = self.buf(n)
+        out = self.buf(pack_floats(kind, N, K, bwd, kc))
         st = PackArgs()
         st.w, st.out, st.N, st.K, st.kind, st.bwd, st.k0, st.kc = self.W(key), out.data_ptr(), N, K, kind, bwd, k0, kc
         self.keep.append(st)
         self.pack_ops.append((_lib.OP_PACK, st))
         self._packs[ck] = out
         return out
+
+    weight = pack                # unet._Plan.weight: the layouts the forward asks for are packed copies refreshed every forward
+    param = W                    # unet._Plan.param: biases and affine parameters are read in place
 
     # ------------------------------------------------------------------ gradient buffers
     def G(self, t):
@@ -176,39 +165,6 @@ class TrainPlan(_Plan):
         self._ws_patch.append((st, field))
 
     # ------------------------------------------------------------------ emitters
-    def gn_t(self, srcs, P, prefix):
-        """GroupNorm statistics -> (scale, shift, mean, rstd); parameters are read in place."""
-        B = self.B
-        c0 = srcs[0][1]
-        c1 = srcs[1][1] if len(srcs) > 1 else 0
-        C = c0 + c1
-        for buf, c in [(s[0], s[1]) for s in srcs]:
-            if buf.data_ptr() not in self.stats_of:
-                self.chan_stats(buf, c, P)
-        job = self.gn_tail_job(srcs, self.W(prefix + ".weight"), self.W(prefix + ".bias"), want_mean=True)
-        if job is not None:
-            return job
-        st = GnFinalizeArgs()
-        self.stats_source(st, 0, srcs[0][0], c0)
-        if c1:
-            self.stats_source(st, 1, srcs[1][0], c1)
-        else:
-            st.stats1, st.rows1, st.fmt1 = None, 0, 0
-        st.gamma, st.beta = self.W(prefix + ".weight"), self.W(prefix + ".bias")
-        scale, shift, mean, rstd = self.buf(B, C), self.buf(B, C), self.buf(B, 32), self.buf(B, 32)
-        st.scale, st.shift, st.mean_out, st.rstd_out = scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-        st.c0, st.c1, st.P, st.B, st.groups, st.eps = c0, c1, P, B, 32, 1e-5
-        self.add(_lib.OP_GN_FINALIZE, st)
-        return scale, shift, mean, rstd
-
-    def linear_t(self, inp, wkey, bkey, K, N, act_in):
-        st = LinearArgs()
-        st.inp, st.w, st.bias = inp.data_ptr(), self.W(wkey), self.W(bkey)
-        o = self.buf(self.B, N)
-        st.out, st.B, st.K, st.N, st.act_in, st.act_out = o.data_ptr(), self.B, K, N, act_in, 0
-        self.add(_lib.OP_LINEAR, st)
-        return o
-
     def linear_bwd(self, x, wkey, bkey, dy, K, N, act_in, dx):
         st = LinearBwdArgs()
         st.x, st.w, st.dy = x.data_ptr(), self.W(wkey), dy.data_ptr()
@@ -368,27 +324,45 @@ class TrainPlan(_Plan):
         self.badd(_lib.OP_GN_BWD, ga)
 
     # ------------------------------------------------------------------ network
-    def _build(self):
-        m = self.model
-        B, S, dev = self.B, self.S, self.device
-        base, ted = m.model_channels, m._ted
-        down, middle, up = m._blocks
-        self.post_pack = []
-        self._bind_params()
-        bias = self.W
+    # The forward is unet._Plan's, inherited.  What differs enters through the overrides below (`weight` / `param` above, `gn`,
+    # `time_path` / `emb_of`, `pool_act`, `dropout`, `keep_probs`); every block method calls the inherited forward and registers
+    # the backward of that block from the record it returns.
+    keep_probs = True            # the softmax output of every attention block is kept for the backward
 
-        # --- timestep path (UNet.py:271-276): pre-activations are kept, SiLU rides on the next layer's input
-        half = base // 2
-        freqs = _posemb_freqs(half).to(dev)
-        self.keep.append(freqs)
-        pe = self.buf(B, base)
-        self.posemb = PosembArgs()
-        self.posemb.t, self.posemb.freqs, self.posemb.out = None, freqs.data_ptr(), pe.data_ptr()
-        self.posemb.B, self.posemb.dim, self.posemb.scale = B, base, 1.0
-        self.add(_lib.OP_POSEMB, self.posemb)
-        z1 = self.linear_t(pe, "time_embedding.1.weight", "time_embedding.1.bias", base, ted, 0)
-        temb = self.linear_t(z1, "time_embedding.3.weight", "time_embedding.3.bias", ted, ted, 1)
-        self.temb = temb
+    def _build(self):
+        self._bind_params()
+        self.walk()
+        # --- backward list: the stages in reverse
+        for fn in reversed(self._bw):
+            self._touched = set()
+            fn()
+            self.bwd_marks.append((len(self.bops), sorted(self._touched)))
+        # split-K workspace of the shared igemm emitter (forward and backward launches) + the training workspace
+        self.share_workspace(self.ops + self.bops)
+        if self._tws_need:
+            tws = self.buf(self._tws_need)
+            for st, field in self._ws_patch:
+                setattr(st, field, tws.data_ptr())
+
+    def gn(self, srcs, P, prefix, into=None):
+        """GroupNorm statistics -> (scale, shift, mean, rstd), always as tensors (the backward reads mean / rstd) and never folded
+        into the consumer `into`; parameters are read in place."""
+        self.gn_sums(srcs, P)
+        gamma, beta = self.W(prefix + ".weight"), self.W(prefix + ".bias")
+        return self.gn_tail_job(srcs, gamma, beta, want_mean=True) or self.gn_finalize(srcs, P, gamma, beta, want_mean=True)
+
+    def pool_act(self):
+        # ANODDPM_NO_POOL_ACT is an A/B switch of the inference plan only: honouring it here would move the first convolution of every
+        # down block from the Winograd kernels to the pool-fused direct one (the backward re-applies the pooling on the raw input either way)
+        return True
+
+    def time_path(self):
+        """Timestep path (UNet.py:271-276): pre-activations are kept, SiLU rides on the next layer's input (the backward needs z1)."""
+        m = self.model
+        base, ted = m.model_channels, m._ted
+        pe = self.posemb_features()
+        z1 = self.linear(pe, self.W("time_embedding.1.weight"), self.W("time_embedding.1.bias"), base, ted, 0)
+        temb = self.temb = self.linear(z1, self.W("time_embedding.3.weight"), self.W("time_embedding.3.bias"), ted, ted, 1)
         g_temb, g_z1 = self.G(temb), self.G(z1)
 
         # Forward: every ResBlock's embedding projection in ONE launch (round 6: 22 launches of ~8 us at config 3) when the projections'
@@ -407,17 +381,7 @@ class TrainPlan(_Plan):
                 bp += 4 * w.shape[0]
                 self._emb_tot += w.shape[0]
             if ok:
-                st = LinearArgs()
-                st.inp, st.w, st.bias = temb.data_ptr(), self.W(ekeys[0] + ".weight"), self.W(ekeys[0] + ".bias")
-                self._emb_all = self.buf(B, self._emb_tot)
-                st.out, st.B, st.K, st.N, st.act_in, st.act_out = self._emb_all.data_ptr(), B, ted, self._emb_tot, 1, 0
-                self.add(_lib.OP_LINEAR, st)
-
-        def emb_of(prefix, cout):
-            """(pointer, row pitch) of a block's embedding projection: a column range of the batched launch, or its own launch."""
-            if self._emb_all is not None:
-                return self._emb_all.data_ptr() + 4 * self._emb_off[prefix], self._emb_tot
-            return self.linear_t(temb, prefix + ".embed_layers.1.weight", prefix + ".embed_layers.1.bias", ted, cout, 1).data_ptr(), cout
+                self._emb_all = self.linear(temb, self.W(ekeys[0] + ".weight"), self.W(ekeys[0] + ".bias"), ted, self._emb_tot, 1)
 
         self._emb_jobs = []          # (weight key, bias key, d_emb buffer, cout) of every ResBlock's embedding projection
         # One batched launch for all of them at the END of the backward.  With a data-parallel reducer attached that is still
@@ -431,381 +395,216 @@ class TrainPlan(_Plan):
             self.linear_bwd(pe, "time_embedding.1.weight", "time_embedding.1.bias", g_z1, base, ted, 0, None)
         self._bw.append(time_bwd)
 
-        def conv3(srcs, Hout, N, gnp, a_mode, wkey, bkey, out, temb_ptr=None, temb_ld=0, res=None, res_up=None):
-            self.igemm(srcs=srcs, H=Hout, W=Hout, ks=3, N=N, gn=(gnp[0], gnp[1]), act=1, a_mode=a_mode,
-                       bmat=lambda: self.pack(wkey, 0), wino=lambda: self.pack(wkey, 1), wino43=lambda: self.pack(wkey, 5),
-                       bias=bias(bkey),
-                       temb=temb_ptr, temb_ld=temb_ld, res=res, res_up=res_up, out=out, want_stats=True)
+    def emb_of(self, prefix, cout):
+        """(pointer, row pitch) of a block's embedding projection: a column range of the batched launch, or its own launch."""
+        if self._emb_all is not None:
+            return super().emb_of(prefix, cout)
+        ted = self.model._ted
+        return self.linear(self.temb, self.W(prefix + ".embed_layers.1.weight"), self.W(prefix + ".embed_layers.1.bias"), ted, cout, 1).data_ptr(), cout
 
-        fuse_gnb = os.environ.get("ANODDPM_NO_GNB_FUSE", "0") != "1"
+    def dropout(self, h1, g2, P, C):
+        """Dropout between the activation and the second convolution of a ResBlock: the dropped activation is materialised once
+        (one elementwise launch) and the convolution, its weight gradient and its data gradient see a plain operand."""
+        a2 = self.buf(self.B, P, C)
+        dr = DropoutArgs()
+        dr.x, dr.out, dr.gn_scale, dr.gn_shift = h1.data_ptr(), a2.data_ptr(), g2[0].data_ptr(), g2[1].data_ptr()
+        dr.n, dr.B, dr.C, dr.mode, dr.p, dr.seed = P * C, self.B, C, 0, self.p_drop, 0
+        self.add(_lib.OP_DROPOUT, dr)
+        self._drop_ops.append([dr, None, len(self._drop_ops)])       # forward order; the block's backward fills in the backward twin
+        return a2
 
-        def dgrad3(dy, Hout, Kc, N, wkey, gnb=None):
-            """da [B][Hout^2][Kc] = conv3x3(dy, flipped / transposed weights): the forward kernels on the packed twin.
-            gnb = (sources, gn_t tuple, GroupNorm prefix) of the operand a = SiLU(GroupNorm(x)) this gradient belongs to: where the
-            launch runs on the channel-sliced F(4x4,3x3) kernel its epilogue also writes the partial sums of the GroupNorm
-            backward's reduction pass (round 6: one pass over x and da less per layer); returns (da, fused) for gn_bwd."""
-            da = self.buf(B, Hout * Hout, Kc)
-            st = self.igemm(srcs=[(dy, N)], H=Hout, W=Hout, ks=3, N=Kc, bmat=lambda: self.pack(wkey, 0, bwd=1),
-                            wino=lambda: self.pack(wkey, 1, bwd=1), wino43=lambda: self.pack(wkey, 5, bwd=1), out=da)
-            st.gnb_partial = None
-            if gnb is None:
-                return da
-            fused = None
-            xs, gnp, gprefix = gnb
-            xc0 = xs[0][1]
-            if (fuse_gnb and st.cfg == 3 and st.ksplit == 1 and xc0 % 16 == 0 and sum(x[1] for x in xs) == Kc
-                    and lib().anoddpm_f43_channel_sliced(Hout, Hout, Kc, B) == 1):
-                rows = (Hout // 16) * (Hout // 16)
-                part = self.buf(B * rows * Kc * 2, dtype=torch.float64)
-                st.gnb_partial = part.data_ptr()
-                st.gnb_x0 = xs[0][0].data_ptr()
-                st.gnb_x1 = xs[1][0].data_ptr() if len(xs) > 1 else None
-                st.gnb_gamma, st.gnb_beta = self.W(gprefix + ".weight"), self.W(gprefix + ".bias")
-                st.gnb_mean, st.gnb_rstd = gnp[2].data_ptr(), gnp[3].data_ptr()
-                P = Hout * Hout
-                xc1 = xs[1][1] if len(xs) > 1 else 0
-                st.gnb_x0_bs, st.gnb_x1_bs = P * xc0, P * xc1
-                st.gnb_c0, st.gnb_x0_ld, st.gnb_x1_ld, st.gnb_groups = xc0, xc0, (xc1 if xc1 else 4), 32
-                fused = (part, rows)
-            return da, fused
+    def dgrad3(self, dy, Hout, Kc, N, wkey, gnb=None):
+        """da [B][Hout^2][Kc] = conv3x3(dy, flipped / transposed weights): the forward kernels on the packed twin.
+        gnb = (sources, gn tuple, GroupNorm prefix) of the operand a = SiLU(GroupNorm(x)) this gradient belongs to: where the
+        launch runs on the channel-sliced F(4x4,3x3) kernel its epilogue also writes the partial sums of the GroupNorm
+        backward's reduction pass (round 6: one pass over x and da less per layer); returns (da, fused) for gn_bwd."""
+        B = self.B
+        da = self.buf(B, Hout * Hout, Kc)
+        st = self.igemm(srcs=[(dy, N)], H=Hout, W=Hout, ks=3, N=Kc, **self.conv_weights(wkey, bwd=1), out=da)
+        st.gnb_partial = None
+        if gnb is None:
+            return da
+        fused = None
+        xs, gnp, gprefix = gnb
+        xc0 = xs[0][1]
+        if (os.environ.get("ANODDPM_NO_GNB_FUSE", "0") != "1" and st.cfg == 3 and st.ksplit == 1 and xc0 % 16 == 0
+                and sum(x[1] for x in xs) == Kc and lib().anoddpm_f43_channel_sliced(Hout, Hout, Kc, B) == 1):
+            rows = (Hout // 16) * (Hout // 16)
+            part = self.buf(B * rows * Kc * 2, dtype=torch.float64)
+            st.gnb_partial = part.data_ptr()
+            st.gnb_x0 = xs[0][0].data_ptr()
+            st.gnb_x1 = xs[1][0].data_ptr() if len(xs) > 1 else None
+            st.gnb_gamma, st.gnb_beta = self.W(gprefix + ".weight"), self.W(gprefix + ".bias")
+            st.gnb_mean, st.gnb_rstd = gnp[2].data_ptr(), gnp[3].data_ptr()
+            P = Hout * Hout
+            xc1 = xs[1][1] if len(xs) > 1 else 0
+            st.gnb_x0_bs, st.gnb_x1_bs = P * xc0, P * xc1
+            st.gnb_c0, st.gnb_x0_ld, st.gnb_x1_ld, st.gnb_groups = xc0, xc0, (xc1 if xc1 else 4), 32
+            fused = (part, rows)
+        return da, fused
 
-        def res_block(prefix, srcs, Hin, cout, resample):
-            cin = sum(s[1] for s in srcs)
-            Hout = Hin * 2 if resample == "up" else (Hin // 2 if resample == "down" else Hin)
-            Pin, Pout = Hin * Hin, Hout * Hout
-            am = {None: 0, "up": 1, "down": 2}[resample]
-            g1 = self.gn_t(srcs, Pin, prefix + ".in_layers.0")
-            emb_ptr, emb_ld = emb_of(prefix, cout)
-            h1 = self.buf(B, Pout, cout)
-            sk_pool = None
-            if resample == "down":
-                # one pass over x: pooled skip input + pooled ACTIVATED conv operand (so the conv runs on the Winograd kernels);
-                # the backward is unchanged -- weight gradient and GroupNorm backward re-apply the pooling on the raw input
-                assert len(srcs) == 1
-                pooled, sk_pool = self.buf(B, Pout, cin), self.buf(B, Pout, cin)
-                st = ResampleArgs()
-                st.inp, st.out = srcs[0][0].data_ptr(), sk_pool.data_ptr()
-                st.B, st.H, st.W, st.C, st.mode, st.scale, st.accumulate = B, Hin, Hin, cin, 2, 1.0, 0
-                st.gn_scale, st.gn_shift, st.out_act = g1[0].data_ptr(), g1[1].data_ptr(), pooled.data_ptr()
-                self.add(_lib.OP_RESAMPLE, st)
-                wk, bk = prefix + ".in_layers.2.weight", prefix + ".in_layers.2.bias"
-                self.igemm(srcs=[(pooled, cin)], H=Hout, W=Hout, ks=3, N=cout, bmat=lambda: self.pack(wk, 0),
-                           wino=lambda: self.pack(wk, 1), wino43=lambda: self.pack(wk, 5), bias=bias(bk),
-                           temb=emb_ptr, temb_ld=emb_ld, out=h1, want_stats=True)
-            else:
-                conv3(srcs, Hout, cout, g1, am, prefix + ".in_layers.2.weight", prefix + ".in_layers.2.bias", h1,
-                      temb_ptr=emb_ptr, temb_ld=emb_ld)
-            g2 = self.gn_t([(h1, cout)], Pout, prefix + ".out_layers.0")
-            skip_kind = "identity"
-            if cin != cout:
-                assert resample is None
-                skip_kind = "conv"
-                sk = self.buf(B, Pout, cout)
-                self.igemm(srcs=srcs, H=Hout, W=Hout, ks=1, N=cout, kind="conv1",
-                           bmat=lambda: self.pack(prefix + ".skip_connection.weight", 2),
-                           bias=bias(prefix + ".skip_connection.bias"), out=sk)
-            elif resample is not None and sk_pool is not None:
-                skip_kind = "resample"
-                sk = sk_pool
-            elif resample == "up" and self.p_drop == 0:
-                # nearest x2 of the block input as the residual: read at half resolution by the F(4x4) epilogue (igemm(res_up=...)
-                # materialises it for every other kernel); the backward of this path is the pooling of gh2 below, unchanged
-                assert len(srcs) == 1
-                skip_kind = "resample"
-                sk = None
-            elif resample is not None:
-                assert len(srcs) == 1
-                skip_kind = "resample"
-                sk = self.buf(B, Pout, cout)
-                st = ResampleArgs()
-                st.inp, st.out = srcs[0][0].data_ptr(), sk.data_ptr()
-                st.B, st.H, st.W, st.C, st.mode, st.scale, st.accumulate = B, Hin, Hin, cin, (1 if resample == "up" else 2), 1.0, 0
-                self.add(_lib.OP_RESAMPLE, st)
-            else:
-                if len(srcs) != 1:
-                    raise NotImplementedError("identity skip over a concatenated input (cin == cout) is not built")
-                sk = srcs[0][0]
-            h2 = self.buf(B, Pout, cout)
-            a2 = None
-            if self.p_drop > 0:
-                # Dropout between the activation and the convolution: the dropped activation is materialised once (one
-                # elementwise launch) and the convolution, its weight gradient and its data gradient see a plain operand
-                a2 = self.buf(B, Pout, cout)
-                dr = DropoutArgs()
-                dr.x, dr.out, dr.gn_scale, dr.gn_shift = h1.data_ptr(), a2.data_ptr(), g2[0].data_ptr(), g2[1].data_ptr()
-                dr.n, dr.B, dr.C, dr.mode, dr.p, dr.seed = Pout * cout, B, cout, 0, self.p_drop, 0
-                self.add(_lib.OP_DROPOUT, dr)
-                drop_entry = [dr, None, len(self._drop_ops)]         # forward order; the backward twin is filled in below
-                self._drop_ops.append(drop_entry)
-                wk, bk = prefix + ".out_layers.3.weight", prefix + ".out_layers.3.bias"
-                self.igemm(srcs=[(a2, cout)], H=Hout, W=Hout, ks=3, N=cout, bmat=lambda: self.pack(wk, 0),
-                           wino=lambda: self.pack(wk, 1), wino43=lambda: self.pack(wk, 5), bias=bias(bk), res=sk, out=h2, want_stats=True)
-            else:
-                conv3([(h1, cout)], Hout, cout, g2, 0, prefix + ".out_layers.3.weight", prefix + ".out_layers.3.bias", h2, res=sk,
-                      res_up=(srcs[0][0] if (resample == "up" and sk is None) else None))
+    def stem_block(self, prefix, cin, cout):
+        r = super().stem_block(prefix, cin, cout)
+        B, S = self.B, self.S
 
-            def bwd():
-                gh2 = self.G(h2)
-                with self.in_backward():
-                    # 1. skip path
-                    if skip_kind == "conv":
-                        self.wgrad1(srcs, Pin, None, 0, gh2, cout, cout, prefix + ".skip_connection.weight",
-                                    prefix + ".skip_connection.bias")
-                        k0 = 0
-                        for (src, c) in [(s[0], s[1]) for s in srcs]:
-                            gs = self.G(src)
-                            acc = self.gacc(src)
-                            self.igemm(srcs=[(gh2, cout)], H=Hout, W=Hout, ks=1, N=c, kind="conv1",
-                                       bmat=self.pack(prefix + ".skip_connection.weight", 2, bwd=1, k0=k0, kc=c),
-                                       res=(gs if acc else None), out=gs)
-                            k0 += c
-                    elif skip_kind == "resample":
-                        src = srcs[0][0]
-                        st = ResampleArgs()
-                        st.inp, st.out = gh2.data_ptr(), self.G(src).data_ptr()
-                        st.B, st.H, st.W, st.C = B, Hout, Hout, cout
-                        # forward nearest-up -> backward sums the four children (avg pool * 4); forward avg pool -> nearest-up / 4
-                        st.mode, st.scale = (2, 4.0) if resample == "up" else (1, 0.25)
-                        st.accumulate = self.gacc(src)
-                        self.add(_lib.OP_RESAMPLE, st)
-                    # 2-4. out_layers: weight gradient, data gradient, GroupNorm + SiLU backward into g(h1)
-                    if a2 is not None:
-                        self.wgrad3([(a2, cout)], Hout, Hout, None, 0, gh2, cout, prefix + ".out_layers.3.weight", prefix + ".out_layers.3.bias")
-                        da2, fused2 = dgrad3(gh2, Hout, cout, cout, prefix + ".out_layers.3.weight"), None
-                        db = DropoutArgs()                           # d(activation) = mask / (1 - p) * d(dropped), in place
-                        db.x, db.out, db.n, db.B, db.C, db.mode, db.p, db.seed = da2.data_ptr(), da2.data_ptr(), Pout * cout, B, cout, 1, self.p_drop, 0
-                        self.add(_lib.OP_DROPOUT, db)
-                        drop_entry[1] = db
-                    else:
-                        self.wgrad3([(h1, cout)], Hout, Hout, g2, 0, gh2, cout, prefix + ".out_layers.3.weight", prefix + ".out_layers.3.bias")
-                        da2, fused2 = dgrad3(gh2, Hout, cout, cout, prefix + ".out_layers.3.weight",
-                                             gnb=([(h1, cout)], g2, prefix + ".out_layers.0"))
-                    self.gn_bwd([(h1, cout)], Hout, da2, Pout, g2, prefix + ".out_layers.0", 1, 0, fused=fused2)
-                    gh1 = self.G(h1)
-                    # 5. in_layers weight gradient; its dy column sums are the conv bias and the embedding gradients
-                    d_emb = self.buf(B, cout)
-                    self.wgrad3(srcs, Hin, Hout, g1, am, gh1, cout, prefix + ".in_layers.2.weight", prefix + ".in_layers.2.bias", d_emb=d_emb)
-                    if self._batch_emb:
-                        self._emb_jobs.append((prefix + ".embed_layers.1.weight", prefix + ".embed_layers.1.bias", d_emb, cout))
-                    else:
-                        self.linear_bwd(temb, prefix + ".embed_layers.1.weight", prefix + ".embed_layers.1.bias", d_emb, ted, cout, 1, g_temb)
-                    # 6-7. data gradient and the fused operand load's backward into the block inputs
-                    if am == 0:
-                        da1, fused1 = dgrad3(gh1, Hout, cin, cout, prefix + ".in_layers.2.weight", gnb=(srcs, g1, prefix + ".in_layers.0"))
-                    else:                                            # a resampling sits between the activation and the convolution
-                        da1, fused1 = dgrad3(gh1, Hout, cin, cout, prefix + ".in_layers.2.weight"), None
-                    self.gn_bwd(srcs, Hin, da1, Pout, g1, prefix + ".in_layers.0", 1, am,
-                                dres=(gh2 if skip_kind == "identity" else None), fused=fused1)
-            self._bw.append(bwd)
-            return h2, Hout
+        def stem_bwd():
+            sb = StemBwdArgs()
+            self.stem_bwd_args = sb
+            sb.x, sb.w, sb.dy = None, self.W(prefix + ".weight"), self.G(r.out).data_ptr()
+            sb.dw, sb.db = self.dW(prefix + ".weight"), self.dW(prefix + ".bias")
+            self.dx = self.buf(B, cin, S, S) if self.want_dx else None
+            sb.dx = self.dx.data_ptr() if self.want_dx else None
+            nblk = B * -(-(S * S) // 1024)
+            sb.ws_floats = nblk * (cin * 9 + 1) * cout
+            self.tws(sb, "ws", sb.ws_floats)
+            sb.B, sb.H, sb.W, sb.Cin, sb.Cout = B, S, S, cin, cout
+            self.badd(_lib.OP_STEM_BWD, sb)
+        self._bw.append(stem_bwd)
+        return r
 
-        def attn_block(prefix, x, Hc, C):
-            L = Hc * Hc
-            heads = m._heads_for(C)
-            ch = C // heads
-            if ch % 4:
-                raise NotImplementedError(f"attention head width {ch} must be a multiple of 4")
-            Z = B * heads
-            alpha = 1.0 / math.sqrt(ch)
-            g = self.gn_t([(x, C)], L, prefix + ".norm")
-            qkv = self.buf(B, L, 3 * C)
-            self.igemm(srcs=[(x, C)], H=Hc, W=Hc, ks=1, N=3 * C, gn=(g[0], g[1]), act=0, kind="qkvproj",
-                       bmat=lambda: self.pack(prefix + ".to_qkv.weight", 2), bias=bias(prefix + ".to_qkv.bias"), out=qkv)
-            Pm = self.buf(Z, L, L)                               # softmax output, kept for the backward
-            qp = qkv.data_ptr()
-            att = self.buf(B, L, C)
-            if not self.attention(qkv, att, L, heads, ch, probs=Pm):
-                self.igemm(srcs=[(qp, ch, 3 * C)], H=1, W=L, ks=1, N=L, b_mode=1, ldb=3 * C, heads=heads,
-                           bmat=qp + 4 * ch, alpha=alpha, kind="attn",
-                           a_strides=(L * 3 * C, 3 * ch), b_strides=(L * 3 * C, 3 * ch),
-                           out=Pm, out_ld=L, o_strides=(heads * L * L, L * L))
-                sm = SoftmaxArgs()
-                sm.x, sm.rows, sm.L = Pm.data_ptr(), Z * L, L
-                self.add(_lib.OP_SOFTMAX, sm)
-                self.igemm(srcs=[(Pm.data_ptr(), L, L)], H=1, W=L, ks=1, N=ch, b_mode=2, ldb=3 * C, heads=heads,
-                           bmat=qp + 4 * 2 * ch, kind="attn",
-                           a_strides=(heads * L * L, L * L), b_strides=(L * 3 * C, 3 * ch),
-                           out=att, out_ld=C, o_strides=(L * C, ch))
-            y = self.buf(B, L, C)
-            self.igemm(srcs=[(att, C)], H=Hc, W=Hc, ks=1, N=C, kind="qkvproj",
-                       bmat=lambda: self.pack(prefix + ".proj_out.weight", 2), bias=bias(prefix + ".proj_out.bias"),
-                       res=x, out=y, want_stats=True)
+    def res_block(self, prefix, srcs, Hin, cout, resample):
+        r = super().res_block(prefix, srcs, Hin, cout, resample)
+        B, ted, temb = self.B, self.model._ted, self.temb
+        cin, Hout, am, g1, g2, h1, h2, a2 = r.cin, r.H, r.a_mode, r.g1, r.g2, r.h1, r.out, r.a2
+        Pin, Pout = Hin * Hin, Hout * Hout
+        drop_entry = self._drop_ops[-1] if a2 is not None else None
 
-            def bwd():
-                gy = self.G(y)
-                with self.in_backward():
-                    # proj_out: dW, d(att)
-                    self.wgrad1([(att, C)], L, None, 0, gy, C, C, prefix + ".proj_out.weight", prefix + ".proj_out.bias")
-                    datt = self.buf(B, L, C)
-                    self.igemm(srcs=[(gy, C)], H=Hc, W=Hc, ks=1, N=C, kind="qkvproj",
-                               bmat=self.pack(prefix + ".proj_out.weight", 2, bwd=1, k0=0, kc=C), out=datt)
-                    dqkv = self.buf(B, L, 3 * C)
-                    dq = dqkv.data_ptr()
-                    dP = self.buf(Z, L, L)
-                    T1 = self.buf(Z, L, L)
-                    # dP = d(att)_h v_h^T
-                    self.igemm(srcs=[(datt.data_ptr(), ch, C)], H=1, W=L, ks=1, N=L, b_mode=1, ldb=3 * C, heads=heads,
-                               bmat=qp + 4 * 2 * ch, kind="attn", a_strides=(L * C, ch), b_strides=(L * 3 * C, 3 * ch),
-                               out=dP, out_ld=L, o_strides=(heads * L * L, L * L))
-                    # dV_h = P^T d(att)_h
-                    tr = TransposeArgs()
-                    tr.inp, tr.out, tr.Z, tr.L = Pm.data_ptr(), T1.data_ptr(), Z, L
-                    self.add(_lib.OP_TRANSPOSE, tr)
-                    self.igemm(srcs=[(T1.data_ptr(), L, L)], H=1, W=L, ks=1, N=ch, b_mode=2, ldb=C, heads=heads,
-                               bmat=datt.data_ptr(), kind="attn", a_strides=(heads * L * L, L * L), b_strides=(L * C, ch),
-                               out=dq + 4 * 2 * ch, out_ld=3 * C, o_strides=(L * 3 * C, 3 * ch))
-                    # dS = P o (dP - rowsum(dP o P)), in place
-                    sb = SoftmaxBwdArgs()
-                    sb.p, sb.dp, sb.rows, sb.L = Pm.data_ptr(), dP.data_ptr(), Z * L, L
-                    self.add(_lib.OP_SOFTMAX_BWD, sb)
-                    # dQ_h = alpha dS k_h ; dK_h = alpha dS^T q_h
-                    self.igemm(srcs=[(dP.data_ptr(), L, L)], H=1, W=L, ks=1, N=ch, b_mode=2, ldb=3 * C, heads=heads,
-                               bmat=qp + 4 * ch, alpha=alpha, kind="attn", a_strides=(heads * L * L, L * L),
-                               b_strides=(L * 3 * C, 3 * ch), out=dq, out_ld=3 * C, o_strides=(L * 3 * C, 3 * ch))
-                    tr2 = TransposeArgs()
-                    tr2.inp, tr2.out, tr2.Z, tr2.L = dP.data_ptr(), T1.data_ptr(), Z, L
-                    self.add(_lib.OP_TRANSPOSE, tr2)
-                    self.igemm(srcs=[(T1.data_ptr(), L, L)], H=1, W=L, ks=1, N=ch, b_mode=2, ldb=3 * C, heads=heads,
-                               bmat=qp, alpha=alpha, kind="attn", a_strides=(heads * L * L, L * L),
-                               b_strides=(L * 3 * C, 3 * ch), out=dq + 4 * ch, out_ld=3 * C, o_strides=(L * 3 * C, 3 * ch))
-                    # to_qkv: dW (input = GroupNorm(x), no SiLU), d(normed x), GroupNorm backward + the residual
-                    self.wgrad1([(x, C)], L, g, 0, dqkv, 3 * C, 3 * C, prefix + ".to_qkv.weight", prefix + ".to_qkv.bias")
-                    da = self.buf(B, L, C)
-                    self.igemm(srcs=[(dqkv, 3 * C)], H=Hc, W=Hc, ks=1, N=C, kind="qkvproj",
-                               bmat=self.pack(prefix + ".to_qkv.weight", 2, bwd=1, k0=0, kc=C), out=da)
-                    self.gn_bwd([(x, C)], Hc, da, L, g, prefix + ".norm", 0, 0, dres=gy)
-            self._bw.append(bwd)
-            return y
-
-        def run(blks, srcs, Hc):
-            for (prefix, kind, cin, cout, resample) in blks:
-                if kind == "stem":
-                    h0 = self.buf(B, S * S, cout)
-                    self.stem = StemArgs()
-                    self.stem.x = None
-                    self.stem.w = self.pack(prefix + ".weight", 3).data_ptr()
-                    self.stem.bias = bias(prefix + ".bias")
-                    self.stem.out = h0.data_ptr()
-                    self.stem.B, self.stem.H, self.stem.W, self.stem.Cin, self.stem.Cout = B, S, S, cin, cout
-                    rows = lib().anoddpm_stem_stats_rows(S, S, cin, cout)
-                    if rows > 0 and os.environ.get("ANODDPM_NO_STEM_STATS", "0") != "1":
-                        # GroupNorm partial sums of the stem output from the stem kernel itself (no chan_stats pass over it)
-                        sstats = self.buf(B, rows, cout, 2)
-                        self.stem.stats, self.stem.stats_rows = sstats.data_ptr(), rows
-                        self.stats_of[h0.data_ptr()] = ("rows", sstats, rows)
-                    self.add(_lib.OP_STEM, self.stem)
-                    srcs = [(h0, cout)]
-
-                    def stem_bwd(prefix=prefix, h0=h0, cin=cin, cout=cout):
-                        sb = StemBwdArgs()
-                        self.stem_bwd_args = sb
-                        sb.x, sb.w, sb.dy = None, self.W(prefix + ".weight"), self.G(h0).data_ptr()
-                        sb.dw, sb.db = self.dW(prefix + ".weight"), self.dW(prefix + ".bias")
-                        self.dx = self.buf(B, cin, S, S) if self.want_dx else None
-                        sb.dx = self.dx.data_ptr() if self.want_dx else None
-                        nblk = B * -(-(S * S) // 1024)
-                        sb.ws_floats = nblk * (cin * 9 + 1) * cout
-                        self.tws(sb, "ws", sb.ws_floats)
-                        sb.B, sb.H, sb.W, sb.Cin, sb.Cout = B, S, S, cin, cout
-                        self.badd(_lib.OP_STEM_BWD, sb)
-                    self._bw.append(stem_bwd)
-                elif kind == "res":
-                    h, Hc = res_block(prefix, srcs, Hc, cout, resample)
-                    srcs = [(h, cout)]
-                elif kind in ("downsample", "upsample"):
-                    h, Hc = resample_layer(prefix, kind, srcs[0][0], Hc, cin, resample == "conv")
-                    srcs = [(h, cin)]
+        def bwd():
+            gh2 = self.G(h2)
+            with self.in_backward():
+                # 1. skip path
+                if r.skip == "conv":
+                    self.wgrad1(srcs, Pin, None, 0, gh2, cout, cout, prefix + ".skip_connection.weight",
+                                prefix + ".skip_connection.bias")
+                    k0 = 0
+                    for (src, c) in [(s[0], s[1]) for s in srcs]:
+                        gs = self.G(src)
+                        acc = self.gacc(src)
+                        self.igemm(srcs=[(gh2, cout)], H=Hout, W=Hout, ks=1, N=c, kind="conv1",
+                                   bmat=self.pack(prefix + ".skip_connection.weight", "conv", bwd=1, k0=k0, kc=c),
+                                   res=(gs if acc else None), out=gs)
+                        k0 += c
+                elif r.skip == "resample":
+                    src = srcs[0][0]
+                    # forward nearest-up -> backward sums the four children (avg pool * 4); forward avg pool -> nearest-up / 4
+                    mode, scale = (2, 4.0) if resample == "up" else (1, 0.25)
+                    self.resample(gh2, Hout, cout, mode, self.G(src), scale, self.gacc(src))
+                # 2-4. out_layers: weight gradient, data gradient, GroupNorm + SiLU backward into g(h1)
+                if a2 is not None:
+                    self.wgrad3([(a2, cout)], Hout, Hout, None, 0, gh2, cout, prefix + ".out_layers.3.weight", prefix + ".out_layers.3.bias")
+                    da2, fused2 = self.dgrad3(gh2, Hout, cout, cout, prefix + ".out_layers.3.weight"), None
+                    db = DropoutArgs()                           # d(activation) = mask / (1 - p) * d(dropped), in place
+                    db.x, db.out, db.n, db.B, db.C, db.mode, db.p, db.seed = da2.data_ptr(), da2.data_ptr(), Pout * cout, B, cout, 1, self.p_drop, 0
+                    self.add(_lib.OP_DROPOUT, db)
+                    drop_entry[1] = db
                 else:
-                    h = attn_block(prefix, srcs[0][0], Hc, cin)
-                    srcs = [(h, cin)]
-                self.block_out[prefix] = (srcs[0][0], srcs[0][1], Hc)
-            return srcs, Hc
+                    self.wgrad3([(h1, cout)], Hout, Hout, g2, 0, gh2, cout, prefix + ".out_layers.3.weight", prefix + ".out_layers.3.bias")
+                    da2, fused2 = self.dgrad3(gh2, Hout, cout, cout, prefix + ".out_layers.3.weight",
+                                              gnb=([(h1, cout)], g2, prefix + ".out_layers.0"))
+                self.gn_bwd([(h1, cout)], Hout, da2, Pout, g2, prefix + ".out_layers.0", 1, 0, fused=fused2)
+                gh1 = self.G(h1)
+                # 5. in_layers weight gradient; its dy column sums are the conv bias and the embedding gradients
+                d_emb = self.buf(B, cout)
+                self.wgrad3(srcs, Hin, Hout, g1, am, gh1, cout, prefix + ".in_layers.2.weight", prefix + ".in_layers.2.bias", d_emb=d_emb)
+                if self._batch_emb:
+                    self._emb_jobs.append((prefix + ".embed_layers.1.weight", prefix + ".embed_layers.1.bias", d_emb, cout))
+                else:
+                    self.linear_bwd(temb, prefix + ".embed_layers.1.weight", prefix + ".embed_layers.1.bias", d_emb, ted, cout, 1, self.G(temb))
+                # 6-7. data gradient and the fused operand load's backward into the block inputs
+                if am == 0:
+                    da1, fused1 = self.dgrad3(gh1, Hout, cin, cout, prefix + ".in_layers.2.weight", gnb=(srcs, g1, prefix + ".in_layers.0"))
+                else:                                            # a resampling sits between the activation and the convolution
+                    da1, fused1 = self.dgrad3(gh1, Hout, cin, cout, prefix + ".in_layers.2.weight"), None
+                self.gn_bwd(srcs, Hin, da1, Pout, g1, prefix + ".in_layers.0", 1, am,
+                            dres=(gh2 if r.skip == "identity" else None), fused=fused1)
+        self._bw.append(bwd)
+        return r
 
-        def resample_layer(prefix, kind, x, Hc, C, conv):
-            """Downsample / Upsample of the biggan_updown=False topology (UNet.py:60-92): raw activations in (no norm, no activation).
-            Forward as the inference plan (unet._Plan); backward: the weight gradient on the plain operand, the data gradient as
-            the forward kernel on the flipped weights, and the adjoint of the resampling around it."""
-            def rs(inp, Hin, mode, out, scale=1.0, acc=0):
-                st = ResampleArgs()
-                st.inp, st.out = inp.data_ptr(), out.data_ptr()
-                st.B, st.H, st.W, st.C, st.mode, st.scale, st.accumulate = B, Hin, Hin, C, mode, scale, acc
-                self.add(_lib.OP_RESAMPLE, st)
+    def attn_block(self, prefix, x, Hc, C):
+        r = super().attn_block(prefix, x, Hc, C)
+        B, L, heads, ch, g, att, Pm, y = self.B, r.L, r.heads, r.ch, r.g, r.att, r.probs, r.out
+        Z = B * heads
+        alpha = 1.0 / math.sqrt(ch)
+        qp = r.qkv.data_ptr()
 
-            def into_gx(dy, H, wkey):
-                """dx (+)= conv3x3(dy, flipped weights), straight into the gradient buffer of x"""
-                gx = self.G(x)
-                acc = self.gacc(x)
-                self.igemm(srcs=[(dy, C)], H=H, W=H, ks=3, N=C, bmat=lambda: self.pack(wkey, 0, bwd=1),
-                           wino=lambda: self.pack(wkey, 1, bwd=1), wino43=lambda: self.pack(wkey, 5, bwd=1),
-                           res=(gx if acc else None), out=gx)
+        def bwd():
+            gy = self.G(y)
+            with self.in_backward():
+                # proj_out: dW, d(att)
+                self.wgrad1([(att, C)], L, None, 0, gy, C, C, prefix + ".proj_out.weight", prefix + ".proj_out.bias")
+                datt = self.buf(B, L, C)
+                self.igemm(srcs=[(gy, C)], H=Hc, W=Hc, ks=1, N=C, kind="qkvproj",
+                           bmat=self.pack(prefix + ".proj_out.weight", "conv", bwd=1, k0=0, kc=C), out=datt)
+                dqkv = self.buf(B, L, 3 * C)
+                dq = dqkv.data_ptr()
+                dP = self.buf(Z, L, L)
+                T1 = self.buf(Z, L, L)
+                # dP = d(att)_h v_h^T
+                self.igemm(srcs=[(datt.data_ptr(), ch, C)], H=1, W=L, ks=1, N=L, b_mode=1, ldb=3 * C, heads=heads,
+                           bmat=qp + 4 * 2 * ch, kind="attn", a_strides=(L * C, ch), b_strides=(L * 3 * C, 3 * ch),
+                           out=dP, out_ld=L, o_strides=(heads * L * L, L * L))
+                # dV_h = P^T d(att)_h
+                tr = TransposeArgs()
+                tr.inp, tr.out, tr.Z, tr.L = Pm.data_ptr(), T1.data_ptr(), Z, L
+                self.add(_lib.OP_TRANSPOSE, tr)
+                self.igemm(srcs=[(T1.data_ptr(), L, L)], H=1, W=L, ks=1, N=ch, b_mode=2, ldb=C, heads=heads,
+                           bmat=datt.data_ptr(), kind="attn", a_strides=(heads * L * L, L * L), b_strides=(L * C, ch),
+                           out=dq + 4 * 2 * ch, out_ld=3 * C, o_strides=(L * 3 * C, 3 * ch))
+                # dS = P o (dP - rowsum(dP o P)), in place
+                sb = SoftmaxBwdArgs()
+                sb.p, sb.dp, sb.rows, sb.L = Pm.data_ptr(), dP.data_ptr(), Z * L, L
+                self.add(_lib.OP_SOFTMAX_BWD, sb)
+                # dQ_h = alpha dS k_h ; dK_h = alpha dS^T q_h
+                self.igemm(srcs=[(dP.data_ptr(), L, L)], H=1, W=L, ks=1, N=ch, b_mode=2, ldb=3 * C, heads=heads,
+                           bmat=qp + 4 * ch, alpha=alpha, kind="attn", a_strides=(heads * L * L, L * L),
+                           b_strides=(L * 3 * C, 3 * ch), out=dq, out_ld=3 * C, o_strides=(L * 3 * C, 3 * ch))
+                tr2 = TransposeArgs()
+                tr2.inp, tr2.out, tr2.Z, tr2.L = dP.data_ptr(), T1.data_ptr(), Z, L
+                self.add(_lib.OP_TRANSPOSE, tr2)
+                self.igemm(srcs=[(T1.data_ptr(), L, L)], H=1, W=L, ks=1, N=ch, b_mode=2, ldb=3 * C, heads=heads,
+                           bmat=qp, alpha=alpha, kind="attn", a_strides=(heads * L * L, L * L),
+                           b_strides=(L * 3 * C, 3 * ch), out=dq + 4 * ch, out_ld=3 * C, o_strides=(L * 3 * C, 3 * ch))
+                # to_qkv: dW (input = GroupNorm(x), no SiLU), d(normed x), GroupNorm backward + the residual
+                self.wgrad1([(x, C)], L, g, 0, dqkv, 3 * C, 3 * C, prefix + ".to_qkv.weight", prefix + ".to_qkv.bias")
+                da = self.buf(B, L, C)
+                self.igemm(srcs=[(dqkv, 3 * C)], H=Hc, W=Hc, ks=1, N=C, kind="qkvproj",
+                           bmat=self.pack(prefix + ".to_qkv.weight", "conv", bwd=1, k0=0, kc=C), out=da)
+                self.gn_bwd([(x, C)], Hc, da, L, g, prefix + ".norm", 0, 0, dres=gy)
+        self._bw.append(bwd)
+        return r
 
-            if kind == "downsample":
-                Ho = Hc // 2
-                out = self.buf(B, Ho * Ho, C)
+    def resample_layer(self, prefix, kind, x, Hc, C, conv):
+        """Downsample / Upsample of the biggan_updown=False topology (UNet.py:60-92).  Backward: the weight gradient on the plain
+        operand, the data gradient as the forward kernel on the flipped weights, and the adjoint of the resampling around it."""
+        r = super().resample_layer(prefix, kind, x, Hc, C, conv)
+        B, out, Ho, wk = self.B, r.out, r.H, r.wkey
+        bk = wk[:-len("weight")] + "bias" if conv else None
+
+        def bwd():
+            with self.in_backward():
                 if not conv:
-                    rs(x, Hc, 2, out)                                   # nn.AvgPool2d(2, 2)
-
-                    def bwd():
-                        with self.in_backward():
-                            rs(self.G(out), Ho, 1, self.G(x), 0.25, self.gacc(x))
-                    self._bw.append(bwd)
-                    return out, Ho
-                wk, bk = prefix + ".downsample.weight", prefix + ".downsample.bias"
-                full = self.buf(B, Hc * Hc, C)                          # the stride-1 result; the stride-2 output = its even pixels
-                self.igemm(srcs=[(x, C)], H=Hc, W=Hc, ks=3, N=C, act=0, bmat=lambda: self.pack(wk, 0), wino=lambda: self.pack(wk, 1),
-                           wino43=lambda: self.pack(wk, 5), bias=bias(bk), out=full)
-                rs(full, Hc, 3, out)
-
-                def bwd():
+                    # avg pool -> nearest-up / 4; nearest x2 -> the sum of the four children
+                    mode, scale = (1, 0.25) if kind == "downsample" else (2, 4.0)
+                    self.resample(self.G(out), Ho, C, mode, self.G(x), scale, self.gacc(x))
+                elif kind == "downsample":
                     gfull = self.buf(B, Hc * Hc, C)
-                    with self.in_backward():
-                        rs(self.G(out), Ho, 4, gfull)                   # gradient on the stride-1 grid: zeros off the even pixels
-                        self.wgrad3([(x, C)], Hc, Hc, None, 0, gfull, C, wk, bk)
-                        into_gx(gfull, Hc, wk)
-                self._bw.append(bwd)
-                return out, Ho
-            Ho = Hc * 2
-            out = self.buf(B, Ho * Ho, C)
-            if not conv:
-                rs(x, Hc, 1, out)                                       # F.interpolate(scale_factor=2, mode="nearest")
-
-                def bwd():
-                    with self.in_backward():
-                        rs(self.G(out), Ho, 2, self.G(x), 4.0, self.gacc(x))
-                self._bw.append(bwd)
-                return out, Ho
-            wk, bk = prefix + ".conv.weight", prefix + ".conv.bias"
-            self.igemm(srcs=[(x, C)], H=Ho, W=Ho, ks=3, N=C, act=0, a_mode=1, bmat=lambda: self.pack(wk, 0), wino=lambda: self.pack(wk, 1),
-                       wino43=lambda: self.pack(wk, 5), bias=bias(bk), out=out, want_stats=True)
-
-            def bwd():
-                with self.in_backward():
+                    self.resample(self.G(out), Ho, C, 4, gfull)     # gradient on the stride-1 grid: zeros off the even pixels
+                    self.wgrad3([(x, C)], Hc, Hc, None, 0, gfull, C, wk, bk)
+                    # dx (+)= conv3x3(dy, flipped weights), straight into the gradient buffer of x
+                    gx = self.G(x)
+                    acc = self.gacc(x)
+                    self.igemm(srcs=[(gfull, C)], H=Hc, W=Hc, ks=3, N=C, **self.conv_weights(wk, bwd=1),
+                               res=(gx if acc else None), out=gx)
+                else:
                     self.wgrad3([(x, C)], Hc, Ho, None, 1, self.G(out), C, wk, bk)
-                    dup = dgrad3(self.G(out), Ho, C, C, wk)             # gradient of the upsampled operand, at the output resolution
-                    rs(dup, Ho, 2, self.G(x), 4.0, self.gacc(x))        # nearest x2 -> the sum of the four children
-            self._bw.append(bwd)
-            return out, Ho
+                    dup = self.dgrad3(self.G(out), Ho, C, C, wk)    # gradient of the upsampled operand, at the output resolution
+                    self.resample(dup, Ho, C, 2, self.G(x), 4.0, self.gacc(x))   # nearest x2 -> the sum of the four children
+        self._bw.append(bwd)
+        return r
 
-        Hc = S
-        srcs = None
-        skips = []
-        for blk in down:
-            srcs, Hc = run(blk, srcs, Hc)
-            skips.append(srcs[0])
-        srcs, Hc = run(middle, srcs, Hc)
-        for blk in up:
-            srcs, Hc = run(blk, [srcs[0], skips.pop()], Hc)
-
-        # --- head (UNet.py:384-388, 405)
-        hfin, cfin = srcs[0]
-        gh = self.gn_t([(hfin, cfin)], S * S, "out.0")
-        nout = m.in_channels
-        self.y = self.buf(B, nout, S, S)
-        st = HeadArgs()
-        st.x, st.w, st.bias = hfin.data_ptr(), self.pack("out.2.weight", 3).data_ptr(), bias("out.2.bias")
-        st.gn_scale, st.gn_shift, st.out = gh[0].data_ptr(), gh[1].data_ptr(), self.y.data_ptr()
-        st.B, st.H, st.W, st.C, st.Cout = B, S, S, cfin, nout
-        self.add(_lib.OP_HEAD, st)
+    def head_block(self, hfin, cfin):
+        r = super().head_block(hfin, cfin)
+        B, S, gh, nout = self.B, self.S, r.g, r.nout
         self.dy = self.buf(B, nout, S, S)
 
         def head_bwd():
@@ -821,22 +620,7 @@ class TrainPlan(_Plan):
             self.badd(_lib.OP_HEAD_BWD, hb)
             self.gn_bwd([(hfin, cfin)], S, da, S * S, gh, "out.0", 1, 0)
         self._bw.append(head_bwd)
-
-        # --- backward list: the stages in reverse
-        for fn in reversed(self._bw):
-            self._touched = set()
-            fn()
-            self.bwd_marks.append((len(self.bops), sorted(self._touched)))
-        # split-K workspace of the inference emitters (forward and backward igemm launches) + the training workspace
-        if self._ws_need:
-            ws = self.buf(self._ws_need)
-            for code, st in self.ops + self.bops:
-                if code == _lib.OP_IGEMM and st.ksplit > 1:
-                    st.ws = ws.data_ptr()
-        if self._tws_need:
-            tws = self.buf(self._tws_need)
-            for st, field in self._ws_patch:
-                setattr(st, field, tws.data_ptr())
+        return r
 
     # ------------------------------------------------------------------ execution
     def run_forward(self, x, t):

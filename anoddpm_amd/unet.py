@@ -18,6 +18,7 @@ op lists of the native training plan (train_plan.py) behind one autograd Functio
 import ctypes
 import math
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -507,8 +508,54 @@ def choose_conv_cfg(H, W, K, N, Z, *, ks=3, a_mode=0, b_mode=0, heads=1, c0=None
     return cfg, ksplit
 
 
+# The layouts a weight is packed into (anoddpm_pack_args.kind): "conv3" / "conv1" [taps][I/4][O][4] for the direct 3x3 and the
+# pointwise kernels, "wino" / "wino43" Winograd-domain 3x3 for F(2x2) / F(4x4), "small" [9][I][O] for the stem / head kernels,
+# "copy" as is.  The one naming both plans use (_Plan.packed, TrainPlan.pack).
+PACK_KINDS = {"conv3": 0, "wino": 1, "conv1": 2, "small": 3, "copy": 4, "wino43": 5}
+_PACK_TAPS = {0: 9, 1: 16, 2: 1, 3: 9, 4: 1, 5: 36}          # packed floats per (output, input) channel pair
+
+
+def pack_kind(kind, shape):
+    """anoddpm_pack_args.kind of the layout named `kind`; "conv" is the direct layout of whatever the weight is (3x3 or pointwise)."""
+    if kind == "conv":
+        kind = "conv3" if (len(shape) == 4 and shape[2] == 3) else "conv1"
+    return PACK_KINDS[kind]
+
+
+def pack_floats(kind, N, K, bwd=0, kc=0):
+    """Floats of the packed copy of an [N][K][...] weight in layout `kind` (a PackArgs.kind); bwd: the data-gradient twin of a
+    pointwise weight covers `kc` of its input channels."""
+    return N * kc if (kind == PACK_KINDS["conv1"] and bwd) else _PACK_TAPS[kind] * N * K
+
+
+def _op_array(ops):
+    arr = (Op * len(ops))()
+    for i, (code, st) in enumerate(ops):
+        arr[i].code = code
+        arr[i].flags = 0
+        arr[i].args = ctypes.addressof(st)
+    return arr
+
+
+def _pack_table(jobs, device):
+    """The device-resident job table of ONE anoddpm_pack_batch launch over the PackArgs structs `jobs` (a block finds its job by
+    bisection of `block0`): (PackBatchArgs, job tensor, block0 tensor) -- the caller keeps the tensors alive."""
+    arr = (PackArgs * len(jobs))()
+    block0 = [0]
+    for i, st in enumerate(jobs):
+        ctypes.memmove(ctypes.addressof(arr[i]), ctypes.addressof(st), ctypes.sizeof(PackArgs))
+        block0.append(block0[-1] + int(lib().anoddpm_pack_job_blocks(ctypes.byref(st))))
+    raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    b0 = torch.tensor(block0, dtype=torch.int32).to(device)
+    pb = PackBatchArgs()
+    pb.jobs, pb.block0, pb.njobs, pb.nblocks = raw.data_ptr(), b0.data_ptr(), len(jobs), block0[-1]
+    return pb, raw, b0
+
+
 class _Plan:
     """Compiled forward for one (batch, size, device): buffers + packed weights + flat op list."""
+    honours_arith = True         # ANODDPM_ARITH selects the opt-in split-bf16 F(4x4) layers; the training plan (a subclass) never does
+    honours_csum = True          # ANODDPM_CSUM selects the fp64-atomic GroupNorm sums; the training plan never does
 
     def __init__(self, model, B, S, device):
         self.model = model
@@ -520,11 +567,10 @@ class _Plan:
         self._packed = {}
         # ANODDPM_ARITH=bf16split3: the OPT-IN side configuration of the large 3x3 layers (csrc/winograd43b.hip: split-bf16 products,
         # not the reference's arithmetic class); inference plan only, never the default
-        self.arith = os.environ.get("ANODDPM_ARITH", "fp32") if type(self) is _Plan else "fp32"
+        self.arith = os.environ.get("ANODDPM_ARITH", "fp32") if self.honours_arith else "fp32"
         if self.arith not in ("fp32", "bf16split3"):
             raise ValueError(f"ANODDPM_ARITH={self.arith}: expected fp32 or bf16split3")
         self.token = None
-        self.flops = {"conv3": 0.0, "conv1": 0.0, "attn": 0.0, "qkvproj": 0.0}
         self.igemm_flops = 0.0
         self._ws_need = 0
         self.stats_of = {}
@@ -537,7 +583,7 @@ class _Plan:
         # 0.2-0.6 % (9.05-9.09 -> 9.05-9.06 ms, 9.02-9.06 -> 8.98-9.00 on another box; profiles/r6_csum_ab.txt) -- the atomics and
         # the fold put 2-3 us of the 4.7 us launch they remove back into the F(4x4) launches.  Off by default: statistics rows +
         # finalize launches everywhere (what the training plan always does: its backward needs mean / rstd as tensors).
-        self.csum_mode = type(self) is _Plan and os.environ.get("ANODDPM_CSUM", "0") == "1"
+        self.csum_mode = self.honours_csum and os.environ.get("ANODDPM_CSUM", "0") == "1"
         self._csum_arena, self._csum_used = None, 0
         if self.csum_mode:
             cap = 2 * B * sum(p.shape[0] for p in model.parameters() if p.dim() == 4 and p.shape[-1] == 3)
@@ -548,12 +594,7 @@ class _Plan:
         if self.csum_mode and getattr(self, "posemb", None) is not None:
             self.posemb.zero = self._csum_arena.data_ptr() if self._csum_used else None
             self.posemb.zero_doubles = self._csum_used
-        n = len(self.ops)
-        self.op_array = (Op * n)()
-        for i, (code, st) in enumerate(self.ops):
-            self.op_array[i].code = code
-            self.op_array[i].flags = 0
-            self.op_array[i].args = ctypes.addressof(st)
+        self.op_array = _op_array(self.ops)
 
     # -- small helpers ------------------------------------------------------------------
     def buf(self, *shape, dtype=torch.float32):
@@ -561,11 +602,8 @@ class _Plan:
         self.keep.append(t)
         return t
 
-    _PACK_KINDS = {"conv": None, "wino": 1, "wino43": 5, "copy": 4, "small": 3}
-
     def packed(self, key, kind, out=None):
-        """Plan-owned device buffer holding parameter `key` in the layout `kind` names ("conv": [taps][I/4][O][4] direct 3x3 or
-        pointwise, "wino" / "wino43": Winograd-domain 3x3, "small": [9][I][O] for the stem / head kernels, "copy": as is).  Filled by
+        """Plan-owned device buffer holding parameter `key` in the layout `kind` names (PACK_KINDS, or "conv").  Filled by
         ONE anoddpm_pack_batch launch over all of the plan's weights (refresh_weights) -- no ATen / rocBLAS kernel."""
         ck = (key, kind, None if out is None else out.data_ptr())
         hit = self._packed.get(ck)
@@ -580,15 +618,10 @@ class _Plan:
             self._bf16_jobs.append((key, dst, N, K))
             self._packed[ck] = dst
             return dst
-        k = self._PACK_KINDS[kind]
-        if kind == "conv":
-            k = 0 if (len(shape) == 4 and shape[2] == 3) else 2
-        if k == 4:
-            N, K, n_out = p.numel(), 1, p.numel()
-        else:
-            N, K = shape[0], shape[1]
-            n_out = {0: 9, 1: 16, 2: 1, 3: 9, 5: 36}[k] * N * K
-        if k in (0, 1, 2, 5) and K % 4:
+        k = pack_kind(kind, shape)
+        N, K = (p.numel(), 1) if k == PACK_KINDS["copy"] else (shape[0], shape[1])
+        n_out = pack_floats(k, N, K)
+        if k not in (PACK_KINDS["small"], PACK_KINDS["copy"]) and K % 4:
             raise NotImplementedError(f"{key}: input channel count {K} must be a multiple of 4")
         dst = out if out is not None else torch.empty(n_out, dtype=torch.float32, device=self.device)
         self.keep.append(dst)
@@ -611,22 +644,14 @@ class _Plan:
         if token == self.token:
             return
         named = dict(self.model.named_parameters())
-        jobs = (PackArgs * len(self._pack_jobs))()
-        block0 = [0]
-        for i, (key, st) in enumerate(self._pack_jobs):
+        for key, st in self._pack_jobs:
             src = named[key]
             if src.device != self.device:
                 raise _lib.AnoddpmError(f"parameter {key} is on {src.device}, plan is on {self.device}")
             if src.dtype != torch.float32 or not src.is_contiguous():
                 raise _lib.AnoddpmError(f"parameter {key} must be contiguous fp32")
             st.w = src.data_ptr()
-            ctypes.memmove(ctypes.addressof(jobs[i]), ctypes.addressof(st), ctypes.sizeof(PackArgs))
-            block0.append(block0[-1] + int(lib().anoddpm_pack_job_blocks(ctypes.byref(st))))
-        with torch.no_grad():
-            raw = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(self.device)
-            b0 = torch.tensor(block0, dtype=torch.int32).to(self.device)
-        pb = PackBatchArgs()
-        pb.jobs, pb.block0, pb.njobs, pb.nblocks = raw.data_ptr(), b0.data_ptr(), len(self._pack_jobs), block0[-1]
+        pb, raw, b0 = _pack_table([st for _, st in self._pack_jobs], self.device)
         check(lib().anoddpm_pack_batch(ctypes.byref(pb), _lib.current_stream()), "weight packing")
         for key, dst, N, K in self._bf16_jobs:
             check(lib().anoddpm_pack_wino43_bf16x3(named[key].data_ptr(), dst.data_ptr(), N, K, _lib.current_stream()), "bf16 weight planes")
@@ -686,21 +711,51 @@ class _Plan:
             return scale, shift, mean, rstd
         return scale, shift
 
-    def gn(self, srcs, P, gamma_key, beta_key, fold=False):
-        """GroupNorm(32) affine of one or two concatenated sources from their per-channel partial sums
-        (emitted by the producing igemm's epilogue).  Returns (scale, shift) [B][Ctot] -- or, with `fold` (the only consumer is a
-        cfg 5 contraction, which finishes the GroupNorm in its own prologue), a _GnFold descriptor and NO launch."""
+    def gn_sums(self, srcs, P):
+        """Every source of a GroupNorm gets per-channel partial sums: its producer's epilogue wrote them, else a chan_stats pass."""
+        for s in srcs:
+            if s[0].data_ptr() not in self.stats_of:
+                self.chan_stats(s[0], s[1], P)
+
+    def gn_finalize(self, srcs, P, gamma, beta, want_mean=False):
+        """The stand-alone finalize launch over the partial sums of one or two concatenated sources: (scale, shift) [B][Ctot],
+        with `want_mean` also (mean, rstd) [B][32]."""
         B = self.B
         c0 = srcs[0][1]
         c1 = srcs[1][1] if len(srcs) > 1 else 0
-        C = c0 + c1
-        for buf, c in [(s[0], s[1]) for s in srcs]:
-            if buf.data_ptr() not in self.stats_of:
-                self.chan_stats(buf, c, P)
-        gamma, beta = self.packed(gamma_key, "copy").data_ptr(), self.packed(beta_key, "copy").data_ptr()
+        st = GnFinalizeArgs()
+        self.stats_source(st, 0, srcs[0][0], c0)
+        if c1:
+            self.stats_source(st, 1, srcs[1][0], c1)
+        else:
+            st.stats1, st.rows1, st.fmt1 = None, 0, 0
+        st.gamma, st.beta = gamma, beta
+        out = (self.buf(B, c0 + c1), self.buf(B, c0 + c1))
+        st.scale, st.shift = out[0].data_ptr(), out[1].data_ptr()
+        if want_mean:
+            out += (self.buf(B, 32), self.buf(B, 32))
+            st.mean_out, st.rstd_out = out[2].data_ptr(), out[3].data_ptr()
+        st.c0, st.c1, st.P, st.B, st.groups, st.eps = c0, c1, P, B, 32, 1e-5
+        self.add(_lib.OP_GN_FINALIZE, st)
+        return out
+
+    def gn(self, srcs, P, prefix, into=None):
+        """GroupNorm(32) affine `prefix`.weight / .bias of one or two concatenated sources from their per-channel partial sums
+        (emitted by the producing igemm's epilogue).  Returns (scale, shift) [B][Ctot] -- or, when its only consumer `into` =
+        (H, N, ks, a_mode) is a contraction that finishes the GroupNorm in its own prologue (cfg 5 / 6, or F(4x4,3x3) over fp64
+        sums), a _GnFold descriptor and NO launch."""
+        self.gn_sums(srcs, P)
+        gamma, beta = self.param(prefix + ".weight"), self.param(prefix + ".bias")
         job = self.gn_tail_job(srcs, gamma, beta)
         if job is not None:
             return job
+        c0 = srcs[0][1]
+        C = sum(s[1] for s in srcs)
+        fold = False
+        if into is not None:
+            H, N, ks, a_mode = into
+            fold = (self.small(H, H, C, N, ks=ks, a_mode=a_mode, c0=c0) or
+                    (ks == 3 and self.f43_fold(H, H, C, N, a_mode=a_mode, c0=c0, c1=C - c0)))
         if fold == "f43" and not all(self.stats_of[s_[0].data_ptr()][0] in ("csum", "asum") for s_ in srcs):
             fold = False                      # an F(4x4,3x3) consumer folds fp64 sums only: a rows source keeps the finalize launch
         if fold and C % 32 == 0:
@@ -711,18 +766,7 @@ class _Plan:
                 kind, buf, extra = self.stats_of[s[0].data_ptr()]
                 d.src.append((buf.data_ptr(), extra if kind == "rows" else 1, 0 if kind == "rows" else 1))
             return d
-        st = GnFinalizeArgs()
-        self.stats_source(st, 0, srcs[0][0], c0)
-        if c1:
-            self.stats_source(st, 1, srcs[1][0], c1)
-        else:
-            st.stats1, st.rows1, st.fmt1 = None, 0, 0
-        st.gamma, st.beta = gamma, beta
-        scale, shift = self.buf(B, C), self.buf(B, C)
-        st.scale, st.shift = scale.data_ptr(), shift.data_ptr()
-        st.c0, st.c1, st.P, st.B, st.groups, st.eps = c0, c1, P, B, 32, 1e-5
-        self.add(_lib.OP_GN_FINALIZE, st)
-        return scale, shift
+        return self.gn_finalize(srcs, P, gamma, beta)
 
     def csum_take(self, n):
         """`n` doubles of the plan's accumulator arena (cleared at the start of every forward), as a tensor view."""
@@ -734,7 +778,7 @@ class _Plan:
 
     def f43_fold(self, H, W, K, N, *, a_mode=0, c0=None, c1=0):
         """"f43" when a 3x3 contraction with these parameters will run on the F(4x4,3x3) kernels without split-K -- they finish a
-        GroupNorm whose sources are all fp64 sums in their prologue (gn(fold="f43")) -- else False."""
+        GroupNorm whose sources are all fp64 sums in their prologue (gn) -- else False."""
         if not self.csum_mode or self.arith != "fp32" or a_mode not in (0, 1) or os.environ.get("ANODDPM_CSUM_NOFOLD", "0") == "1":
             return False
         cfg, ksplit = choose_conv_cfg(H, W, K, N, self.B, ks=3, a_mode=a_mode, c0=(K if c0 is None else c0), c1=c1,
@@ -760,7 +804,6 @@ class _Plan:
         if not hasattr(self, "attention_log"):
             self.attention_log = []
         self.attention_log.append(dict(kind="attn_fused", L=L, ch=ch, heads=heads, gflop=fl / 1e9))
-        self.flops["attn"] = self.flops.get("attn", 0.0) + fl
         self.igemm_flops += fl
         return True
 
@@ -795,7 +838,6 @@ class _Plan:
             st.fold_stats0, st.fold_rows0, st.fold_fmt0 = fold.src[0]
             if c1:
                 st.fold_stats1, st.fold_rows1, st.fold_fmt1 = fold.src[1]
-        self._pending_bmat = (st, bmat, wino)
         st.b_bs, st.b_hs = b_strides
         st.bias = (bias if isinstance(bias, int) else bias.data_ptr()) if bias is not None else None
         st.temb = temb if temb else None
@@ -842,16 +884,15 @@ class _Plan:
                 rs.B, rs.H, rs.W, rs.C, rs.mode = B, H // 2, W // 2, N, 1
                 self.add(_lib.OP_RESAMPLE, rs)
                 st.res = sk.data_ptr()
-        _st, _bmat, _wino = self._pending_bmat
         if cfg == 7:
-            _bmat = wino43("wino43b")                          # F(4x4,3x3) weights as three bf16 planes
+            bmat = wino43("wino43b")                           # F(4x4,3x3) weights as three bf16 planes
         elif cfg == 3:
-            _bmat = wino43()                                   # F(4x4,3x3) weights
+            bmat = wino43()                                    # F(4x4,3x3) weights
         elif cfg in (2, 6):
-            _bmat = _wino()                                    # Winograd-domain weights for this layer
-        elif callable(_bmat):
-            _bmat = _bmat()                                    # packed lazily: only the layout this launch uses
-        st.bmat = _bmat if isinstance(_bmat, int) else _bmat.data_ptr()
+            bmat = wino()                                      # Winograd-domain weights for this layer
+        elif callable(bmat):
+            bmat = bmat()                                      # packed lazily: only the layout this launch uses
+        st.bmat = bmat if isinstance(bmat, int) else bmat.data_ptr()
         st.ws = None                      # patched after the build (one shared workspace)
         if ksplit > 1:
             self._ws_need = max(self._ws_need, ksplit * Z * P * N)
@@ -907,250 +948,240 @@ class _Plan:
                                    res=(0.0 if not st.res else (0.25 if st.res_mode == 1 else 1.0))))
         if want_stats and st.stats is None and not st.tail_csum and not st.stats_csum:
             self.chan_stats(out, N, P)
-        fl = 2.0 * K * N * ks * ks * P * Z
-        self.flops[kind] = self.flops.get(kind, 0.0) + fl
-        self.igemm_flops += fl
+        self.igemm_flops += 2.0 * K * N * ks * ks * P * Z
         return st
 
     # -- network ------------------------------------------------------------------------------
-    def _build(self):
-        m = self.model
-        B, S, dev = self.B, self.S, self.device
-        base, ted = m.model_channels, m._ted
-        down, middle, up = m._blocks
-        # --- timestep path: features -> MLP -> all per-block projections in one launch (UNet.py:271-276,185-188)
-        half = base // 2
-        freqs = _posemb_freqs(half).to(dev)
+    # The forward, stated once for the inference plan and the training plan (train_plan.TrainPlan inherits it).  One method per
+    # block kind; each returns a record of what it produced -- what a backward needs to know.  The points where the two plans
+    # differ are the overridable methods `weight` / `param` (where a weight layout / a bias or affine parameter is read), `gn`
+    # (how a GroupNorm is finished), `time_path` / `emb_of` (timestep MLP and embedding projections), `pool_act`, and the class
+    # attributes `keep_probs` / `p_drop` (+ the `dropout` emitter the training plan defines).
+    keep_probs = False           # attention probabilities are scratch (the training plan keeps them for its backward)
+    p_drop = 0.0                 # nn.Dropout of ResBlock.out_layers (UNet.py:192) is the identity in eval mode
+
+    def weight(self, key, kind):
+        """Parameter `key` in the layout `kind` (PACK_KINDS, or "conv"), as a tensor."""
+        return self.packed(key, kind)
+
+    def param(self, key):
+        """Address a bias / affine parameter is read at."""
+        return self.packed(key, "copy").data_ptr()
+
+    def conv_weights(self, key, **twin):
+        """The layouts of a 3x3 weight igemm chooses from, packed lazily: only the one the launch uses."""
+        return dict(bmat=lambda: self.weight(key, "conv", **twin), wino=lambda: self.weight(key, "wino", **twin),
+                    wino43=lambda kind="wino43": self.weight(key, kind, **twin))
+
+    def pool_act(self):
+        """Down ResBlock: ONE pass over x gives both the pooled skip input and the pooled ACTIVATED operand of the first
+        convolution, which then runs on the Winograd kernels instead of the pool-fused direct one (ANODDPM_NO_POOL_ACT=1: A/B)."""
+        return os.environ.get("ANODDPM_NO_POOL_ACT", "0") != "1"
+
+    def linear(self, inp, w, bias, K, N, act_in, act_out=0):
+        st = LinearArgs()
+        st.inp, st.w, st.bias = inp.data_ptr(), w, bias
+        o = self.buf(self.B, N)
+        st.out = o.data_ptr()
+        st.B, st.K, st.N, st.act_in, st.act_out = self.B, K, N, act_in, act_out
+        self.add(_lib.OP_LINEAR, st)
+        return o
+
+    def resample(self, inp, H, C, mode, out, scale=1.0, acc=0):
+        """2x resample of [B][H*H][C] (csrc/unet_kernels.hip: mode 1 nearest up, 2 average pool, 3 even-pixel pick, 4 its adjoint)."""
+        st = ResampleArgs()
+        st.inp, st.out = inp.data_ptr(), out.data_ptr()
+        st.B, st.H, st.W, st.C, st.mode, st.scale, st.accumulate = self.B, H, H, C, mode, scale, acc
+        return self.add(_lib.OP_RESAMPLE, st)
+
+    def posemb_features(self):
+        """Sinusoidal timestep features [B][base] (UNet.py:271): the plan's first op."""
+        B, base = self.B, self.model.model_channels
+        freqs = _posemb_freqs(base // 2).to(self.device)
         self.keep.append(freqs)
         pe = self.buf(B, base)
         self.posemb = PosembArgs()
         self.posemb.t, self.posemb.freqs, self.posemb.out = None, freqs.data_ptr(), pe.data_ptr()
         self.posemb.B, self.posemb.dim, self.posemb.scale = B, base, 1.0
         self.add(_lib.OP_POSEMB, self.posemb)
+        return pe
 
-        def linear(inp, wkey, bkey, K, N, act_in, act_out, w=None, b=None):
-            st = LinearArgs()
-            st.inp = inp.data_ptr()
-            wt = w if w is not None else self.packed(wkey, "copy")
-            bt = b if b is not None else self.packed(bkey, "copy")
-            st.w, st.bias = wt.data_ptr(), bt.data_ptr()
-            o = self.buf(B, N)
-            st.out = o.data_ptr()
-            st.B, st.K, st.N, st.act_in, st.act_out = B, K, N, act_in, act_out
-            self.add(_lib.OP_LINEAR, st)
-            return o
-        h1 = linear(pe, "time_embedding.1.weight", "time_embedding.1.bias", base, ted, 0, 1)
-        temb = linear(h1, "time_embedding.3.weight", "time_embedding.3.bias", ted, ted, 0, 0)
-        self.temb = temb
-
+    def time_path(self):
+        """Timestep path: features -> MLP -> all per-block projections in one launch over a packed, concatenated copy of their
+        weights (UNet.py:271-276,185-188)."""
+        m = self.model
+        base, ted = m.model_channels, m._ted
+        down, middle, up = m._blocks
+        pe = self.posemb_features()
+        h1 = self.linear(pe, self.param("time_embedding.1.weight"), self.param("time_embedding.1.bias"), base, ted, 0, 1)
+        self.temb = self.linear(h1, self.param("time_embedding.3.weight"), self.param("time_embedding.3.bias"), ted, ted, 0, 0)
         res_blocks = [b for grp in (down, [middle], up) for blk in grp for b in blk if b[1] == "res"]
-        offs, tot = {}, 0
+        self._emb_off, tot = {}, 0
         for b in res_blocks:
-            offs[b[0]] = tot
+            self._emb_off[b[0]] = tot
             tot += b[3]
         w_all = self.buf(tot, ted)
         b_all = self.buf(tot)
         for blk_ in res_blocks:                                  # every block's projection copied into the concatenated matrix
-            o = offs[blk_[0]]
+            o = self._emb_off[blk_[0]]
             self.packed(blk_[0] + ".embed_layers.1.weight", "copy", out=w_all[o:o + blk_[3]])
             self.packed(blk_[0] + ".embed_layers.1.bias", "copy", out=b_all[o:o + blk_[3]])
-        emb_all = linear(temb, None, None, ted, tot, 1, 0, w=w_all, b=b_all)
-        self.emb_tot = tot
+        self._emb_tot = tot
+        self._emb_all = self.linear(self.temb, w_all.data_ptr(), b_all.data_ptr(), ted, tot, 1, 0)
 
-        # --- blocks ---------------------------------------------------------------------------
-        def res_block(prefix, srcs, Hin, cout, resample):
-            cin = sum(s[1] for s in srcs)
-            Hout = Hin * 2 if resample == "up" else (Hin // 2 if resample == "down" else Hin)
-            Pin, Pout = Hin * Hin, Hout * Hout
-            g1 = self.gn(srcs, Pin, prefix + ".in_layers.0.weight", prefix + ".in_layers.0.bias",
-                         fold=(resample in (None, "up") and (self.small(Hout, Hout, cin, cout, ks=3, c0=srcs[0][1],
-                                                                        a_mode=(1 if resample == "up" else 0)) or
-                                                             self.f43_fold(Hout, Hout, cin, cout, a_mode=(1 if resample == "up" else 0),
-                                                                           c0=srcs[0][1], c1=cin - srcs[0][1]))))
-            h1 = self.buf(B, Pout, cout)
-            pooled = None
-            if resample == "down" and len(srcs) == 1 and os.environ.get("ANODDPM_NO_POOL_ACT", "0") != "1":
-                # down block: ONE pass over x gives both the pooled skip input and the pooled ACTIVATED operand of the first
-                # convolution, which then runs on the Winograd kernels instead of the pool-fused direct one
-                pooled = self.buf(B, Pout, cin)
-                sk_pool = self.buf(B, Pout, cin)
-                st = ResampleArgs()
-                st.inp, st.out = srcs[0][0].data_ptr(), sk_pool.data_ptr()
-                st.B, st.H, st.W, st.C, st.mode, st.scale, st.accumulate = B, Hin, Hin, cin, 2, 1.0, 0
-                st.gn_scale, st.gn_shift, st.out_act = g1[0].data_ptr(), g1[1].data_ptr(), pooled.data_ptr()
-                self.add(_lib.OP_RESAMPLE, st)
-            self.igemm(srcs=([(pooled, cin)] if pooled is not None else srcs), H=Hout, W=Hout, ks=3, N=cout,
-                       gn=(None if pooled is not None else g1), act=(0 if pooled is not None else 1),
-                       a_mode=(0 if pooled is not None else {None: 0, "up": 1, "down": 2}[resample]),
-                       bmat=lambda p=prefix: self.packed(p + ".in_layers.2.weight", "conv"),
-                       wino=lambda p=prefix: self.packed(p + ".in_layers.2.weight", "wino"),
-                       wino43=lambda kind="wino43", p=prefix: self.packed(p + ".in_layers.2.weight", kind),
-                       bias=self.packed(prefix + ".in_layers.2.bias", "copy"),
-                       temb=emb_all.data_ptr() + 4 * offs[prefix], temb_ld=tot, out=h1, want_stats=True)
-            g2 = self.gn([(h1, cout)], Pout, prefix + ".out_layers.0.weight", prefix + ".out_layers.0.bias",
-                         fold=(self.small(Hout, Hout, cout, cout, ks=3) or self.f43_fold(Hout, Hout, cout, cout)))
-            if cin != cout:
-                sk = self.buf(B, Pout, cout)
-                assert resample is None
-                self.igemm(srcs=srcs, H=Hout, W=Hout, ks=1, N=cout, kind="conv1",
-                           bmat=self.packed(prefix + ".skip_connection.weight", "conv"),
-                           bias=self.packed(prefix + ".skip_connection.bias", "copy"), out=sk)
-            elif resample is not None and pooled is not None:
-                sk = sk_pool
-            elif resample == "up":
-                assert len(srcs) == 1
-                sk = None                                          # igemm(res_up=...) below: fused into the F(4x4) epilogue, else materialised there
-            elif resample is not None:
-                assert len(srcs) == 1
-                sk = self.buf(B, Pout, cout)
-                st = ResampleArgs()
-                st.inp, st.out = srcs[0][0].data_ptr(), sk.data_ptr()
-                st.B, st.H, st.W, st.C, st.mode = B, Hin, Hin, cin, 2
-                self.add(_lib.OP_RESAMPLE, st)
-            else:
-                if len(srcs) != 1:
-                    raise NotImplementedError("identity skip over a concatenated input (cin == cout) is not built")
-                sk = srcs[0][0]
-            h2 = self.buf(B, Pout, cout)
-            self.igemm(srcs=[(h1, cout)], H=Hout, W=Hout, ks=3, N=cout, gn=g2, act=1,
-                       bmat=lambda p=prefix: self.packed(p + ".out_layers.3.weight", "conv"),
-                       wino=lambda p=prefix: self.packed(p + ".out_layers.3.weight", "wino"),
-                       wino43=lambda kind="wino43", p=prefix: self.packed(p + ".out_layers.3.weight", kind),
-                       bias=self.packed(prefix + ".out_layers.3.bias", "copy"),
-                       res=sk, res_up=(srcs[0][0] if (resample == "up" and sk is None) else None), out=h2, want_stats=True)
-            return h2, Hout
+    def emb_of(self, prefix, cout):
+        """(pointer, row pitch) of a ResBlock's embedding projection: a column range of the batched launch."""
+        return self._emb_all.data_ptr() + 4 * self._emb_off[prefix], self._emb_tot
 
-        def attn_block(prefix, x, Hc, C):
-            L = Hc * Hc
-            heads = m._heads_for(C)
-            ch = C // heads
-            if ch % 4:
-                raise NotImplementedError(f"attention head width {ch} must be a multiple of 4")
-            g = self.gn([(x, C)], L, prefix + ".norm.weight", prefix + ".norm.bias", fold=self.small(Hc, Hc, C, 3 * C, ks=1))
-            qkv = self.buf(B, L, 3 * C)
-            self.igemm(srcs=[(x, C)], H=Hc, W=Hc, ks=1, N=3 * C, gn=g, act=0, kind="qkvproj",
-                       bmat=self.packed(prefix + ".to_qkv.weight", "conv"),
-                       bias=self.packed(prefix + ".to_qkv.bias", "copy"), out=qkv)
-            att = self.buf(B, L, C)
-            if not self.attention(qkv, att, L, heads, ch):
-                S_ = self.buf(B * heads, L, L)
-                qp = qkv.data_ptr()
-                # scores = (q*s)^T (k*s), s = ch^-1/4  ->  alpha = ch^-1/2 on the product (UNet.py:147-150)
-                self.igemm(srcs=[(qp, ch, 3 * C)], H=1, W=L, ks=1, N=L, b_mode=1, ldb=3 * C, heads=heads,
-                           bmat=qp + 4 * ch, alpha=1.0 / math.sqrt(ch), kind="attn",
-                           a_strides=(L * 3 * C, 3 * ch), b_strides=(L * 3 * C, 3 * ch),
-                           out=S_, out_ld=L, o_strides=(heads * L * L, L * L))
-                sm = SoftmaxArgs()
-                sm.x, sm.rows, sm.L = S_.data_ptr(), B * heads * L, L
-                self.add(_lib.OP_SOFTMAX, sm)
-                self.igemm(srcs=[(S_.data_ptr(), L, L)], H=1, W=L, ks=1, N=ch, b_mode=2, ldb=3 * C, heads=heads,
-                           bmat=qp + 4 * 2 * ch, kind="attn",
-                           a_strides=(heads * L * L, L * L), b_strides=(L * 3 * C, 3 * ch),
-                           out=att, out_ld=C, o_strides=(L * C, ch))
-            y = self.buf(B, L, C)
-            self.igemm(srcs=[(att, C)], H=Hc, W=Hc, ks=1, N=C, kind="qkvproj",
-                       bmat=self.packed(prefix + ".proj_out.weight", "conv"),
-                       bias=self.packed(prefix + ".proj_out.bias", "copy"),
-                       res=x, out=y, want_stats=True)
-            return y
+    def stem_block(self, prefix, cin, cout):
+        B, S = self.B, self.S
+        h0 = self.buf(B, S * S, cout)
+        self.stem = StemArgs()
+        self.stem.x = None
+        self.stem.w = self.weight(prefix + ".weight", "small").data_ptr()
+        self.stem.bias = self.param(prefix + ".bias")
+        self.stem.out = h0.data_ptr()
+        self.stem.B, self.stem.H, self.stem.W, self.stem.Cin, self.stem.Cout = B, S, S, cin, cout
+        rows = lib().anoddpm_stem_stats_rows(S, S, cin, cout)
+        if rows > 0 and os.environ.get("ANODDPM_NO_STEM_STATS", "0") != "1":
+            # GroupNorm partial sums of the stem output from the stem kernel itself (no chan_stats pass over it)
+            sstats = self.buf(B, rows, cout, 2)
+            self.stem.stats, self.stem.stats_rows = sstats.data_ptr(), rows
+            self.stats_of[h0.data_ptr()] = ("rows", sstats, rows)
+        self.add(_lib.OP_STEM, self.stem)
+        return SimpleNamespace(out=h0, C=cout, H=S, prefix=prefix, cin=cin)
 
-        def resample_layer(prefix, kind, x, Hc, C, conv):
-            """Downsample / Upsample of the biggan_updown=False topology (UNet.py:60-92) on raw activations (no norm, no
-            activation).  The stride-2 convolution runs as the stride-1 one on the existing kernels followed by the even-pixel
-            pick (its outputs are exactly those of the stride-1 result at (2i, 2j)): 4x the necessary work on a layer no
-            shipped configuration uses, zero new contraction code."""
-            def rs(inp, H, mode, out):
-                st = ResampleArgs()
-                st.inp, st.out = inp.data_ptr(), out.data_ptr()
-                st.B, st.H, st.W, st.C, st.mode, st.scale, st.accumulate = B, H, H, C, mode, 1.0, 0
-                self.add(_lib.OP_RESAMPLE, st)
-            if kind == "downsample":
-                Ho = Hc // 2
-                out = self.buf(B, Ho * Ho, C)
-                if not conv:
-                    rs(x, Hc, 2, out)                                   # nn.AvgPool2d(2, 2)
-                    return out, Ho
-                full = self.buf(B, Hc * Hc, C)
-                self.igemm(srcs=[(x, C)], H=Hc, W=Hc, ks=3, N=C, act=0,
-                           bmat=lambda p=prefix: self.packed(p + ".downsample.weight", "conv"),
-                           wino=lambda p=prefix: self.packed(p + ".downsample.weight", "wino"),
-                           wino43=lambda kind="wino43", p=prefix: self.packed(p + ".downsample.weight", kind),
-                           bias=self.packed(prefix + ".downsample.bias", "copy"), out=full)
-                rs(full, Hc, 3, out)
-                return out, Ho
-            Ho = Hc * 2
-            out = self.buf(B, Ho * Ho, C)
-            if not conv:
-                rs(x, Hc, 1, out)                                       # F.interpolate(scale_factor=2, mode="nearest")
-                return out, Ho
-            self.igemm(srcs=[(x, C)], H=Ho, W=Ho, ks=3, N=C, act=0, a_mode=1,      # nearest x2 fused into the operand load
-                       bmat=lambda p=prefix: self.packed(p + ".conv.weight", "conv"),
-                       wino=lambda p=prefix: self.packed(p + ".conv.weight", "wino"),
-                       wino43=lambda kind="wino43", p=prefix: self.packed(p + ".conv.weight", kind),
-                       bias=self.packed(prefix + ".conv.bias", "copy"), out=out, want_stats=True)
-            return out, Ho
+    def res_block(self, prefix, srcs, Hin, cout, resample):
+        B = self.B
+        cin = sum(s[1] for s in srcs)
+        Hout = Hin * 2 if resample == "up" else (Hin // 2 if resample == "down" else Hin)
+        Pin, Pout = Hin * Hin, Hout * Hout
+        am = {None: 0, "up": 1, "down": 2}[resample]
+        g1 = self.gn(srcs, Pin, prefix + ".in_layers.0", into=(None if resample == "down" else (Hout, cout, 3, am)))
+        emb_ptr, emb_ld = self.emb_of(prefix, cout)
+        h1 = self.buf(B, Pout, cout)
+        pooled = None
+        if resample == "down" and self.pool_act():
+            assert len(srcs) == 1                                # (the down path has no concatenated input)
+            pooled, sk_pool = self.buf(B, Pout, cin), self.buf(B, Pout, cin)
+            st = self.resample(srcs[0][0], Hin, cin, 2, sk_pool)
+            st.gn_scale, st.gn_shift, st.out_act = g1[0].data_ptr(), g1[1].data_ptr(), pooled.data_ptr()
+        self.igemm(srcs=([(pooled, cin)] if pooled is not None else srcs), H=Hout, W=Hout, ks=3, N=cout,
+                   gn=(None if pooled is not None else g1), act=(0 if pooled is not None else 1),
+                   a_mode=(0 if pooled is not None else am),
+                   **self.conv_weights(prefix + ".in_layers.2.weight"), bias=self.param(prefix + ".in_layers.2.bias"),
+                   temb=emb_ptr, temb_ld=emb_ld, out=h1, want_stats=True)
+        g2 = self.gn([(h1, cout)], Pout, prefix + ".out_layers.0", into=(Hout, cout, 3, 0))
+        skip = "resample"
+        if cin != cout:
+            assert resample is None
+            skip, sk = "conv", self.buf(B, Pout, cout)
+            self.igemm(srcs=srcs, H=Hout, W=Hout, ks=1, N=cout, kind="conv1",
+                       bmat=self.weight(prefix + ".skip_connection.weight", "conv"),
+                       bias=self.param(prefix + ".skip_connection.bias"), out=sk)
+        elif pooled is not None:
+            sk = sk_pool
+        elif resample == "up" and self.p_drop == 0:
+            # nearest x2 of the block input as the residual: igemm(res_up=...) below fuses it into the F(4x4) epilogue, else
+            # materialises it there.  Not offered with dropout: that plan has always materialised it here, ahead of the dropout launch
+            assert len(srcs) == 1
+            sk = None
+        elif resample is not None:
+            assert len(srcs) == 1
+            sk = self.buf(B, Pout, cout)
+            # scale: the kernel treats 0 (what the pool of a down block has always carried) and 1 alike (resample2x_kernel scales
+            # only when `scale != 0 && scale != 1`); both spellings are kept so that the emitted structs stay byte-identical
+            self.resample(srcs[0][0], Hin, cin, (1 if resample == "up" else 2), sk, scale=(1.0 if resample == "up" else 0.0))
+        else:
+            if len(srcs) != 1:
+                raise NotImplementedError("identity skip over a concatenated input (cin == cout) is not built")
+            skip, sk = "identity", srcs[0][0]
+        h2 = self.buf(B, Pout, cout)
+        # with dropout the dropped activation is materialised and the second convolution sees a plain operand
+        a2 = self.dropout(h1, g2, Pout, cout) if self.p_drop > 0 else None
+        self.igemm(srcs=[(h1 if a2 is None else a2, cout)], H=Hout, W=Hout, ks=3, N=cout,
+                   gn=(g2 if a2 is None else None), act=(1 if a2 is None else 0),
+                   **self.conv_weights(prefix + ".out_layers.3.weight"), bias=self.param(prefix + ".out_layers.3.bias"),
+                   res=sk, res_up=(srcs[0][0] if (resample == "up" and sk is None) else None), out=h2, want_stats=True)
+        return SimpleNamespace(out=h2, C=cout, H=Hout, prefix=prefix, srcs=srcs, Hin=Hin, cin=cin, a_mode=am, resample=resample,
+                               g1=g1, g2=g2, h1=h1, a2=a2, skip=skip)
 
-        def run(blks, srcs, Hc):
-            for (prefix, kind, cin, cout, resample) in blks:
-                if kind == "stem":
-                    h0 = self.buf(B, S * S, cout)
-                    self.stem = StemArgs()
-                    self.stem.x = None
-                    self.stem.w = self.packed(prefix + ".weight", "small").data_ptr()
-                    self.stem.bias = self.packed(prefix + ".bias", "copy").data_ptr()
-                    self.stem.out = h0.data_ptr()
-                    self.stem.B, self.stem.H, self.stem.W, self.stem.Cin, self.stem.Cout = B, S, S, cin, cout
-                    rows = lib().anoddpm_stem_stats_rows(S, S, cin, cout)
-                    if rows > 0 and os.environ.get("ANODDPM_NO_STEM_STATS", "0") != "1":
-                        # GroupNorm partial sums of the stem output from the stem kernel itself (no chan_stats pass over it)
-                        sstats = self.buf(B, rows, cout, 2)
-                        self.stem.stats, self.stem.stats_rows = sstats.data_ptr(), rows
-                        self.stats_of[h0.data_ptr()] = ("rows", sstats, rows)
-                    self.add(_lib.OP_STEM, self.stem)
-                    self.flops["conv3"] += 2.0 * cin * cout * 9 * S * S * B
-                    srcs = [(h0, cout)]
-                elif kind == "res":
-                    h, Hc = res_block(prefix, srcs, Hc, cout, resample)
-                    srcs = [(h, cout)]
-                elif kind in ("downsample", "upsample"):
-                    h, Hc = resample_layer(prefix, kind, srcs[0][0], Hc, cin, resample == "conv")
-                    srcs = [(h, cin)]
-                else:
-                    h = attn_block(prefix, srcs[0][0], Hc, cin)
-                    srcs = [(h, cin)]
-                self.block_out[prefix] = (srcs[0][0], srcs[0][1], Hc)
-            return srcs, Hc
+    def attn_block(self, prefix, x, Hc, C):
+        B = self.B
+        L = Hc * Hc
+        heads = self.model._heads_for(C)
+        ch = C // heads
+        if ch % 4:
+            raise NotImplementedError(f"attention head width {ch} must be a multiple of 4")
+        g = self.gn([(x, C)], L, prefix + ".norm", into=(Hc, 3 * C, 1, 0))
+        qkv = self.buf(B, L, 3 * C)
+        self.igemm(srcs=[(x, C)], H=Hc, W=Hc, ks=1, N=3 * C, gn=g, act=0, kind="qkvproj",
+                   bmat=self.weight(prefix + ".to_qkv.weight", "conv"), bias=self.param(prefix + ".to_qkv.bias"), out=qkv)
+        att = self.buf(B, L, C)
+        probs = self.buf(B * heads, L, L) if self.keep_probs else None
+        if not self.attention(qkv, att, L, heads, ch, probs=probs):
+            S_ = probs if probs is not None else self.buf(B * heads, L, L)       # scores, softmaxed in place
+            qp = qkv.data_ptr()
+            # scores = (q*s)^T (k*s), s = ch^-1/4  ->  alpha = ch^-1/2 on the product (UNet.py:147-150)
+            self.igemm(srcs=[(qp, ch, 3 * C)], H=1, W=L, ks=1, N=L, b_mode=1, ldb=3 * C, heads=heads,
+                       bmat=qp + 4 * ch, alpha=1.0 / math.sqrt(ch), kind="attn",
+                       a_strides=(L * 3 * C, 3 * ch), b_strides=(L * 3 * C, 3 * ch),
+                       out=S_, out_ld=L, o_strides=(heads * L * L, L * L))
+            sm = SoftmaxArgs()
+            sm.x, sm.rows, sm.L = S_.data_ptr(), B * heads * L, L
+            self.add(_lib.OP_SOFTMAX, sm)
+            self.igemm(srcs=[(S_.data_ptr(), L, L)], H=1, W=L, ks=1, N=ch, b_mode=2, ldb=3 * C, heads=heads,
+                       bmat=qp + 4 * 2 * ch, kind="attn",
+                       a_strides=(heads * L * L, L * L), b_strides=(L * 3 * C, 3 * ch),
+                       out=att, out_ld=C, o_strides=(L * C, ch))
+        y = self.buf(B, L, C)
+        self.igemm(srcs=[(att, C)], H=Hc, W=Hc, ks=1, N=C, kind="qkvproj",
+                   bmat=self.weight(prefix + ".proj_out.weight", "conv"), bias=self.param(prefix + ".proj_out.bias"),
+                   res=x, out=y, want_stats=True)
+        return SimpleNamespace(out=y, C=C, H=Hc, prefix=prefix, x=x, L=L, heads=heads, ch=ch, g=g, qkv=qkv, att=att, probs=probs)
 
-        Hc = S
-        srcs = None
-        skips = []
-        for blk in down:
-            srcs, Hc = run(blk, srcs, Hc)
-            skips.append(srcs[0])
-        srcs, Hc = run(middle, srcs, Hc)
-        for blk in up:
-            srcs, Hc = run(blk, [srcs[0], skips.pop()], Hc)
+    def resample_layer(self, prefix, kind, x, Hc, C, conv):
+        """Downsample / Upsample of the biggan_updown=False topology (UNet.py:60-92) on raw activations (no norm, no
+        activation).  The stride-2 convolution runs as the stride-1 one on the existing kernels followed by the even-pixel
+        pick (its outputs are exactly those of the stride-1 result at (2i, 2j)): 4x the necessary work on a layer no
+        shipped configuration uses, zero new contraction code."""
+        B = self.B
+        Ho = Hc // 2 if kind == "downsample" else Hc * 2
+        out = self.buf(B, Ho * Ho, C)
+        full = wkey = None
+        if not conv:
+            self.resample(x, Hc, C, (2 if kind == "downsample" else 1), out)    # nn.AvgPool2d(2, 2) / F.interpolate(scale_factor=2, mode="nearest")
+        elif kind == "downsample":
+            wkey = prefix + ".downsample.weight"
+            full = self.buf(B, Hc * Hc, C)                          # the stride-1 result; the stride-2 output = its even pixels
+            self.igemm(srcs=[(x, C)], H=Hc, W=Hc, ks=3, N=C, act=0, **self.conv_weights(wkey),
+                       bias=self.param(prefix + ".downsample.bias"), out=full)
+            self.resample(full, Hc, C, 3, out)
+        else:
+            wkey = prefix + ".conv.weight"
+            self.igemm(srcs=[(x, C)], H=Ho, W=Ho, ks=3, N=C, act=0, a_mode=1, **self.conv_weights(wkey),      # nearest x2 fused into the operand load
+                       bias=self.param(prefix + ".conv.bias"), out=out, want_stats=True)
+        return SimpleNamespace(out=out, C=C, H=Ho, prefix=prefix, kind=kind, conv=conv, x=x, Hin=Hc, full=full, wkey=wkey)
 
-        # --- head: GN + SiLU + 3x3 conv to in_channels (UNet.py:384-388,405)
-        hfin, cfin = srcs[0]
-        g = self.gn([(hfin, cfin)], S * S, "out.0.weight", "out.0.bias")
-        nout = m.in_channels
+    def head_block(self, hfin, cfin):
+        """Head: GN + SiLU + 3x3 conv to in_channels (UNet.py:384-388,405)."""
+        B, S = self.B, self.S
+        g = self.gn([(hfin, cfin)], S * S, "out.0")
+        nout = self.model.in_channels
         if nout <= 4 and S % 8 == 0 and (100 * (cfin + 16) + 9 * cfin * nout) * 4 <= 64 * 1024:
-            # dedicated HBM-bound head kernel, writes the caller's NCHW layout directly
+            # dedicated HBM-bound head kernel, writes the caller's NCHW layout directly (train_plan.eligible() admits only these shapes)
             self.y = self.buf(B, nout, S, S)
             st = HeadArgs()
             st.x = hfin.data_ptr()
-            st.w = self.packed("out.2.weight", "small").data_ptr()
-            st.bias = self.packed("out.2.bias", "copy").data_ptr()
+            st.w = self.weight("out.2.weight", "small").data_ptr()
+            st.bias = self.param("out.2.bias")
             st.gn_scale, st.gn_shift, st.out = g[0].data_ptr(), g[1].data_ptr(), self.y.data_ptr()
             st.B, st.H, st.W, st.C, st.Cout = B, S, S, cfin, nout
             self.add(_lib.OP_HEAD, st)
-            self.flops["conv3"] += 2.0 * cfin * nout * 9 * S * S * B
         else:
             y_nhwc = self.buf(B, S * S, nout)
             self.igemm(srcs=[(hfin, cfin)], H=S, W=S, ks=3, N=nout, gn=g, act=1,
-                       bmat=self.packed("out.2.weight", "conv"),
-                       bias=self.packed("out.2.bias", "copy"), out=y_nhwc)
+                       bmat=self.weight("out.2.weight", "conv"), bias=self.param("out.2.bias"), out=y_nhwc)
             if nout == 1:
                 self.y = y_nhwc.view(B, 1, S, S)
             else:
@@ -1158,12 +1189,46 @@ class _Plan:
                 st = LayoutArgs()
                 st.inp, st.out, st.B, st.P, st.C, st.in_ld = y_nhwc.data_ptr(), self.y.data_ptr(), B, S * S, nout, nout
                 self.add(_lib.OP_LAYOUT, st)
-        # one split-K workspace shared by every op (ops run in stream order)
+        return SimpleNamespace(x=hfin, C=cfin, g=g, nout=nout)
+
+    def run_blocks(self, blks, srcs, Hc):
+        for (prefix, kind, cin, cout, resample) in blks:
+            if kind == "stem":
+                r = self.stem_block(prefix, cin, cout)
+            elif kind == "res":
+                r = self.res_block(prefix, srcs, Hc, cout, resample)
+            elif kind in ("downsample", "upsample"):
+                r = self.resample_layer(prefix, kind, srcs[0][0], Hc, cin, resample == "conv")
+            else:
+                r = self.attn_block(prefix, srcs[0][0], Hc, cin)
+            srcs, Hc = [(r.out, r.C)], r.H
+            self.block_out[prefix] = (r.out, r.C, Hc)
+        return srcs, Hc
+
+    def walk(self):
+        """The whole forward: timestep path, down / middle / up with the skip stack, head."""
+        self.time_path()
+        down, middle, up = self.model._blocks
+        Hc, srcs, skips = self.S, None, []
+        for blk in down:
+            srcs, Hc = self.run_blocks(blk, srcs, Hc)
+            skips.append(srcs[0])
+        srcs, Hc = self.run_blocks(middle, srcs, Hc)
+        for blk in up:
+            srcs, Hc = self.run_blocks(blk, [srcs[0], skips.pop()], Hc)
+        return self.head_block(*srcs[0])
+
+    def share_workspace(self, ops):
+        """One split-K workspace shared by every igemm of `ops` (ops run in stream order)."""
         if self._ws_need:
             ws = self.buf(self._ws_need)
-            for code, st in self.ops:
+            for code, st in ops:
                 if code == _lib.OP_IGEMM and st.ksplit > 1:
                     st.ws = ws.data_ptr()
+
+    def _build(self):
+        self.walk()
+        self.share_workspace(self.ops)
 
     def run(self, x, t):
         """x: contiguous fp32 [B,C,S,S] on self.device; t: int64 [B].  Returns the plan-owned output."""
