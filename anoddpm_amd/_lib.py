@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ANODDPM_LIB_TAG=<tag>: load lib/libanoddpm_hip_<tag>.so instead -- a second build of the same sources with other compiler flags
 # (ANODDPM_BUILD_TAG / ANODDPM_EXTRA_FLAGS of anoddpm_amd.build), for A/B measurements of one gpurun session.  Same ABI, same checks.
 SO_PATH = os.path.join(_HERE, "lib", "libanoddpm_hip%s.so" % ("_" + os.environ["ANODDPM_LIB_TAG"] if os.environ.get("ANODDPM_LIB_TAG") else ""))
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 OP_IGEMM, OP_GN_STATS, OP_SOFTMAX, OP_RESAMPLE, OP_LINEAR, OP_POSEMB, OP_STEM, OP_LAYOUT, OP_CHAN_STATS, OP_GN_FINALIZE, OP_HEAD = range(1, 12)
 (OP_WGRAD3, OP_WGRAD1, OP_GN_BWD, OP_PACK, OP_SOFTMAX_BWD, OP_TRANSPOSE, OP_LINEAR_BWD, OP_STEM_BWD, OP_HEAD_BWD,
@@ -251,7 +251,8 @@ class RocArgs(Structure):
     _fields_ = [("score", c_void_p), ("mask", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64),
                 ("auc", c_void_p), ("counts", c_void_p), ("status", c_void_p),
                 ("curve_fps", c_void_p), ("curve_tps", c_void_p), ("curve_thr", c_void_p), ("curve_len", c_void_p),
-                ("curve_cap", c_int64), ("n", c_int64), ("score_stride", c_int64), ("mask_stride", c_int64), ("S", c_int32)]
+                ("curve_cap", c_int64), ("n", c_int64), ("score_stride", c_int64), ("mask_stride", c_int64), ("S", c_int32),
+                ("curve_mode", c_int32), ("ap", c_void_p), ("best_dice", c_void_p), ("best_thr", c_void_p), ("best_counts", c_void_p)]
 
 
 class SsimArgs(Structure):
@@ -264,6 +265,7 @@ class SsimArgs(Structure):
 ANOMALY_NCOUNTS = 12
 ANOMALY_BLOCKS = 64
 ROC_NAN, ROC_INF, ROC_NEGATIVE, ROC_BAD_MASK, ROC_CURVE_TRUNCATED = 1, 2, 4, 8, 16      # bits of anoddpm_roc_args.status
+ROC_CURVE_DROP, ROC_CURVE_ALL = 0, 1                                                    # anoddpm_roc_args.curve_mode
 SSIM_UNIFORM, SSIM_GAUSSIAN = 0, 1                                                      # anoddpm_ssim_args.mode
 SSIM_MAX_WIN = 15
 

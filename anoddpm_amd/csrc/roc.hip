@@ -12,7 +12,14 @@
 //   4. twoU = sum_v P_v * (2 * N_below(v) + N_v) in uint64 (the tie-corrected Mann-Whitney statistic = the trapezoid area under
 //      sklearn's curve, independent of summation order), AUC = twoU / (2 P N) in fp64
 //   5. optionally the curve points sklearn keeps (drop_intermediate: first, last, and every point where the second difference of
-//      fps or tps is non-zero, i.e. where the next lower run has other counts), written compactly from the highest score down
+//      fps or tps is non-zero, i.e. where the next lower run has other counts), written compactly from the highest score down;
+//      curve mode ANODDPM_ROC_CURVE_ALL keeps every run instead (what sklearn.metrics.precision_recall_curve works on)
+//   6. optionally one more walk over the run list (the EXTRA instantiation; a launch that asks for none of it runs the plain one):
+//      per run r, tps_r = P - runtp[r] and cnt_r = n - runpos[r] = tps_r + fps_r are the counts of the prediction score >= thr_r
+//      - average precision = sum_r (p_r / P) * (tps_r / cnt_r) in fp64: thread t adds the runs t, t + 1024, ... in that order, a
+//        halving tree folds the 64 partials of a wave and then the 16 wave sums.  Fixed order, no atomics: same input, same bits
+//      - best Dice = max_r 2 tps_r / (cnt_r + P): a > b iff tps_a * den_b > tps_b * den_a, exact in uint64 (tps < 2^31, den <
+//        3 * 2^31); ties go to the higher score.  That order is total, so the reduction's shape does not matter
 // All counters are integers: the result is deterministic.  Compiled with -ffp-contract=off like the other metric kernels.
 #include "common.h"
 
@@ -69,6 +76,15 @@ __device__ __forceinline__ bool keep_point(const uint32_t *runpos, const uint32_
     return (tp1 - tp) != (tp - tpm) || (rs1 - rs) != (rs - rsm);
 }
 
+// candidate (tps, cnt, r) of the best Dice: is a better than b?  den = cnt + P
+__device__ __forceinline__ bool dice_better(uint32_t tpa, uint32_t ca, uint32_t ra, uint32_t tpb, uint32_t cb, uint32_t rb, uint32_t P)
+{
+    const unsigned long long x = (unsigned long long)tpa * ((unsigned long long)cb + P);
+    const unsigned long long y = (unsigned long long)tpb * ((unsigned long long)ca + P);
+    return x > y || (x == y && ra > rb);
+}
+
+template <bool EXTRA>
 __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, int64_t seg_words)
 {
     __shared__ uint32_t hist[WAVES * RADIX];                     // wave-private rows: digit counts, then scatter offsets
@@ -204,6 +220,7 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
 
     // ---- 4. + 5. per run, from the highest score down (q = R - 1 - r): its term of twoU, and its curve point if kept
     const bool want_curve = a.curve_fps != nullptr;
+    const bool all = EXTRA && a.curve_mode == ANODDPM_ROC_CURVE_ALL;     // every run is a curve point
     const uint32_t qchunk = ((R + WAVES - 1) / WAVES + 63u) & ~63u;
     const uint32_t q0 = min((uint32_t)wave * qchunk, R), q1 = min(q0 + qchunk, R);
     uint32_t carry_k = 0, K = 0;
@@ -211,7 +228,7 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
         uint32_t ck = 0;
         for (uint32_t base = q0; base < q1; base += 64) {
             const uint32_t q = base + lane;
-            const bool keep = q < q1 && keep_point(runpos, runtp, R - 1 - q, R);
+            const bool keep = q < q1 && (all || keep_point(runpos, runtp, R - 1 - q, R));
             ck += __popcll(__ballot(keep));
         }
         if (lane == 0) wtot_p[wave] = ck;                        // free since the barrier that ended step 3
@@ -230,7 +247,7 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
             tp = runtp[r];
             const uint32_t pr = runtp[r + 1] - tp, nr = (runpos[r + 1] - rs) - pr;
             acc += (unsigned long long)pr * (2ull * (rs - tp) + nr);     // rs - tp = negatives with a lower score
-            keep = want_curve && keep_point(runpos, runtp, r, R);
+            keep = want_curve && (all || keep_point(runpos, runtp, r, R));
         }
         if (want_curve) {
             const uint64_t bk = __ballot(keep);
@@ -262,6 +279,53 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
         a.status[seg] = (int32_t)(s_status | ((want_curve && (int64_t)K > a.curve_cap) ? ANODDPM_ROC_CURVE_TRUNCATED : 0u));
         if (want_curve) a.curve_len[seg] = (int32_t)K;
     }
+
+    // ---- 6. average precision and best Dice: one more walk over the runs, ascending, thread t takes r = t, t + THREADS, ...
+    if constexpr (EXTRA) {
+        const bool want_ap = a.ap != nullptr, want_best = a.best_dice != nullptr;
+        if (!want_ap && !want_best) return;                      // block-uniform
+        __shared__ double wap[WAVES];
+        __shared__ uint32_t wbt[WAVES], wbc[WAVES], wbr[WAVES];
+        const double dP = (double)P;
+        double part = 0.0;
+        uint32_t btp = 0, bc = 1, br = 0;                         // loses against every run, or is run 0 itself when P == 0
+        for (uint32_t r = tid; r < R; r += THREADS) {
+            const uint32_t tp0 = runtp[r], tps = P - tp0, cnt = n - runpos[r], pr = runtp[r + 1] - tp0;
+            // a run without positives adds +0.0, which leaves the bits of the partial as they are: skipped
+            if (want_ap && pr != 0) part += ((double)pr / dP) * ((double)tps / (double)cnt);
+            if (dice_better(tps, cnt, r, btp, bc, br, P)) { btp = tps; bc = cnt; br = r; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            part += __shfl_xor(part, off);
+            const uint32_t otp = __shfl_xor(btp, off), oc = __shfl_xor(bc, off), orr = __shfl_xor(br, off);
+            if (dice_better(otp, oc, orr, btp, bc, br, P)) { btp = otp; bc = oc; br = orr; }
+        }
+        if (lane == 0) { wap[wave] = part; wbt[wave] = btp; wbc[wave] = bc; wbr[wave] = br; }
+        __syncthreads();
+        if (wave == 0) {
+            part = lane < WAVES ? wap[lane] : 0.0;
+            btp = lane < WAVES ? wbt[lane] : 0u;
+            bc = lane < WAVES ? wbc[lane] : 1u;
+            br = lane < WAVES ? wbr[lane] : 0u;
+#pragma unroll
+            for (int off = WAVES / 2; off > 0; off >>= 1) {
+                part += __shfl_xor(part, off);
+                const uint32_t otp = __shfl_xor(btp, off), oc = __shfl_xor(bc, off), orr = __shfl_xor(br, off);
+                if (dice_better(otp, oc, orr, btp, bc, br, P)) { btp = otp; bc = oc; br = orr; }
+            }
+            if (lane == 0) {
+                if (want_ap) a.ap[seg] = P == 0 ? (double)NAN : (P == n ? 1.0 : part);
+                if (want_best) {
+                    const uint32_t rs = runpos[br], tps = P - runtp[br], cnt = n - rs;
+                    a.best_dice[seg] = P == 0 ? (double)NAN : (double)(2ull * tps) / (double)((unsigned long long)cnt + P);
+                    a.best_thr[seg] = __uint_as_float(src[rs] >> 1);
+                    a.best_counts[(int64_t)seg * 2] = tps;
+                    a.best_counts[(int64_t)seg * 2 + 1] = cnt - tps;
+                }
+            }
+        }
+    }
 }
 
 int64_t seg_words_of(int64_t n) { return (n + 1 + 63) / 64 * 64; }
@@ -290,6 +354,14 @@ extern "C" int anoddpm_roc_auc(const anoddpm_roc_args *a, void *stream)
         ANODDPM_REQUIRE(a->curve_fps && a->curve_tps && a->curve_thr && a->curve_len, "roc_auc: curve output needs curve_fps, curve_tps, curve_thr and curve_len");
         ANODDPM_REQUIRE(a->curve_cap >= 2, "roc_auc: curve capacity must be >= 2 points per segment");
     }
-    hipLaunchKernelGGL(roc_auc_kernel, dim3(a->S), dim3(THREADS), 0, as_stream(stream), *a, seg_words_of(a->n));
+    ANODDPM_REQUIRE(a->curve_mode == ANODDPM_ROC_CURVE_DROP || a->curve_mode == ANODDPM_ROC_CURVE_ALL, "roc_auc: unknown curve_mode");
+    ANODDPM_REQUIRE(a->curve_mode == ANODDPM_ROC_CURVE_DROP || any_curve, "roc_auc: curve_mode needs the curve outputs");
+    const bool any_best = a->best_dice || a->best_thr || a->best_counts;
+    if (any_best) ANODDPM_REQUIRE(a->best_dice && a->best_thr && a->best_counts, "roc_auc: best Dice output needs best_dice, best_thr and best_counts");
+    // the plain instantiation is the kernel as it was before average precision, best Dice and the full curve existed
+    if (a->ap || any_best || a->curve_mode != ANODDPM_ROC_CURVE_DROP)
+        hipLaunchKernelGGL(roc_auc_kernel<true>, dim3(a->S), dim3(THREADS), 0, as_stream(stream), *a, seg_words_of(a->n));
+    else
+        hipLaunchKernelGGL(roc_auc_kernel<false>, dim3(a->S), dim3(THREADS), 0, as_stream(stream), *a, seg_words_of(a->n));
     return check_launch("roc_auc");
 }

@@ -984,19 +984,26 @@ class GaussianDiffusionModel:
         rec.update(output=output, mean=maps["mean"], mse=maps["mse_img"], threshold=maps["thr_img"],
                    counts=counts)
         rec["auc"] = rec["auc_status"] = None                       # filled by _attach_auc when there is a mask
+        rec["ap"] = rec["best_dice"] = rec["best_threshold"] = None
         rec["ssim"] = None                                          # filled by _attach_ssim
         return rec, maps
 
     @staticmethod
     def _attach_auc(records, sqerrs, mask):
         """detection.py:230-231 for every setting of a sweep in ONE batched launch: `auc` (fp64 device scalar; NaN when the mask has
-        one class only or when `auc_status`, the kernel's status word, is non-zero) per record.  Never raises, never synchronises."""
+        one class only or when `auc_status`, the kernel's status word, is non-zero) per record, and from the same launch and the
+        same sort `ap` (average precision), `best_dice` (the largest Dice over all thresholds; both fp64 device scalars, NaN when
+        the mask has no positive or the status is non-zero) and `best_threshold` (fp32 device scalar: the highest threshold that
+        reaches it).  Never raises, never synchronises."""
         if mask is None or not records:
             return
         from . import metrics
-        auc, status = metrics.roc_auc(mask, torch.stack([s.reshape(-1) for s in sqerrs]), batched=True, return_status=True)
+        o = metrics._roc_launch(mask, torch.stack([s.reshape(-1) for s in sqerrs]), batched=True, curve=False, pr=True)
+        status = o["status"]
+        auc, ap, best = (metrics._nan_where_status(o[k], status) for k in ("auc", "ap", "best_dice"))
         for j, rec in enumerate(records):
             rec["auc"], rec["auc_status"] = auc[j], status[j]
+            rec["ap"], rec["best_dice"], rec["best_threshold"] = ap[j], best[j], o["best_threshold"][j]
 
     @staticmethod
     def _attach_ssim(records, x_0):

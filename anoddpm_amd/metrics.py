@@ -24,6 +24,14 @@ are; -0.0 is reported as +0.0) and masks 0 / 1: anything else sets a status word
 arguments of `ROC_AUC` and `AUC_score` go through sklearn as upstream; sklearn's UndefinedMetricWarning for an empty class is not
 re-issued by the native path (the arrays are NaN as sklearn's are).
 
+Precision-recall (sklearn's `precision_recall_curve` / `average_precision_score`, and the best Dice over all thresholds, which the
+reference has no counterpart of: it scores every map at the one cut 0.5) come from the SAME launch and the same sort: one more walk
+over the runs of equal score.  `average_precision` returns the `[S]` fp64 APs (fixed summation order: same input, same bits; within
+n * 2^-52 of sklearn), `best_dice` the largest `2 tp / (tp + fp + P)` over all thresholds -- found by exact integer comparison,
+ties to the highest threshold -- with that threshold and its `tp` / `fp`, both without a host synchronisation; `pr_points` every
+point of the curve as integer counts, `PR_curve` on device tensors sklearn's `(precision, recall, thresholds)` triple bit for bit.
+A segment without positives has AP = NaN and best Dice = NaN (sklearn: AP 0.0 after a warning); one without negatives has AP = 1.0.
+
 `anomaly_metrics` is the native entry: everything the metric loop needs from one launch and one 96-byte D2H copy (plus the AUC launch).
 The individual functions accept the reference's arguments; they use the fused pass when handed device tensors of
 the shapes the reference passes and raise `AnoddpmError` otherwise (no CPU path)."""
@@ -34,7 +42,7 @@ import torch
 from . import _lib
 from ._lib import AnomalyArgs, RocArgs, SsimArgs, check, current_stream, lib
 
-__all__ = ["anomaly_maps", "anomaly_metrics", "roc_auc", "roc_points", "ssim", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
+__all__ = ["anomaly_maps", "anomaly_metrics", "roc_auc", "roc_points", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
 
 NC = _lib.ANOMALY_NCOUNTS
@@ -119,9 +127,11 @@ def _segments(x, S, name):
     return x, n, x.stride(0)
 
 
-def _roc_launch(mask, score, batched, curve):
+def _roc_launch(mask, score, batched, curve, pr=False):
     """One `anoddpm_roc_auc` launch.  score: [S, ...] when batched, else one segment; mask: like score, or the shape of one
-    segment (one mask shared by every segment).  Returns a dict of device tensors; nothing is copied to the host."""
+    segment (one mask shared by every segment).  `pr` adds the average precision and the best Dice (`ap`, `best_dice`,
+    `best_threshold`, `best_counts`) and makes `curve` every run of equal score instead of the points sklearn's roc_curve keeps.
+    Returns a dict of device tensors; nothing is copied to the host."""
     if not isinstance(score, torch.Tensor) or not isinstance(mask, torch.Tensor):
         raise TypeError("roc: mask and score must be device tensors")
     S = score.shape[0] if batched else 1
@@ -157,6 +167,14 @@ def _roc_launch(mask, score, batched, curve):
         out["len"] = torch.empty((S,), dtype=torch.int32, device=dev)
         a.curve_fps, a.curve_tps, a.curve_thr = out["fps"].data_ptr(), out["tps"].data_ptr(), out["thresholds"].data_ptr()
         a.curve_len, a.curve_cap = out["len"].data_ptr(), cap
+        a.curve_mode = _lib.ROC_CURVE_ALL if pr else _lib.ROC_CURVE_DROP
+    if pr:
+        out["ap"] = torch.empty((S,), dtype=torch.float64, device=dev)
+        out["best_dice"] = torch.empty((S,), dtype=torch.float64, device=dev)
+        out["best_threshold"] = torch.empty((S,), dtype=torch.float32, device=dev)
+        out["best_counts"] = torch.empty((S, 2), dtype=torch.int64, device=dev)
+        a.ap, a.best_dice = out["ap"].data_ptr(), out["best_dice"].data_ptr()
+        a.best_thr, a.best_counts = out["best_threshold"].data_ptr(), out["best_counts"].data_ptr()
     with torch.cuda.device(dev):
         check(lib().anoddpm_roc_auc(ctypes.byref(a), current_stream()), "roc_auc")
     return out
@@ -191,6 +209,52 @@ def roc_points(mask, score, batched=None):
         res.append({"fps": o["fps"][s, :L].cpu().numpy().astype("int64"), "tps": o["tps"][s, :L].cpu().numpy().astype("int64"),
                     "thresholds": o["thresholds"][s, :L].cpu().numpy(), "auc": float(auc[s]),
                     "P": int(counts[s, 0]), "N": int(counts[s, 1]), "twoU": int(counts[s, 2])})
+    return res
+
+
+def _nan_where_status(x, status):
+    return torch.where(status != 0, torch.full_like(x, float("nan")), x)
+
+
+def average_precision(mask, score, batched=None, return_status=False):
+    """Average precision (area under the precision-recall curve as sklearn's `average_precision_score` defines it: the step sum
+    `sum_k (R_k - R_{k-1}) P_k` over the distinct scores) of every segment; arguments as `roc_auc`.  Returns an [S] fp64 device
+    tensor without a host synchronisation.  NaN where the segment has no positive: sklearn returns 0.0 after a warning there,
+    which would silently pull down a mean over slices, most of which have no lesion.  1.0 where it has no negative.  NaN where
+    the inputs break the precondition (`return_status=True` also returns the [S] int32 status words)."""
+    o = _roc_launch(mask, score, _is_batched(score, batched), curve=False, pr=True)
+    ap = _nan_where_status(o["ap"], o["status"])
+    return (ap, o["status"]) if return_status else ap
+
+
+def best_dice(mask, score, batched=None):
+    """The largest Dice `2 tp / (tp + fp + P)` the prediction `score >= threshold` reaches over all thresholds (the plain
+    definition, without the reference's 1e-6 smoothing), per segment; arguments as `roc_auc`.  Returns a dict of device tensors,
+    no host synchronisation: `dice` [S] fp64, `threshold` [S] fp32 (the highest one when several reach it), `tp` / `fp` [S] int64
+    at that threshold (precision, recall and IoU there follow from them and P), `status` [S] int32.  `dice` is NaN where the
+    segment has no positive and where the status is non-zero."""
+    o = _roc_launch(mask, score, _is_batched(score, batched), curve=False, pr=True)
+    return {"dice": _nan_where_status(o["best_dice"], o["status"]), "threshold": o["best_threshold"],
+            "tp": o["best_counts"][:, 0], "fp": o["best_counts"][:, 1], "status": o["status"]}
+
+
+def pr_points(mask, score, batched=None):
+    """Every point of the precision-recall curve, per segment: one per distinct score, from the highest threshold down, as the
+    integer counts of the prediction `score >= threshold`.  A list of dicts with `fps`, `tps` (int64), `thresholds` (fp32), `P`,
+    `N`, `ap`, `best_dice`, `best_threshold`, `best_tp`, `best_fp` (Python numbers).  Copies to the host; raises ValueError for
+    inputs outside the precondition."""
+    o = _roc_launch(mask, score, _is_batched(score, batched), curve=True, pr=True)
+    status, lens, counts = o["status"].cpu(), o["len"].cpu(), o["counts"].cpu()
+    for s, st in enumerate(status.tolist()):
+        if st:
+            raise ValueError(f"pr: segment {s}: {_roc_status_text(st)} (scores must be finite and >= 0, masks 0 or 1)")
+    ap, bd, bt, bc = o["ap"].cpu(), o["best_dice"].cpu(), o["best_threshold"].cpu(), o["best_counts"].cpu()
+    res = []
+    for s, L in enumerate(lens.tolist()):
+        res.append({"fps": o["fps"][s, :L].cpu().numpy().astype("int64"), "tps": o["tps"][s, :L].cpu().numpy().astype("int64"),
+                    "thresholds": o["thresholds"][s, :L].cpu().numpy(), "P": int(counts[s, 0]), "N": int(counts[s, 1]),
+                    "ap": float(ap[s]), "best_dice": float(bd[s]), "best_threshold": float(bt[s]),
+                    "best_tp": int(bc[s, 0]), "best_fp": int(bc[s, 1])})
     return res
 
 
@@ -272,13 +336,15 @@ def ssim(real, recon, batched=None, data_range=2.0, win_size=7, gaussian_weights
 
 def anomaly_metrics(real, recon, mask, threshold=0.5):
     """dice / IoU / precision / recall / FPR / mse / PSNR of detection.py:229-250 from one launch, the AUC of
-    detection.py:230-231 (the whole batch flattened into one curve, evaluation.py:81) from a second one and the SSIM of
+    detection.py:230-231 (the whole batch flattened into one curve, evaluation.py:81) from a second one -- which also gives `AP`
+    (average precision), `best_dice` and `best_threshold` (the largest Dice over all thresholds and the highest threshold that
+    reaches it; NaN like `AUC`, and NaN when the mask has no positive) of that same flattened curve -- and the SSIM of
     detection.py:241-246 (mean over the batch of the per-image SSIM of `real` against the `mean` map, i.e. the reconstruction
     averaged over `navg`) from a third.  Returns a dict of Python floats plus the maps (device tensors).  `AUC` is NaN when a
     class is empty or when `AUC_status` (the status word of the ROC kernel) is non-zero; without a mask there is no AUC (NaN,
     status 0).  `SSIM` is NaN when the inputs are not `[B, C, H, W]` or are smaller than the 7 x 7 window."""
     maps, counts = anomaly_maps(real, recon, mask, threshold)
-    roc = _roc_launch(mask, maps["sqerr"], batched=False, curve=False) if mask is not None else None
+    roc = _roc_launch(mask, maps["sqerr"], batched=False, curve=False, pr=True) if mask is not None else None
     ss = ssim(real, maps["mean"]) if real.dim() == 4 and min(real.shape[-2:]) >= 7 and real.numel() > 0 else None
     c = counts.cpu()
     r = {k: float(v) for k, v in _ratios(c).items() if k != "dice_per_image"}
@@ -288,6 +354,10 @@ def anomaly_metrics(real, recon, mask, threshold=0.5):
     r["PSNR"] = float(20.0 * torch.log10(torch.tensor(float(c[:, 10].max())) / torch.sqrt(torch.tensor(mse)))) if mse > 0 else float("inf")
     r["AUC_status"] = int(roc["status"].cpu()[0]) if roc is not None else 0
     r["AUC"] = float(roc["auc"].cpu()[0]) if roc is not None and r["AUC_status"] == 0 else float("nan")
+    for key, src in (("AP", "ap"), ("best_dice", "best_dice"), ("best_threshold", "best_threshold")):
+        r[key] = float(roc[src].cpu()[0]) if roc is not None and r["AUC_status"] == 0 else float("nan")
+    if r["best_dice"] != r["best_dice"]:
+        r["best_threshold"] = float("nan")                           # no positive: no threshold is better than another
     r["SSIM"] = float(ss.mean().cpu()) if ss is not None else float("nan")
     r["maps"] = maps
     return r
@@ -389,6 +459,25 @@ def ROC_AUC(real_mask, square_error):
     if isinstance(real_mask, torch.Tensor):
         return roc_curve(real_mask.detach().cpu().numpy().flatten(), square_error.detach().cpu().numpy().flatten())
     return roc_curve(real_mask.flatten(), square_error.flatten())
+
+
+def PR_curve(real_mask, square_error):
+    """sklearn's `precision_recall_curve(real_mask.flatten(), square_error.flatten())`: `(precision, recall, thresholds)` in
+    ascending threshold order with the final `(1, 0)` point appended.  Device tensors: the native sort (`pr_points` of the
+    flattened inputs); the host divides the integer counts in fp64, which gives sklearn's arrays bit for bit.  Recall is all
+    ones when the mask has no positive, as sklearn's is; its warning is not re-issued.  Host inputs (numpy arrays, CPU
+    tensors): sklearn."""
+    if isinstance(real_mask, torch.Tensor) and isinstance(square_error, torch.Tensor) and real_mask.is_cuda and square_error.is_cuda:
+        import numpy as np
+        p = pr_points(real_mask, square_error, batched=False)[0]
+        tps, fps = p["tps"].astype(np.float64), p["fps"].astype(np.float64)
+        prec = tps / (tps + fps)                                         # tps + fps >= 1: every point predicts something
+        rec = tps / tps[-1] if tps[-1] > 0 else np.ones_like(tps)
+        return np.hstack((prec[::-1], 1)), np.hstack((rec[::-1], 0)), p["thresholds"][::-1]
+    from sklearn.metrics import precision_recall_curve
+    if isinstance(real_mask, torch.Tensor):
+        return precision_recall_curve(real_mask.detach().cpu().numpy().flatten(), square_error.detach().cpu().numpy().flatten())
+    return precision_recall_curve(real_mask.flatten(), square_error.flatten())
 
 
 def AUC_score(fpr, tpr):

@@ -546,8 +546,19 @@ int anoddpm_anomaly_map(const anoddpm_anomaly_args *a, void *stream);
  *              [S][curve_cap] thresholds, curve_len[s] = points of segment s.  A segment with more than curve_cap points
  *              gets its first curve_cap points, its full count in curve_len and ANODDPM_ROC_CURVE_TRUNCATED; curve_cap = n
  *              (at least 2) always suffices.
+ *   curve_mode ANODDPM_ROC_CURVE_DROP (0): the points above.  ANODDPM_ROC_CURVE_ALL: one point per distinct score, nothing
+ *              dropped -- what sklearn.metrics.precision_recall_curve works on; needs the curve_* outputs
+ *   ap[s]      optional: average precision = sum over distinct scores v of (P_v / P) * (tps_v / (tps_v + fps_v)), the counts
+ *              being those of the prediction score >= v (sklearn.metrics.average_precision_score).  fp64, fixed summation
+ *              order (same input, same bits).  NaN when P == 0 (sklearn: 0.0 after a warning), 1.0 when N == 0
+ *   best_*     optional (all three or none): the largest Dice 2 tps / (tps + fps + P) over all thresholds, found by exact
+ *              integer comparison, ties to the highest threshold: best_dice[s] (one fp64 division; NaN when P == 0),
+ *              best_thr[s] that threshold, best_counts[s] = {tps, fps} of the prediction score >= best_thr[s]
  *   workspace  [dev] anoddpm_roc_workspace_bytes(S, n) bytes (three uint32 buffers of n + 1 words per segment)
- * n < 2^31.  twoU is exact in uint64; its conversion to fp64 is exact up to 2^53 (n <= 2^26 always is). */
+ * n < 2^31.  twoU is exact in uint64; its conversion to fp64 is exact up to 2^53 (n <= 2^26 always is).  A launch with
+ * curve_mode 0 and none of ap / best_* runs the same kernel as before these fields existed. */
+#define ANODDPM_ROC_CURVE_DROP 0
+#define ANODDPM_ROC_CURVE_ALL 1
 #define ANODDPM_ROC_NAN 1
 #define ANODDPM_ROC_INF 2
 #define ANODDPM_ROC_NEGATIVE 4
@@ -567,6 +578,11 @@ typedef struct anoddpm_roc_args {
     int64_t curve_cap;
     int64_t n, score_stride, mask_stride;
     int32_t S;
+    int32_t curve_mode;             /* ANODDPM_ROC_CURVE_* */
+    double *ap;                     /* [dev] [S] or NULL */
+    double *best_dice;              /* [dev] [S] or NULL */
+    float *best_thr;                /* [dev] [S] or NULL */
+    int64_t *best_counts;           /* [dev] [S][2] or NULL */
 } anoddpm_roc_args;
 
 int anoddpm_roc_auc(const anoddpm_roc_args *a, void *stream);
