@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ANODDPM_LIB_TAG=<tag>: load lib/libanoddpm_hip_<tag>.so instead -- a second build of the same sources with other compiler flags
 # (ANODDPM_BUILD_TAG / ANODDPM_EXTRA_FLAGS of anoddpm_amd.build), for A/B measurements of one gpurun session.  Same ABI, same checks.
 SO_PATH = os.path.join(_HERE, "lib", "libanoddpm_hip%s.so" % ("_" + os.environ["ANODDPM_LIB_TAG"] if os.environ.get("ANODDPM_LIB_TAG") else ""))
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 OP_IGEMM, OP_GN_STATS, OP_SOFTMAX, OP_RESAMPLE, OP_LINEAR, OP_POSEMB, OP_STEM, OP_LAYOUT, OP_CHAN_STATS, OP_GN_FINALIZE, OP_HEAD = range(1, 12)
 (OP_WGRAD3, OP_WGRAD1, OP_GN_BWD, OP_PACK, OP_SOFTMAX_BWD, OP_TRANSPOSE, OP_LINEAR_BWD, OP_STEM_BWD, OP_HEAD_BWD,
@@ -262,17 +262,36 @@ class SsimArgs(Structure):
                 ("S", c_int32), ("C", c_int32), ("H", c_int32), ("W", c_int32), ("win", c_int32), ("mode", c_int32)]
 
 
+class MedianArgs(Structure):
+    _fields_ = [("src", c_void_p), ("roi", c_void_p), ("dst", c_void_p), ("status", c_void_p),
+                ("src_stride", c_int64), ("roi_stride", c_int64), ("S", c_int32), ("H", c_int32), ("W", c_int32), ("k", c_int32)]
+
+
+class ErodeArgs(Structure):
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("src_stride", c_int64),
+                ("S", c_int32), ("H", c_int32), ("W", c_int32), ("n", c_int32), ("level", c_float)]
+
+
+class ComponentsArgs(Structure):
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("counts", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64),
+                ("src_stride", c_int64), ("S", c_int32), ("H", c_int32), ("W", c_int32),
+                ("min_size", c_int32), ("connectivity", c_int32), ("level", c_float)]
+
+
 ANOMALY_NCOUNTS = 12
 ANOMALY_BLOCKS = 64
 ROC_NAN, ROC_INF, ROC_NEGATIVE, ROC_BAD_MASK, ROC_CURVE_TRUNCATED = 1, 2, 4, 8, 16      # bits of anoddpm_roc_args.status
 ROC_CURVE_DROP, ROC_CURVE_ALL = 0, 1                                                    # anoddpm_roc_args.curve_mode
 SSIM_UNIFORM, SSIM_GAUSSIAN = 0, 1                                                      # anoddpm_ssim_args.mode
 SSIM_MAX_WIN = 15
+MEDIAN_SIZES = (3, 5, 7)                                                                # anoddpm_median_args.k
+ERODE_MAX = 8                                                                           # anoddpm_erode_args.n
 
 _STRUCTS = [SimplexArgs, PUpdateArgs, IgemmArgs, GnArgs, SoftmaxArgs, ResampleArgs, LinearArgs,
             PosembArgs, StemArgs, LayoutArgs, Op, AdamwArgs, ChanStatsArgs, GnFinalizeArgs, HeadArgs, AnomalyArgs, VlbArgs, WgradArgs, GnBwdArgs,
             Wgrad1Args, PackArgs, SoftmaxBwdArgs, TransposeArgs, LinearBwdArgs, StemBwdArgs, HeadBwdArgs, ColsumFoldArgs,
-            MriSliceArgs, ResizeArgs, AttentionArgs, PackBatchArgs, LinearBwdBatchArgs, LossArgs, DropoutArgs, RocArgs, SsimArgs]
+            MriSliceArgs, ResizeArgs, AttentionArgs, PackBatchArgs, LinearBwdBatchArgs, LossArgs, DropoutArgs, RocArgs, SsimArgs,
+            MedianArgs, ErodeArgs, ComponentsArgs]
 
 # every symbol include/anoddpm_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -289,6 +308,7 @@ SYMBOLS = [
     "anoddpm_volume_normalise", "anoddpm_mri_slice_prepare", "anoddpm_resize_bilinear_pil", "anoddpm_attention", "anoddpm_wgrad43_groups", "anoddpm_wgrad43_colsum_items", "anoddpm_pack_batch", "anoddpm_pack_job_blocks", "anoddpm_linear_small_backward_batch",
     "anoddpm_loss_forward", "anoddpm_loss_backward", "anoddpm_dropout", "anoddpm_roc_auc", "anoddpm_roc_workspace_bytes",
     "anoddpm_ssim", "anoddpm_ssim_workspace_bytes",
+    "anoddpm_median2d", "anoddpm_erode2d", "anoddpm_small_components", "anoddpm_small_components_workspace_bytes",
 ]
 
 _lib = None
@@ -374,6 +394,11 @@ def lib():
     L.anoddpm_ssim.argtypes = [POINTER(SsimArgs), c_void_p]
     L.anoddpm_ssim_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
     L.anoddpm_ssim_workspace_bytes.restype = c_int64
+    L.anoddpm_median2d.argtypes = [POINTER(MedianArgs), c_void_p]
+    L.anoddpm_erode2d.argtypes = [POINTER(ErodeArgs), c_void_p]
+    L.anoddpm_small_components.argtypes = [POINTER(ComponentsArgs), c_void_p]
+    L.anoddpm_small_components_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.anoddpm_small_components_workspace_bytes.restype = c_int64
     L.anoddpm_vlb_terms.argtypes = [POINTER(VlbArgs), c_void_p]
     L.anoddpm_dropout.argtypes = [POINTER(DropoutArgs), c_void_p]
     L.anoddpm_loss_forward.argtypes = [POINTER(LossArgs), c_void_p]

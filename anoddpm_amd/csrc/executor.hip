@@ -93,7 +93,7 @@ extern "C" int anoddpm_ablate_build(void)
 #endif
 }
 
-extern "C" int anoddpm_abi_version(void) { return 27; }
+extern "C" int anoddpm_abi_version(void) { return 28; }
 
 extern "C" const char *anoddpm_last_error(void) { return g_err; }
 
@@ -232,6 +232,9 @@ extern "C" int anoddpm_struct_size(int32_t which)
         case 33: return (int)sizeof(anoddpm_dropout_args);
         case 34: return (int)sizeof(anoddpm_roc_args);
         case 35: return (int)sizeof(anoddpm_ssim_args);
+        case 36: return (int)sizeof(anoddpm_median_args);
+        case 37: return (int)sizeof(anoddpm_erode_args);
+        case 38: return (int)sizeof(anoddpm_components_args);
         default: return -1;
     }
 }

@@ -452,6 +452,11 @@ class _FusedLoss(torch.autograd.Function):
 
 
 class GaussianDiffusionModel:
+    # opt-in post-processing of the detection records (metrics.PostProcess, and an optional 0 / 1 region-of-interest tensor shaped
+    # like one image or like x_0): see _attach_postprocessed.  Plain attributes: pickled and deep-copied with the instance.
+    postprocess = None
+    postprocess_roi = None
+
     def __init__(self, img_size, betas, img_channels=1, loss_type="l2", loss_weight='none', noise="gauss"):
         super().__init__()
         if noise == "gauss":
@@ -692,7 +697,8 @@ class GaussianDiffusionModel:
         self.__dict__.pop("_chains", None)
 
     def __getstate__(self):
-        """Pickle / deepcopy without the device-side caches: kept chains hold CUDAGraph objects, `_dev` holds device tensors."""
+        """Pickle / deepcopy without the device-side caches: kept chains hold CUDAGraph objects, `_dev` holds device tensors.
+        `postprocess` / `postprocess_roi` travel like every other plain attribute (they are in `__dict__` once assigned)."""
         d = dict(self.__dict__)
         d.pop("_chains", None)
         d["_dev"] = {}
@@ -1020,6 +1026,27 @@ class GaussianDiffusionModel:
         for j, rec in enumerate(records):
             rec["ssim"] = val[j]
 
+    def _attach_postprocessed(self, records, sqerrs, mask, x_0):
+        """Opt-in (`self.postprocess`, a metrics.PostProcess): the squared-error maps of every setting of a sweep after the median
+        filter inside the eroded region of interest (`self.postprocess_roi`, else `x_0 > postprocess.roi_level`, else the whole
+        image) -- ONE erosion launch, ONE median launch over all settings' maps -- as `sqerr_pp`, and with a mask ONE ROC launch on
+        them: `auc_pp`, `ap_pp`, `best_dice_pp` (fp64 device scalars, NaN as `auc` / `ap` / `best_dice`) and `best_threshold_pp`
+        (None without a mask).  Without `self.postprocess` the records keep exactly their keys.  Never synchronises."""
+        pp = self.postprocess
+        if pp is None or not records:
+            return
+        from . import metrics
+        filtered = metrics.postprocess_maps(torch.stack(sqerrs), pp, real=x_0, roi=self.postprocess_roi)     # [R, B, C, H, W]
+        for j, rec in enumerate(records):
+            rec["sqerr_pp"] = filtered[j]
+            rec["auc_pp"] = rec["ap_pp"] = rec["best_dice_pp"] = rec["best_threshold_pp"] = None
+        if mask is None:
+            return
+        o = metrics._roc_launch(mask, filtered.reshape(len(records), -1), batched=True, curve=False, pr=True)
+        auc, ap, best = (metrics._nan_where_status(o[k], o["status"]) for k in ("auc", "ap", "best_dice"))
+        for j, rec in enumerate(records):
+            rec["auc_pp"], rec["ap_pp"], rec["best_dice_pp"], rec["best_threshold_pp"] = auc[j], ap[j], best[j], o["best_threshold"][j]
+
     def detection_A(self, model, x_0, args, file, mask, total_avg=2):
         """GaussianDiffusion.py:480-529: simplex frequencies 2^7..2^1 x t_distance 50..0.6T step 50, `total_avg` chains each -- all
         of them one batched reverse loop (`_run_chains`).  Returns None as upstream; the per-setting results upstream only plots
@@ -1041,6 +1068,7 @@ class GaussianDiffusionModel:
             sqerrs.append(maps["sqerr"])
         self._attach_auc(self.last_detection, sqerrs, mask)
         self._attach_ssim(self.last_detection, x_0)
+        self._attach_postprocessed(self.last_detection, sqerrs, mask, x_0)
 
     def detection_B(self, model, x_0, args, file, mask, denoise_fn="gauss", total_avg=5):
         """GaussianDiffusion.py:531-594: t_distance 50..end step 50 with gaussian or 6-octave simplex forward noise,
@@ -1069,4 +1097,5 @@ class GaussianDiffusionModel:
             dice_coeff.append(None)                                 # evaluation.heatmap() returns None (evaluation.py:12-22)
         self._attach_auc(self.last_detection, sqerrs, mask)
         self._attach_ssim(self.last_detection, x_0)
+        self._attach_postprocessed(self.last_detection, sqerrs, mask, x_0)
         return dice_coeff

@@ -32,6 +32,14 @@ ties to the highest threshold -- with that threshold and its `tp` / `fp`, both w
 point of the curve as integer counts, `PR_curve` on device tensors sklearn's `(precision, recall, thresholds)` triple bit for bit.
 A segment without positives has AP = NaN and best Dice = NaN (sklearn: AP 0.0 after a warning); one without negatives has AP = 1.0.
 
+Post-processing (the reference has none: it scores the raw squared error).  Published brain-MRI anomaly-segmentation pipelines
+median-filter the residual, restrict it to an eroded brain mask and drop tiny components from the binary prediction before they
+report AP and Dice.  `median_filter` (scipy.ndimage.median_filter, windows 3 / 5 / 7, reflect border), `erode_mask`
+(scipy.ndimage.binary_erosion, cross, 1 ... 8 iterations) and `remove_small_components` (scipy.ndimage.label + bincount) do that
+on the device (csrc/postproc.hip), batched over all maps of a sweep, bit for bit what scipy returns and without a host
+synchronisation.  `PostProcess` holds the settings; `anomaly_metrics(..., postprocess=pp)` and the detection records add `_pp`
+results beside the raw ones.  Everything is opt-in: without it nothing changes.
+
 `anomaly_metrics` is the native entry: everything the metric loop needs from one launch and one 96-byte D2H copy (plus the AUC launch).
 The individual functions accept the reference's arguments; they use the fused pass when handed device tensors of
 the shapes the reference passes and raise `AnoddpmError` otherwise (no CPU path)."""
@@ -40,9 +48,10 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import AnomalyArgs, RocArgs, SsimArgs, check, current_stream, lib
+from ._lib import AnomalyArgs, ComponentsArgs, ErodeArgs, MedianArgs, RocArgs, SsimArgs, check, current_stream, lib
 
-__all__ = ["anomaly_maps", "anomaly_metrics", "roc_auc", "roc_points", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
+__all__ = ["anomaly_maps", "anomaly_metrics", "roc_auc", "roc_points", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "median_filter", "erode_mask",
+           "remove_small_components", "PostProcess", "postprocess_maps", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
 
 NC = _lib.ANOMALY_NCOUNTS
@@ -333,8 +342,199 @@ def ssim(real, recon, batched=None, data_range=2.0, win_size=7, gaussian_weights
         check(lib().anoddpm_ssim(ctypes.byref(a), current_stream()), "ssim")
     return (out, smap) if full else out
 
+# ---------------------------------------------------------------------------------- post-processing on the device
+def _planes(x, batched, what):
+    """Shape bookkeeping of [S][C...][H][W]: (S, C, H, W); all dimensions between the batch axis and the plane are channels."""
+    lead = 1 if batched else 0
+    if x.dim() - lead < 2:
+        raise ValueError(f"{what}: a segment is [..., H, W], got shape {tuple(x.shape)}" + (" as a batch" if batched else ""))
+    S = x.shape[0] if batched else 1
+    C = 1
+    for d in x.shape[lead:-2]:
+        C *= d
+    H, W = x.shape[-2], x.shape[-1]
+    if S < 1 or C < 1 or H < 1 or W < 1:
+        raise ValueError(f"{what}: empty input {tuple(x.shape)}")
+    return S, C, H, W
 
-def anomaly_metrics(real, recon, mask, threshold=0.5):
+
+def _plane_rows(x, S, C, H, W, name):
+    """x as S * C planes of H * W contiguous fp32: (tensor that owns the memory, plane stride in elements)."""
+    t, n, stride = _segments(x, S, name)
+    if C > 1 and stride != n:
+        t, stride = t.contiguous(), n
+    return t, (H * W if C > 1 else stride)
+
+
+def median_filter(score, size=5, roi=None, batched=None, return_status=False):
+    """`scipy.ndimage.median_filter(plane, size=size)` (reflect border) of every H x W plane of score: [S, ..., H, W] (`batched`;
+    the default is `roc_auc`'s: three or more dimensions are a batch, a 2-D tensor is one map), every dimension before the last
+    two a stack of planes.  size 3, 5 or 7, at most min(H, W).  `roi`: a 0 / 1 tensor shaped like one plane (shared by all), one
+    segment or score; the result is +0.0 where it is 0 (the filter itself sees the unmasked map).  Returns a device tensor
+    shaped like score, bit for bit scipy's, without a host synchronisation.  Scores must be finite and >= 0 as for `roc_auc`: a
+    plane that is not gets a non-zero status word (`return_status=True` also returns them, int32, shaped like score without its
+    last two dimensions) and an unspecified result."""
+    if not isinstance(score, torch.Tensor):
+        raise TypeError("median_filter: score must be a device tensor")
+    if size not in _lib.MEDIAN_SIZES:
+        raise ValueError(f"median_filter: size must be one of {_lib.MEDIAN_SIZES}, got {size!r}")
+    S, C, H, W = _planes(score, _is_batched(score, batched), "median_filter")
+    if min(H, W) < size:
+        raise ValueError(f"median_filter: window of {size} exceeds the {H} x {W} plane")
+    sc, s_stride = _plane_rows(score, S, C, H, W, "median_filter(score)")
+    dev = sc.device
+    a = MedianArgs()
+    if roi is not None:
+        if not isinstance(roi, torch.Tensor):
+            raise TypeError("median_filter: roi must be a device tensor")
+        if roi.numel() == H * W:
+            a.roi_stride = 0
+        elif roi.numel() == C * H * W:
+            roi = roi.reshape(1, C, H, W).expand(S, C, H, W)
+            a.roi_stride = H * W
+        elif roi.numel() == S * C * H * W:
+            a.roi_stride = H * W
+        else:
+            raise ValueError(f"median_filter: roi {tuple(roi.shape)} is neither a plane, a segment nor the shape of score {tuple(score.shape)}")
+        rt = _f32c(roi, "median_filter(roi)")
+        if rt.device != dev:
+            raise ValueError("median_filter: roi and score are on different devices")
+        a.roi = rt.data_ptr()
+    out = torch.empty(tuple(score.shape), dtype=torch.float32, device=dev)
+    status = torch.empty(tuple(score.shape[:-2]), dtype=torch.int32, device=dev)
+    a.src, a.dst, a.status, a.src_stride = sc.data_ptr(), out.data_ptr(), status.data_ptr(), s_stride
+    a.S, a.H, a.W, a.k = S * C, H, W, int(size)
+    with torch.cuda.device(dev):
+        check(lib().anoddpm_median2d(ctypes.byref(a), current_stream()), "median2d")
+    return (out, status) if return_status else out
+
+
+def erode_mask(x, iterations=3, level=0.0):
+    """`scipy.ndimage.binary_erosion(plane > level, iterations=iterations)` (the 4-neighbour cross, zero outside the image) of
+    every H x W plane of x ([..., H, W]); 1 ... 8 iterations.  Returns an fp32 0 / 1 device tensor shaped like x, no host
+    synchronisation.  With the default level a 0 / 1 mask is eroded; with `level` an image is thresholded and eroded at once."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("erode_mask: x must be a device tensor")
+    if int(iterations) != iterations or not 1 <= iterations <= _lib.ERODE_MAX:
+        raise ValueError(f"erode_mask: iterations must be in 1 ... {_lib.ERODE_MAX}, got {iterations!r}")
+    S, C, H, W = _planes(x, False, "erode_mask")
+    xt = _f32c(x, "erode_mask(x)")
+    out = torch.empty(tuple(x.shape), dtype=torch.float32, device=xt.device)
+    a = ErodeArgs()
+    a.src, a.dst, a.src_stride = xt.data_ptr(), out.data_ptr(), H * W
+    a.S, a.H, a.W, a.n, a.level = C, H, W, int(iterations), float(level)
+    with torch.cuda.device(xt.device):
+        check(lib().anoddpm_erode2d(ctypes.byref(a), current_stream()), "erode2d")
+    return out
+
+
+def _small_components(x, level, min_size, connectivity):
+    """One `anoddpm_small_components` run on the planes of x > level: (fp32 0 / 1 map shaped like x, int64 counts [..., 2])."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("remove_small_components: pred must be a device tensor")
+    if int(min_size) != min_size or min_size < 0:
+        raise ValueError(f"remove_small_components: min_size must be an integer >= 0, got {min_size!r}")
+    if connectivity not in (1, 2):
+        raise ValueError(f"remove_small_components: connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got {connectivity!r}")
+    S, C, H, W = _planes(x, False, "remove_small_components")
+    xt = _f32c(x, "remove_small_components(pred)")
+    dev = xt.device
+    nbytes = lib().anoddpm_small_components_workspace_bytes(C, H, W)
+    if nbytes < 0:
+        raise ValueError(f"remove_small_components: {tuple(x.shape)} has 2^31 pixels or more")
+    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    out = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)
+    counts = torch.empty(tuple(x.shape[:-2]) + (2,), dtype=torch.int64, device=dev)
+    a = ComponentsArgs()
+    a.src, a.dst, a.counts, a.workspace, a.workspace_bytes = xt.data_ptr(), out.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes
+    a.src_stride, a.S, a.H, a.W = H * W, C, H, W
+    a.min_size, a.connectivity, a.level = int(min_size), int(connectivity), float(level)
+    with torch.cuda.device(dev):
+        check(lib().anoddpm_small_components(ctypes.byref(a), current_stream()), "small_components")
+    return out, counts
+
+
+def remove_small_components(pred, min_size=7, connectivity=1, return_counts=False):
+    """The binary prediction `pred` ([..., H, W], fp32 0 / 1) without its connected components of fewer than `min_size` pixels:
+    `lab, _ = scipy.ndimage.label(plane); keep = numpy.bincount(lab.ravel()) >= min_size; keep[0] = False; keep[lab]` per plane.
+    connectivity 1: 4 neighbours (label's default), 2: 8 neighbours.  Returns an fp32 0 / 1 device tensor shaped like pred,
+    with `return_counts=True` also int64 `[..., 2]`: components found and components kept per plane.  No host synchronisation;
+    the same bits every run."""
+    out, counts = _small_components(pred, 0.0, min_size, connectivity)
+    return (out, counts) if return_counts else out
+
+
+class PostProcess:
+    """Settings of the post-processing between the squared error and its scores; immutable.  `median`: window of the median
+    filter (3, 5, 7; None: off).  `erode`: erosions of the region of interest (0 ... 8; 0: used as it is).  `roi_level`: when not
+    None the region of interest is `real > roi_level` (the images live in [-1, 1] with a -1 background) unless the caller hands
+    one in.  `min_size` / `connectivity`: components of the thresholded map below that many pixels are dropped (0: off).  The
+    defaults are the values common in published pipelines."""
+    __slots__ = ("median", "erode", "roi_level", "min_size", "connectivity")
+
+    def __init__(self, median=5, erode=3, roi_level=None, min_size=7, connectivity=1):
+        if median is not None and median not in _lib.MEDIAN_SIZES:
+            raise ValueError(f"PostProcess: median must be None or one of {_lib.MEDIAN_SIZES}, got {median!r}")
+        if isinstance(erode, bool) or int(erode) != erode or not 0 <= erode <= _lib.ERODE_MAX:
+            raise ValueError(f"PostProcess: erode must be in 0 ... {_lib.ERODE_MAX}, got {erode!r}")
+        if isinstance(min_size, bool) or int(min_size) != min_size or min_size < 0:
+            raise ValueError(f"PostProcess: min_size must be an integer >= 0, got {min_size!r}")
+        if connectivity not in (1, 2):
+            raise ValueError(f"PostProcess: connectivity must be 1 or 2, got {connectivity!r}")
+        for k, v in (("median", median), ("erode", int(erode)), ("roi_level", None if roi_level is None else float(roi_level)),
+                     ("min_size", int(min_size)), ("connectivity", int(connectivity))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("PostProcess is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("PostProcess is immutable")
+
+    def _key(self):
+        return tuple(getattr(self, k) for k in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, PostProcess) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "PostProcess(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+    def __reduce__(self):
+        return PostProcess, self._key()
+
+
+def postprocess_maps(sqerr, pp, real=None, roi=None):
+    """The squared-error maps `sqerr` ([S, ..., H, W]; batching as `median_filter`) after `pp`'s median filter inside the region
+    of interest.  The region is `roi` (a 0 / 1 tensor) when given, else `real > pp.roi_level` when `pp.roi_level` is set, else
+    everything; it has the shape of one plane (shared by all maps), one segment or sqerr, and is eroded `pp.erode` times in ONE
+    launch before the ONE median launch applies it.  Returns a device tensor shaped like sqerr, no host synchronisation.  With
+    `pp.median` None the region is applied by an elementwise product."""
+    if not isinstance(pp, PostProcess):
+        raise TypeError("postprocess_maps: pp must be a PostProcess")
+    level = 0.0
+    if roi is None and pp.roi_level is not None:
+        if real is None:
+            raise ValueError("postprocess_maps: PostProcess.roi_level needs the real image")
+        roi, level = real, pp.roi_level
+    if roi is not None:
+        roi = erode_mask(roi, pp.erode, level) if pp.erode else (_f32c(roi, "postprocess_maps(roi)") > level).float()
+    if pp.median is not None:
+        return median_filter(sqerr, pp.median, roi=roi)
+    out = _f32c(sqerr, "postprocess_maps(sqerr)")
+    if roi is None:
+        return out.clone()
+    S, C, H, W = _planes(out, _is_batched(out, None), "postprocess_maps")
+    if roi.numel() not in (H * W, C * H * W, S * C * H * W):
+        raise ValueError(f"postprocess_maps: roi {tuple(roi.shape)} does not match sqerr {tuple(sqerr.shape)}")
+    shape = (1, 1, H, W) if roi.numel() == H * W else ((1, C, H, W) if roi.numel() == C * H * W else (S, C, H, W))
+    return (out.reshape(S, C, H, W) * roi.reshape(shape)).reshape(out.shape)
+
+
+def anomaly_metrics(real, recon, mask, threshold=0.5, postprocess=None, roi=None):
     """dice / IoU / precision / recall / FPR / mse / PSNR of detection.py:229-250 from one launch, the AUC of
     detection.py:230-231 (the whole batch flattened into one curve, evaluation.py:81) from a second one -- which also gives `AP`
     (average precision), `best_dice` and `best_threshold` (the largest Dice over all thresholds and the highest threshold that
@@ -342,7 +542,13 @@ def anomaly_metrics(real, recon, mask, threshold=0.5):
     detection.py:241-246 (mean over the batch of the per-image SSIM of `real` against the `mean` map, i.e. the reconstruction
     averaged over `navg`) from a third.  Returns a dict of Python floats plus the maps (device tensors).  `AUC` is NaN when a
     class is empty or when `AUC_status` (the status word of the ROC kernel) is non-zero; without a mask there is no AUC (NaN,
-    status 0).  `SSIM` is NaN when the inputs are not `[B, C, H, W]` or are smaller than the 7 x 7 window."""
+    status 0).  `SSIM` is NaN when the inputs are not `[B, C, H, W]` or are smaller than the 7 x 7 window.
+
+    `postprocess` (a `PostProcess`; `roi`: its region of interest, see `postprocess_maps`) ADDS, and changes nothing else:
+    `AUC_pp`, `AP_pp`, `best_dice_pp`, `best_threshold_pp`, `AUC_pp_status` -- the same launch on the filtered map
+    `maps["sqerr_pp"]` -- and `dice_pp`, `precision_pp`, `recall_pp`: the filtered map cut at `threshold`, without its
+    components below `postprocess.min_size` pixels (`maps["pred_pp"]`), counted by the same pass as `dice` / `precision` /
+    `recall`.  The inputs must be `[..., H, W]` images then."""
     maps, counts = anomaly_maps(real, recon, mask, threshold)
     roc = _roc_launch(mask, maps["sqerr"], batched=False, curve=False, pr=True) if mask is not None else None
     ss = ssim(real, maps["mean"]) if real.dim() == 4 and min(real.shape[-2:]) >= 7 and real.numel() > 0 else None
@@ -360,7 +566,28 @@ def anomaly_metrics(real, recon, mask, threshold=0.5):
         r["best_threshold"] = float("nan")                           # no positive: no threshold is better than another
     r["SSIM"] = float(ss.mean().cpu()) if ss is not None else float("nan")
     r["maps"] = maps
+    if postprocess is not None:
+        _add_postprocessed(r, real, mask, threshold, postprocess, roi)
     return r
+
+
+def _add_postprocessed(r, real, mask, threshold, pp, roi):
+    """The `_pp` keys of `anomaly_metrics`."""
+    maps = r["maps"]
+    sq = postprocess_maps(maps["sqerr"], pp, real=real, roi=roi)
+    pred, _ = _small_components(sq, float(threshold), pp.min_size, pp.connectivity)
+    roc = _roc_launch(mask, sq, batched=False, curve=False, pr=True) if mask is not None else None
+    _, counts = anomaly_maps(torch.zeros_like(pred), pred, mask, threshold=0.5, want=())    # (pred - 0)^2 > 0.5 is pred itself
+    ratios = _ratios(counts.cpu())
+    for key in ("dice", "precision", "recall"):
+        r[key + "_pp"] = float(ratios[key])
+    st = int(roc["status"].cpu()[0]) if roc is not None else 0
+    r["AUC_pp_status"] = st
+    for key, src in (("AUC_pp", "auc"), ("AP_pp", "ap"), ("best_dice_pp", "best_dice"), ("best_threshold_pp", "best_threshold")):
+        r[key] = float(roc[src].cpu()[0]) if roc is not None and st == 0 else float("nan")
+    if r["best_dice_pp"] != r["best_dice_pp"]:
+        r["best_threshold_pp"] = float("nan")
+    maps["sqerr_pp"], maps["pred_pp"] = sq, pred
 
 
 # ---------------------------------------------------------------------------------- evaluation.py surface

@@ -624,6 +624,66 @@ typedef struct anoddpm_ssim_args {
 int anoddpm_ssim(const anoddpm_ssim_args *a, void *stream);
 int64_t anoddpm_ssim_workspace_bytes(int32_t S, int32_t C, int32_t H, int32_t W);   /* HOST function; -1 for a dimension < 1 or S*C*tiles >= 2^31 */
 
+/* ------------------------------------------------------------------ post-processing of anomaly maps before they are scored
+ * The three steps published brain-MRI anomaly-segmentation pipelines apply between the squared error and AP / Dice (the
+ * reference has no counterpart: it scores the raw map).  All three select or count, so each output equals scipy's bit for bit.
+ * S planes of H x W fp32, plane p at src + p * src_stride (src_stride >= H*W); outputs are contiguous [S][H][W].
+ *
+ * anoddpm_median2d replaces scipy.ndimage.median_filter(plane, size=k) (default mode="reflect": d c b a | a b c d | d c b a),
+ *   k in {3, 5, 7}, min(H, W) >= k: dst = the middle one of the k*k values of the window, selected, never averaged.
+ *   Precondition as anoddpm_roc_auc: values finite and >= 0 (-0.0 is reported as +0.0); a plane that breaks it sets bits of
+ *   status[p] (ANODDPM_ROC_NAN / _INF / _NEGATIVE) and its output is unspecified; no other plane is touched.
+ *   roi     optional fp32 0/1 planes at roi + p * roi_stride (roi_stride 0 = one ROI for every plane): dst is +0.0 where the
+ *           ROI is 0 (the filter itself sees the unmasked plane).  A value other than 0 / 1 sets ANODDPM_ROC_BAD_MASK.
+ *   One launch (after an asynchronous clear of status): a workgroup stages a 16 x 32 tile and its k/2 halo in LDS; the grid is
+ *   tiles x planes.
+ *
+ * anoddpm_erode2d replaces scipy.ndimage.binary_erosion(plane > level, iterations=n) with scipy's defaults (the 4-neighbour
+ *   cross, border_value=0), 1 <= n <= 8: n passes of the cross are one pass of the L1 ball of radius n with everything outside
+ *   the image counting as 0.  dst is fp32 0 / 1.  NaN is not above any level.  One launch, n-pixel LDS halo.
+ *
+ * anoddpm_small_components replaces  lab, m = scipy.ndimage.label(plane > level, structure);  sizes = numpy.bincount(lab.ravel());
+ *   plane * (sizes >= min_size)[lab]  (with label 0 cleared): dst is fp32 0 / 1, the foreground without its connected
+ *   components of fewer than min_size pixels.  connectivity 1: 4 neighbours (label's default structure), 2: 8 neighbours.
+ *   counts[p] = {components found, components kept}.  Union-find on 32-bit labels in global memory: clear, link (atomic minimum
+ *   on roots), flatten, sizes (atomic add at the root), filter -- five launches, and launch boundaries are the only ordering
+ *   between workgroups.  The outputs are a set and two integers: independent of execution order, same bits every run.
+ *   workspace  [dev] anoddpm_small_components_workspace_bytes(S, H, W) bytes = 8 per pixel (label and size words)
+ * No allocation and no host synchronisation in any of them. */
+typedef struct anoddpm_median_args {
+    const float *src;               /* [dev] */
+    const float *roi;               /* [dev] or NULL */
+    float *dst;                     /* [dev] [S][H][W] */
+    int32_t *status;                /* [dev] [S] */
+    int64_t src_stride, roi_stride;
+    int32_t S, H, W, k;
+} anoddpm_median_args;
+
+typedef struct anoddpm_erode_args {
+    const float *src;               /* [dev] */
+    float *dst;                     /* [dev] [S][H][W] */
+    int64_t src_stride;
+    int32_t S, H, W, n;
+    float level;
+} anoddpm_erode_args;
+
+typedef struct anoddpm_components_args {
+    const float *src;               /* [dev] */
+    float *dst;                     /* [dev] [S][H][W] */
+    int64_t *counts;                /* [dev] [S][2] */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    int64_t src_stride;
+    int32_t S, H, W;
+    int32_t min_size, connectivity;
+    float level;
+} anoddpm_components_args;
+
+int anoddpm_median2d(const anoddpm_median_args *a, void *stream);
+int anoddpm_erode2d(const anoddpm_erode_args *a, void *stream);
+int anoddpm_small_components(const anoddpm_components_args *a, void *stream);
+int64_t anoddpm_small_components_workspace_bytes(int32_t S, int32_t H, int32_t W);  /* HOST function; -1 for an extent < 1 or S*H*W >= 2^31 */
+
 /* Variational-bound terms of one reverse step (GaussianDiffusion.py:384-397 calc_vlb_xt, and the two MSE curves of
  * calc_total_vlb :445-478): per sample b
  *   out[0*B + b] = mean_flat( t==0 ? -discretised_gaussian_log_likelihood(x_0; mean, 0.5*logvar)
