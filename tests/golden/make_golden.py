@@ -8,7 +8,8 @@ recipe from SURVEY.md 8c).  Outputs are DATA (inputs + expected outputs), never 
     simplex_kat.npz      _init tables, noise3 point KATs (bit patterns), octave fields, C4 crops
     diffusion_kat.npz    schedule tables (linear/cosine), sample_q / p_mean_variance / sample_p
     unet_<name>.npz      UNetModel.forward outputs (+ per-block activation probes); unet_c2_256_b128_batch4.npz: BASELINE
-                         config 2 at its benchmarked batch 4 with four timesteps, output only
+                         config 2 at its benchmarked batch 4 with four timesteps, output only; unet_structured_<name>.npz:
+                         blank slice / phantom / noised phantom / uniform inputs (tests/gn_cases.py), output only
     metrics_kat.npz      evaluation.py metrics + the mean / mse / threshold images of detection_A/B
     simplex2_kat.npz     2-D noise2 point KATs (bit patterns), a coordinate grid, octave fields
     vlb_kat.npz          calc_vlb_xt (KL and decoder-NLL branches) and the MSE curves of calc_total_vlb
@@ -195,7 +196,8 @@ UNET_CASES = {
 }
 
 
-def run_unet_case(name, kw, batch, ts, probes=True):
+def run_unet_case(name, kw, batch, ts, probes=True, x=None):
+    """x: an injected input batch (default: uniform in [-1, 1], seeded by the case name)."""
     kw = dict(kw)
     model = ref_unet.UNetModel(**kw)
     shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
@@ -208,7 +210,9 @@ def run_unet_case(name, kw, batch, ts, probes=True):
     model.load_state_dict(sd)
     model.eval()
     g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
-    x = torch.rand(batch, kw.get("in_channels", 1), kw["img_size"], kw["img_size"], generator=g) * 2 - 1
+    if x is None:
+        x = torch.rand(batch, kw.get("in_channels", 1), kw["img_size"], kw["img_size"], generator=g) * 2 - 1
+    assert x.shape[0] == batch
     t = torch.tensor(ts)
     rec = {}
     hooks = []
@@ -268,6 +272,27 @@ def gen_unet_c2_batch4():
     out.pop("keys"); out.pop("key_shapes")
     np.savez_compressed(os.path.join(HERE, "unet_c2_256_b128_batch4.npz"), **out)
     print("unet_c2_256_b128_batch4.npz |y| mean", float(np.abs(out["y"]).mean()))
+
+
+UNET_STRUCTURED = {
+    # 1 channel per group behind the stem: the blank slice reaches r = |mean| / sqrt(var + eps) = 14 in a GroupNorm
+    "i64_b32_hc32": dict(img_size=64, base_channels=32, n_head_channels=32, attention_resolutions="16,8"),
+    # 4 channels per group, wide enough for the F(4x4,3x3) layers
+    "i64_b128_h2": dict(img_size=64, base_channels=128, n_heads=2, attention_resolutions="16,8"),
+}
+
+
+def gen_unet_structured():
+    """Structured inputs instead of uniform noise (tests/gn_cases.py:structured_batch): batch 4 = [blank -1 slice, Gaussian-blob
+    phantom on -1, the phantom noised as at t = 250, uniform] at t = [0, 100, 250, 999].  Output only."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import gn_cases
+    for name, kw in UNET_STRUCTURED.items():
+        x, t = gn_cases.structured_batch(kw["img_size"])
+        out = run_unet_case("structured_" + name, kw, 4, t.tolist(), probes=False, x=x)
+        out.pop("keys"); out.pop("key_shapes")
+        np.savez_compressed(os.path.join(HERE, f"unet_structured_{name}.npz"), **out)
+        print(f"unet_structured_{name}.npz |y| mean per image", np.abs(out["y"]).mean(axis=(1, 2, 3)))
 
 
 def gen_unet_c5():
@@ -788,7 +813,7 @@ def gen_boundary_names():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["simplex", "diffusion", "unet", "metrics", "vlb", "vlb_total", "loss", "simplex2", "unet_c5", "unet_c2_batch4", "training",
+    which = sys.argv[1:] or ["simplex", "diffusion", "unet", "metrics", "vlb", "vlb_total", "loss", "simplex2", "unet_c5", "unet_c2_batch4", "unet_structured", "training",
                              "detection", "loader", "detection_loops", "simplex_crosscheck", "boundary_names"]
     torch.set_num_threads(8)
     if "simplex" in which:
@@ -813,6 +838,8 @@ if __name__ == "__main__":
         gen_unet_c5()
     if "unet_c2_batch4" in which:
         gen_unet_c2_batch4()
+    if "unet_structured" in which:
+        gen_unet_structured()
     if "training" in which:
         gen_training()
     if any(w.startswith("training:") for w in which):

@@ -82,16 +82,17 @@ def chan_stats(x, nslab):
     return stats
 
 
-def gn_finalize(stats, gamma, beta, P, want_mean_rstd=False):
-    """stats: list of 1-2 tensors [B][rows][c][2] -> scale, shift [B][Ctot] (+ mean, rstd [B][32])."""
+def gn_finalize(stats, gamma, beta, P, want_mean_rstd=False, fmts=(0, 0)):
+    """stats: list of 1-2 tensors [B][rows][c][2] -> scale, shift [B][Ctot] (+ mean, rstd [B][32]).
+    fmts[i] = 1: source i is one row of fp64 sums [B][c][2] (a split-K tail's tail_csum, the atomic stats_csum)."""
     B = stats[0].shape[0]
-    c0 = stats[0].shape[2]
-    c1 = stats[1].shape[2] if len(stats) > 1 else 0
+    c0 = stats[0].shape[1 if fmts[0] else 2]
+    c1 = stats[1].shape[1 if fmts[1] else 2] if len(stats) > 1 else 0
     scale = torch.empty(B, c0 + c1, device=stats[0].device)
     shift = torch.empty(B, c0 + c1, device=stats[0].device)
     st = GnFinalizeArgs()
-    st.stats0, st.rows0 = stats[0].data_ptr(), stats[0].shape[1]
-    st.stats1, st.rows1 = (stats[1].data_ptr(), stats[1].shape[1]) if c1 else (None, 0)
+    st.stats0, st.rows0, st.fmt0 = stats[0].data_ptr(), (1 if fmts[0] else stats[0].shape[1]), fmts[0]
+    st.stats1, st.rows1, st.fmt1 = (stats[1].data_ptr(), (1 if fmts[1] else stats[1].shape[1]), fmts[1]) if c1 else (None, 0, 0)
     st.gamma, st.beta, st.scale, st.shift = gamma.data_ptr(), beta.data_ptr(), scale.data_ptr(), shift.data_ptr()
     st.c0, st.c1, st.P, st.B, st.groups, st.eps = c0, c1, P, B, 32, 1e-5
     mean = rstd = None

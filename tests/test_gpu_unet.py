@@ -268,3 +268,46 @@ def test_input_view_at_an_odd_storage_offset():
     m.train()
     ya, yb = m(xo, t), m(x, t)
     assert ya.requires_grad and torch.equal(ya.detach(), yb.detach())
+
+
+STRUCTURED = {
+    "i64_b32_hc32": CASES["i64_b32_hc32"],
+    "i64_b128_h2": dict(img_size=64, base_channels=128, n_heads=2, attention_resolutions="16,8"),
+}
+
+
+@pytest.mark.parametrize("name", list(STRUCTURED))
+def test_structured_inputs_match_reference_output(name):
+    """Inputs that are not centred noise (tests/golden/make_golden.py:gen_unet_structured, tests/gn_cases.py:structured_batch):
+    batch 4 = [blank -1 slice, Gaussian-blob phantom on -1, the phantom noised as at t = 250, uniform] at t = [0, 100, 250, 999],
+    against the reference model's output.  The blank slice drives the first GroupNorm behind the stem of the base-32 model
+    (1 channel per group) to |mean| / sqrt(var + eps) = 14, where the variance Q / n - mean^2 of the fused statistics has lost
+    two and a half digits (tests/test_gn_reference.py measures that envelope).
+
+    Statistics routes of the two plans (tools/plan_dump.py, batch 4 and batch 1): the stem's rows; contraction epilogue rows of
+    cfg 1, 5, 6 (base 32) and cfg 1, 2, 3, 5, 6 (base 128: F(4x4,3x3) at batch 4, F(2x2,3x3) split-K at batch 1); split-K tails
+    with rows, with folded fp64 sums and with the consumer GroupNorm attached, one of them read by gn_finalize as its fp64
+    source; the prologue fold of cfg 5 / 6 from rows; gn_finalize over one and two sources.  NOT reached by these plans: the
+    stand-alone fp64 gn_stats and the chan_stats pass (every producer has an epilogue), cfg 0 rows, the atomic fp64 sums with the
+    F(4x4,3x3) prologue fold (opt-in), cfg 7 (opt-in), mean / rstd outputs (training) -- tests/test_gpu_gn_conditioning.py runs
+    those as single launches."""
+    g = np.load(os.path.join(GOLDEN, f"unet_structured_{name}.npz"))
+    from UNet import UNetModel
+    from oracle import unet_oracle as uo
+    kw = STRUCTURED[name]
+    m = UNetModel(**kw)
+    m.load_state_dict(uo.fill_deterministic({k: tuple(v.shape) for k, v in m.state_dict().items()}))
+    m = m.to(DEV).eval()
+    x, t = torch.from_numpy(g["x"]).to(DEV), torch.from_numpy(g["t"]).to(DEV)
+    assert x.shape[0] == 4 and (x[0] == -1).all() and g["t"].tolist() == [0, 100, 250, 999]
+    with torch.no_grad():
+        y = m(x, t)
+        y1 = torch.cat([m(x[i:i + 1], t[i:i + 1]) for i in range(4)])
+    ref = torch.from_numpy(g["y"])
+    assert torch.isfinite(y).all()
+    errs = [((y[b].cpu() - ref[b]).abs().max() / ref[b].abs().max()).item() for b in range(4)]
+    one = [((y[b] - y1[b]).abs().max() / y1[b].abs().max()).item() for b in range(4)]
+    print(f"{name}: per-image error vs reference {['%.2e' % e for e in errs]}, batch 4 vs batch 1 {['%.2e' % e for e in one]}")
+    for b in range(4):                                                  # per image: the blank one may not hide behind another
+        assert errs[b] < 5e-5, f"image {b} (t = {int(g['t'][b])}): rel err {errs[b]:.3e}"
+        assert one[b] < 2e-5, f"image {b}: batch 4 vs batch 1 {one[b]:.3e}"

@@ -85,3 +85,24 @@ def test_zero_init_convention_not_used():
 def test_unsupported_size():
     with pytest.raises(ValueError):
         uo.layout(48, 32)
+
+
+STRUCTURED = {
+    "i64_b32_hc32": CASES["i64_b32_hc32"],
+    "i64_b128_h2": dict(img_size=64, base_channels=128, n_heads=2, attention_resolutions="16,8"),
+}
+
+
+@pytest.mark.parametrize("name", list(STRUCTURED))
+def test_structured_inputs_match_reference(name):
+    """The oracle on the structured-input fixtures (blank slice, phantom, noised phantom, uniform; tests/gn_cases.py), and the
+    fixture's input is what `structured_batch` builds."""
+    import gn_cases
+    kw = STRUCTURED[name]
+    g = np.load(os.path.join(GOLDEN, f"unet_structured_{name}.npz"))
+    x, t = gn_cases.structured_batch(kw["img_size"])
+    np.testing.assert_allclose(x.numpy(), g["x"], rtol=0, atol=1e-6)
+    assert t.tolist() == g["t"].tolist()
+    sd = uo.fill_deterministic(shapes_of(kw))
+    y = uo.forward(sd, torch.from_numpy(g["x"]), torch.from_numpy(g["t"]), **kw)
+    np.testing.assert_allclose(y.numpy(), g["y"], rtol=0, atol=2e-5)
