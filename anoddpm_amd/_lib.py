@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ANODDPM_LIB_TAG=<tag>: load lib/libanoddpm_hip_<tag>.so instead -- a second build of the same sources with other compiler flags
 # (ANODDPM_BUILD_TAG / ANODDPM_EXTRA_FLAGS of anoddpm_amd.build), for A/B measurements of one gpurun session.  Same ABI, same checks.
 SO_PATH = os.path.join(_HERE, "lib", "libanoddpm_hip%s.so" % ("_" + os.environ["ANODDPM_LIB_TAG"] if os.environ.get("ANODDPM_LIB_TAG") else ""))
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 OP_IGEMM, OP_GN_STATS, OP_SOFTMAX, OP_RESAMPLE, OP_LINEAR, OP_POSEMB, OP_STEM, OP_LAYOUT, OP_CHAN_STATS, OP_GN_FINALIZE, OP_HEAD = range(1, 12)
 (OP_WGRAD3, OP_WGRAD1, OP_GN_BWD, OP_PACK, OP_SOFTMAX_BWD, OP_TRANSPOSE, OP_LINEAR_BWD, OP_STEM_BWD, OP_HEAD_BWD,
@@ -278,6 +278,7 @@ class ComponentsArgs(Structure):
                 ("min_size", c_int32), ("connectivity", c_int32), ("level", c_float)]
 
 
+PHILOX_REVERSE, PHILOX_FORWARD, PHILOX_FILL = 0, 1, 2                                   # the `domain` word of the philox counter
 ANOMALY_NCOUNTS = 12
 ANOMALY_BLOCKS = 64
 ROC_NAN, ROC_INF, ROC_NEGATIVE, ROC_BAD_MASK, ROC_CURVE_TRUNCATED = 1, 2, 4, 8, 16      # bits of anoddpm_roc_args.status
@@ -309,6 +310,7 @@ SYMBOLS = [
     "anoddpm_loss_forward", "anoddpm_loss_backward", "anoddpm_dropout", "anoddpm_roc_auc", "anoddpm_roc_workspace_bytes",
     "anoddpm_ssim", "anoddpm_ssim_workspace_bytes",
     "anoddpm_median2d", "anoddpm_erode2d", "anoddpm_small_components", "anoddpm_small_components_workspace_bytes",
+    "anoddpm_philox_fill", "anoddpm_philox_bits_host", "anoddpm_p_sample_update_gauss", "anoddpm_q_sample_gauss",
 ]
 
 _lib = None
@@ -363,6 +365,12 @@ def lib():
                                    c_int32, c_int64, c_int32, c_void_p]
     L.anoddpm_p_sample_update.argtypes = [POINTER(PUpdateArgs), c_void_p]
     L.anoddpm_chain_advance.argtypes = [c_void_p, c_int32, c_void_p, c_void_p]
+    L.anoddpm_philox_fill.argtypes = [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                      c_void_p, ctypes.c_uint32, c_int32, c_void_p]
+    L.anoddpm_philox_bits_host.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int64, c_void_p]
+    L.anoddpm_p_sample_update_gauss.argtypes = [POINTER(PUpdateArgs), c_void_p, c_void_p, ctypes.c_uint32, c_void_p]
+    L.anoddpm_q_sample_gauss.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32,
+                                         c_void_p, c_void_p, ctypes.c_uint32, c_void_p]
     L.anoddpm_igemm.argtypes = [POINTER(IgemmArgs), c_void_p]
     L.anoddpm_gn_stats.argtypes = [POINTER(GnArgs), c_void_p]
     L.anoddpm_chan_stats.argtypes = [POINTER(ChanStatsArgs), c_void_p]

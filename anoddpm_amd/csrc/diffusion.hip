@@ -4,16 +4,126 @@
 // HBM-bound elementwise work: sample_q moves 12 B/pixel, the reverse update 16 B/pixel.
 // Compiled with -ffp-contract=off so every product and sum rounds exactly as the reference's
 // separate fp32 ATen kernels do (results are bit-identical to its CPU path).
+// Seeded Gaussian noise: the *_gauss forms generate their normals in registers from a counter-based stream instead
+// of reading a noise tensor (reverse update 12 B/pixel, no noise launch).
 #include "common.h"
 
 namespace {
 
+// ---------------------------------------------------------------- Philox4x32-10 (Random123) -> Box-Muller normals
+struct PhiloxWords {
+    uint32_t w[4];
+};
+
+__host__ __device__ __forceinline__ PhiloxWords philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return PhiloxWords{{c0, c1, c2, c3}};
+}
+
+// The key block of the C ABI as the kernels receive it (seed and stream ids are read from device memory at run time).
+struct PhiloxKey {
+    const uint64_t *seed;
+    const int32_t *streams;
+    uint32_t stream0, domain;
+};
+
+// What one sample's threads share: the key and the three counter words that do not depend on the element.
+struct PhiloxSample {
+    uint32_t k0, k1, stream, step, domain;
+};
+
+__device__ __forceinline__ PhiloxSample philox_sample(const PhiloxKey &key, int b, uint32_t step)
+{
+    const uint64_t seed = *key.seed;
+    PhiloxSample s;
+    s.k0 = (uint32_t)seed;
+    s.k1 = (uint32_t)(seed >> 32);
+    s.stream = key.streams ? (uint32_t)key.streams[b] : key.stream0 + (uint32_t)b;
+    s.step = step;
+    s.domain = key.domain;
+    return s;
+}
+
+__device__ __forceinline__ float philox_unit(uint32_t w)
+{
+    return ((float)(w >> 9) + 0.5f) * 1.1920928955078125e-07f;      // ((w >> 9) + 0.5) * 2^-23: exact, in (0, 1)
+}
+
+// The four normals of one quad.  The ONLY place normals are made: anoddpm_philox_fill and the fused kernels share it, which
+// (with -ffp-contract=off) is what makes fused == fill + unfused bit for bit.
+__device__ __forceinline__ void philox_normals(const PhiloxSample &s, uint32_t quad, float z[4])
+{
+    const PhiloxWords p = philox4x32_10(quad, s.stream, s.step, s.domain, s.k0, s.k1);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float r = sqrtf(-2.0f * logf(philox_unit(p.w[2 * h])));
+        float sn, cs;
+        sincospif(2.0f * philox_unit(p.w[2 * h + 1]), &sn, &cs);
+        z[2 * h] = r * cs;
+        z[2 * h + 1] = r * sn;
+    }
+}
+
+// python-style step of sample b (the update kernels' own normalisation): t < 0 means t + T; out of range -> 0 (those samples are
+// NaN in the update kernels)
+__device__ __forceinline__ uint32_t philox_step_of(long long ti, int T)
+{
+    if (T > 0) {
+        ti = ti < 0 ? ti + T : ti;
+        if (ti < 0 || ti >= T) ti = 0;
+    }
+    return (uint32_t)ti;
+}
+
 template <int VEC>
+__global__ __launch_bounds__(256) void philox_fill_kernel(uint32_t *__restrict__ out, int kind, int64_t n, PhiloxKey key,
+                                                          const int64_t *__restrict__ t, uint32_t step0, int T)
+{
+    const int b = blockIdx.y;
+    const PhiloxSample s = philox_sample(key, b, t ? philox_step_of(t[b], T) : step0);
+    out += (int64_t)b * n;
+    const int64_t nq = (n + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
+        uint32_t v[4];
+        if (kind == 0) {
+            const PhiloxWords p = philox4x32_10((uint32_t)q, s.stream, s.step, s.domain, s.k0, s.k1);
+#pragma unroll
+            for (int l = 0; l < 4; ++l) v[l] = p.w[l];
+        } else {
+            float z[4];
+            philox_normals(s, (uint32_t)q, z);
+#pragma unroll
+            for (int l = 0; l < 4; ++l) v[l] = __float_as_uint(z[l]);
+        }
+        if (VEC == 4) {
+            *reinterpret_cast<uint4 *>(out + 4 * q) = make_uint4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                if (4 * q + l < n) out[4 * q + l] = v[l];
+        }
+    }
+}
+
+// GAUSS: `noise` is not read; the normals come from `key` (one thread owns whole quads) and go to noise_out if that is given.
+template <int VEC, bool GAUSS>
 __global__ __launch_bounds__(256) void q_sample_kernel(float *__restrict__ out, const float *__restrict__ x,
                                                        const float *__restrict__ noise,
                                                        const int64_t *__restrict__ t,
                                                        const float *__restrict__ ca,
-                                                       const float *__restrict__ cb, int64_t n, int T)
+                                                       const float *__restrict__ cb, int64_t n, int T,
+                                                       float *__restrict__ noise_out, PhiloxKey key)
 {
     const int b = blockIdx.y;
     long long ti = t[b];
@@ -25,6 +135,34 @@ __global__ __launch_bounds__(256) void q_sample_kernel(float *__restrict__ out, 
     const float qnan = __builtin_nanf("");
     const float a = bad ? qnan : ca[ti], c = bad ? qnan : cb[ti];
     const int64_t base = (int64_t)b * n;
+    if (GAUSS) {
+        const PhiloxSample ps = philox_sample(key, b, (uint32_t)ti);
+        const int64_t nq = (n + 3) >> 2;
+        for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
+            float z[4];
+            philox_normals(ps, (uint32_t)q, z);
+            const int64_t i = base + 4 * q;
+            if (VEC == 4) {
+                const float4 xv = *reinterpret_cast<const float4 *>(x + i);
+                float4 o;
+                o.x = a * xv.x + c * z[0];
+                o.y = a * xv.y + c * z[1];
+                o.z = a * xv.z + c * z[2];
+                o.w = a * xv.w + c * z[3];
+                *reinterpret_cast<float4 *>(out + i) = o;
+                if (noise_out) *reinterpret_cast<float4 *>(noise_out + i) = make_float4(z[0], z[1], z[2], z[3]);
+            } else {
+#pragma unroll
+                for (int l = 0; l < 4; ++l) {
+                    if (4 * q + l < n) {
+                        out[i + l] = a * x[i + l] + c * z[l];
+                        if (noise_out) noise_out[i + l] = z[l];
+                    }
+                }
+            }
+        }
+        return;
+    }
     for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC; i < n; i += (int64_t)gridDim.x * 256 * VEC) {
         if (VEC == 4) {
             const float4 xv = *reinterpret_cast<const float4 *>(x + base + i);
@@ -55,8 +193,33 @@ __device__ __forceinline__ float reverse_one(float xt, float e, float nz, const 
     return mean + k.sigma * nz;
 }
 
-template <int VEC>
-__global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a)
+__device__ __forceinline__ void reverse_store4(const anoddpm_p_update_args &a, const StepCoef &k, int64_t i, const float4 nv)
+{
+    const float4 xv = *reinterpret_cast<const float4 *>(a.x_t + i);
+    const float4 ev = *reinterpret_cast<const float4 *>(a.eps + i);
+    float4 o, p0, mu;
+    o.x = reverse_one(xv.x, ev.x, nv.x, k, &p0.x, &mu.x);
+    o.y = reverse_one(xv.y, ev.y, nv.y, k, &p0.y, &mu.y);
+    o.z = reverse_one(xv.z, ev.z, nv.z, k, &p0.z, &mu.z);
+    o.w = reverse_one(xv.w, ev.w, nv.w, k, &p0.w, &mu.w);
+    *reinterpret_cast<float4 *>(a.x_prev + i) = o;
+    if (a.pred_x0) *reinterpret_cast<float4 *>(a.pred_x0 + i) = p0;
+    if (a.mean_out) *reinterpret_cast<float4 *>(a.mean_out + i) = mu;
+}
+
+__device__ __forceinline__ void reverse_store1(const anoddpm_p_update_args &a, const StepCoef &k, int64_t i, float nz)
+{
+    float p0, mu;
+    const float o = reverse_one(a.x_t[i], a.eps[i], nz, k, &p0, &mu);
+    a.x_prev[i] = o;
+    if (a.pred_x0) a.pred_x0[i] = p0;
+    if (a.mean_out) a.mean_out[i] = mu;
+}
+
+// GAUSS: a.noise is NULL; the step noise comes from `key` at (stream of sample b, step = normalised t[b]).  It is generated at
+// t == 0 too, where sigma is 0: mean + 0 * nz keeps the sign-of-zero behaviour of the unfused pair.
+template <int VEC, bool GAUSS>
+__global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a, PhiloxKey key)
 {
     const int b = blockIdx.y;
     long long ti = a.t[b];
@@ -71,27 +234,29 @@ __global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a)
     k.coef2 = a.c_coef2[ti];
     k.sigma = nonzero ? a.c_sigma[ti] : 0.0f;        // (t != 0).float() * exp(0.5*logvar)
     const int64_t base = (int64_t)b * a.n;
+    if (GAUSS) {
+        const PhiloxSample ps = philox_sample(key, b, (uint32_t)ti);
+        const int64_t nq = (a.n + 3) >> 2;
+        for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
+            float z[4];
+            philox_normals(ps, (uint32_t)q, z);
+            if (VEC == 4) {
+                reverse_store4(a, k, base + 4 * q, make_float4(z[0], z[1], z[2], z[3]));
+            } else {
+#pragma unroll
+                for (int l = 0; l < 4; ++l)
+                    if (4 * q + l < a.n) reverse_store1(a, k, base + 4 * q + l, z[l]);
+            }
+        }
+        return;
+    }
     for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC; i < a.n; i += (int64_t)gridDim.x * 256 * VEC) {
         if (VEC == 4) {
-            const float4 xv = *reinterpret_cast<const float4 *>(a.x_t + base + i);
-            const float4 ev = *reinterpret_cast<const float4 *>(a.eps + base + i);
             float4 nv = make_float4(0.f, 0.f, 0.f, 0.f);
             if (a.noise) nv = *reinterpret_cast<const float4 *>(a.noise + base + i);
-            float4 o, p0, mu;
-            o.x = reverse_one(xv.x, ev.x, nv.x, k, &p0.x, &mu.x);
-            o.y = reverse_one(xv.y, ev.y, nv.y, k, &p0.y, &mu.y);
-            o.z = reverse_one(xv.z, ev.z, nv.z, k, &p0.z, &mu.z);
-            o.w = reverse_one(xv.w, ev.w, nv.w, k, &p0.w, &mu.w);
-            *reinterpret_cast<float4 *>(a.x_prev + base + i) = o;
-            if (a.pred_x0) *reinterpret_cast<float4 *>(a.pred_x0 + base + i) = p0;
-            if (a.mean_out) *reinterpret_cast<float4 *>(a.mean_out + base + i) = mu;
+            reverse_store4(a, k, base + i, nv);
         } else {
-            float p0, mu;
-            const float nz = a.noise ? a.noise[base + i] : 0.0f;
-            const float o = reverse_one(a.x_t[base + i], a.eps[base + i], nz, k, &p0, &mu);
-            a.x_prev[base + i] = o;
-            if (a.pred_x0) a.pred_x0[base + i] = p0;
-            if (a.mean_out) a.mean_out[base + i] = mu;
+            reverse_store1(a, k, base + i, a.noise ? a.noise[base + i] : 0.0f);
         }
     }
 }
@@ -360,6 +525,45 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 }  // namespace
 
+// grid.x of the elementwise launches: one thread per unit of work, at most 4096 blocks (grid-stride beyond)
+inline unsigned grid_x(int64_t work) { return (unsigned)((work + 255) / 256 > 4096 ? 4096 : (work + 255) / 256); }
+
+static int philox_key_check(const uint64_t *seed, int64_t n, const char *who)
+{
+    ANODDPM_REQUIRE(seed, "%s: null seed pointer", who);
+    ANODDPM_REQUIRE(n <= ((int64_t)1 << 34), "%s: more than 2^34 elements per sample (the quad counter is 32 bits)", who);
+    return ANODDPM_OK;
+}
+
+extern "C" int anoddpm_philox_bits_host(uint64_t seed, uint32_t stream, uint32_t step, uint32_t domain, uint32_t quad0,
+                                        int64_t nquads, uint32_t *out)
+{
+    ANODDPM_REQUIRE(nquads >= 0 && (nquads == 0 || out), "philox_bits_host: bad arguments");
+    for (int64_t j = 0; j < nquads; ++j) {
+        const PhiloxWords p = philox4x32_10(quad0 + (uint32_t)j, stream, step, domain, (uint32_t)seed, (uint32_t)(seed >> 32));
+        for (int l = 0; l < 4; ++l) out[4 * j + l] = p.w[l];
+    }
+    return ANODDPM_OK;
+}
+
+extern "C" int anoddpm_philox_fill(void *out, int32_t kind, int32_t B, int64_t n, const uint64_t *seed, const int32_t *streams,
+                                   uint32_t stream0, uint32_t domain, const int64_t *t, uint32_t step0, int32_t T, void *stream)
+{
+    ANODDPM_REQUIRE(B >= 0 && n >= 0 && T >= 0 && (kind == 0 || kind == 1), "philox_fill: bad sizes / kind");
+    if (B == 0 || n == 0) return ANODDPM_OK;
+    ANODDPM_REQUIRE(out, "philox_fill: null pointer");
+    ANODDPM_REQUIRE(B <= 65535, "philox_fill: B > 65535");
+    if (const int rc = philox_key_check(seed, n, "philox_fill")) return rc;
+    const PhiloxKey key = {seed, streams, stream0, domain};
+    const unsigned gx = grid_x((n + 3) / 4);
+    uint32_t *o = static_cast<uint32_t *>(out);
+    if ((n % 4 == 0) && aligned16(out))
+        hipLaunchKernelGGL(philox_fill_kernel<4>, dim3(gx, B), dim3(256), 0, anoddpm::as_stream(stream), o, kind, n, key, t, step0, T);
+    else
+        hipLaunchKernelGGL(philox_fill_kernel<1>, dim3(gx, B), dim3(256), 0, anoddpm::as_stream(stream), o, kind, n, key, t, step0, T);
+    return anoddpm::check_launch("philox_fill");
+}
+
 extern "C" int anoddpm_q_sample(float *out, const float *x, const float *noise, const int64_t *t,
                                 const float *ca, const float *cb, int32_t B, int64_t n, int32_t T, void *stream)
 {
@@ -368,33 +572,75 @@ extern "C" int anoddpm_q_sample(float *out, const float *x, const float *noise, 
     ANODDPM_REQUIRE(out && x && noise && t && ca && cb, "q_sample: null pointer");
     ANODDPM_REQUIRE(B <= 65535, "q_sample: B > 65535");
     const bool v4 = (n % 4 == 0) && aligned16(out) && aligned16(x) && aligned16(noise);
-    const int64_t work = v4 ? n / 4 : n;
-    const unsigned gx = (unsigned)((work + 255) / 256 > 4096 ? 4096 : (work + 255) / 256);
+    const unsigned gx = grid_x(v4 ? n / 4 : n);
+    const PhiloxKey none = {};
     if (v4)
-        hipLaunchKernelGGL(q_sample_kernel<4>, dim3(gx, B), dim3(256), 0, anoddpm::as_stream(stream), out, x, noise, t, ca, cb, n, T);
+        hipLaunchKernelGGL((q_sample_kernel<4, false>), dim3(gx, B), dim3(256), 0, anoddpm::as_stream(stream), out, x, noise, t, ca, cb, n, T, (float *)nullptr, none);
     else
-        hipLaunchKernelGGL(q_sample_kernel<1>, dim3(gx, B), dim3(256), 0, anoddpm::as_stream(stream), out, x, noise, t, ca, cb, n, T);
+        hipLaunchKernelGGL((q_sample_kernel<1, false>), dim3(gx, B), dim3(256), 0, anoddpm::as_stream(stream), out, x, noise, t, ca, cb, n, T, (float *)nullptr, none);
     return anoddpm::check_launch("q_sample");
+}
+
+extern "C" int anoddpm_q_sample_gauss(float *out, float *noise_out, const float *x, const int64_t *t, const float *ca,
+                                      const float *cb, int32_t B, int64_t n, int32_t T, const uint64_t *seed,
+                                      const int32_t *streams, uint32_t stream0, void *stream)
+{
+    ANODDPM_REQUIRE(B >= 0 && n >= 0 && T > 0, "q_sample_gauss: bad sizes");
+    if (B == 0 || n == 0) return ANODDPM_OK;
+    ANODDPM_REQUIRE(out && x && t && ca && cb, "q_sample_gauss: null pointer");
+    ANODDPM_REQUIRE(B <= 65535, "q_sample_gauss: B > 65535");
+    if (const int rc = philox_key_check(seed, n, "q_sample_gauss")) return rc;
+    const PhiloxKey key = {seed, streams, stream0, 1u};       // domain 1: forward / training noise
+    const bool v4 = (n % 4 == 0) && aligned16(out) && aligned16(x) && (!noise_out || aligned16(noise_out));
+    const unsigned gx = grid_x((n + 3) / 4);
+    if (v4)
+        hipLaunchKernelGGL((q_sample_kernel<4, true>), dim3(gx, B), dim3(256), 0, anoddpm::as_stream(stream), out, x, (const float *)nullptr, t, ca, cb, n, T, noise_out, key);
+    else
+        hipLaunchKernelGGL((q_sample_kernel<1, true>), dim3(gx, B), dim3(256), 0, anoddpm::as_stream(stream), out, x, (const float *)nullptr, t, ca, cb, n, T, noise_out, key);
+    return anoddpm::check_launch("q_sample_gauss");
+}
+
+// key == nullptr: anoddpm_p_sample_update; else the step noise is generated in the kernel
+static int p_update_launch(const anoddpm_p_update_args *a, const PhiloxKey *key, void *stream, const char *who)
+{
+    ANODDPM_REQUIRE(a, "%s: null argument struct", who);
+    ANODDPM_REQUIRE(a->B >= 0 && a->n >= 0 && a->T > 0, "%s: bad sizes", who);
+    if (a->B == 0 || a->n == 0) return ANODDPM_OK;
+    ANODDPM_REQUIRE(a->x_prev && a->x_t && a->eps && a->t, "%s: null pointer", who);
+    ANODDPM_REQUIRE(a->c_recip && a->c_recipm1 && a->c_coef1 && a->c_coef2 && a->c_sigma, "%s: null table", who);
+    ANODDPM_REQUIRE(a->B <= 65535, "%s: B > 65535", who);
+    const bool v4 = (a->n % 4 == 0) && aligned16(a->x_prev) && aligned16(a->x_t) && aligned16(a->eps) &&
+                    (!a->noise || aligned16(a->noise)) && (!a->pred_x0 || aligned16(a->pred_x0)) &&
+                    (!a->mean_out || aligned16(a->mean_out));
+    if (key) {
+        if (const int rc = philox_key_check(key->seed, a->n, who)) return rc;
+        ANODDPM_REQUIRE(!a->noise, "%s: a noise tensor was given as well", who);
+        const unsigned gx = grid_x((a->n + 3) / 4);
+        if (v4)
+            hipLaunchKernelGGL((p_update_kernel<4, true>), dim3(gx, a->B), dim3(256), 0, anoddpm::as_stream(stream), *a, *key);
+        else
+            hipLaunchKernelGGL((p_update_kernel<1, true>), dim3(gx, a->B), dim3(256), 0, anoddpm::as_stream(stream), *a, *key);
+        return anoddpm::check_launch(who);
+    }
+    const unsigned gx = grid_x(v4 ? a->n / 4 : a->n);
+    const PhiloxKey none = {};
+    if (v4)
+        hipLaunchKernelGGL((p_update_kernel<4, false>), dim3(gx, a->B), dim3(256), 0, anoddpm::as_stream(stream), *a, none);
+    else
+        hipLaunchKernelGGL((p_update_kernel<1, false>), dim3(gx, a->B), dim3(256), 0, anoddpm::as_stream(stream), *a, none);
+    return anoddpm::check_launch(who);
 }
 
 extern "C" int anoddpm_p_sample_update(const anoddpm_p_update_args *a, void *stream)
 {
-    ANODDPM_REQUIRE(a, "p_sample_update: null argument struct");
-    ANODDPM_REQUIRE(a->B >= 0 && a->n >= 0 && a->T > 0, "p_sample_update: bad sizes");
-    if (a->B == 0 || a->n == 0) return ANODDPM_OK;
-    ANODDPM_REQUIRE(a->x_prev && a->x_t && a->eps && a->t, "p_sample_update: null pointer");
-    ANODDPM_REQUIRE(a->c_recip && a->c_recipm1 && a->c_coef1 && a->c_coef2 && a->c_sigma, "p_sample_update: null table");
-    ANODDPM_REQUIRE(a->B <= 65535, "p_sample_update: B > 65535");
-    const bool v4 = (a->n % 4 == 0) && aligned16(a->x_prev) && aligned16(a->x_t) && aligned16(a->eps) &&
-                    (!a->noise || aligned16(a->noise)) && (!a->pred_x0 || aligned16(a->pred_x0)) &&
-                    (!a->mean_out || aligned16(a->mean_out));
-    const int64_t work = v4 ? a->n / 4 : a->n;
-    const unsigned gx = (unsigned)((work + 255) / 256 > 4096 ? 4096 : (work + 255) / 256);
-    if (v4)
-        hipLaunchKernelGGL(p_update_kernel<4>, dim3(gx, a->B), dim3(256), 0, anoddpm::as_stream(stream), *a);
-    else
-        hipLaunchKernelGGL(p_update_kernel<1>, dim3(gx, a->B), dim3(256), 0, anoddpm::as_stream(stream), *a);
-    return anoddpm::check_launch("p_sample_update");
+    return p_update_launch(a, nullptr, stream, "p_sample_update");
+}
+
+extern "C" int anoddpm_p_sample_update_gauss(const anoddpm_p_update_args *a, const uint64_t *seed, const int32_t *streams,
+                                             uint32_t stream0, void *stream)
+{
+    const PhiloxKey key = {seed, streams, stream0, 0u};       // domain 0: reverse-step noise
+    return p_update_launch(a, &key, stream, "p_sample_update_gauss");
 }
 
 extern "C" int anoddpm_chain_advance(int64_t *t, int32_t B, int32_t *step, void *stream)

@@ -27,11 +27,11 @@ import random
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, philox
 from ._lib import LossArgs, PUpdateArgs, VlbArgs, check, current_stream, lib, ptr
 from .simplex import Simplex_CLASS, perm_tables
 
-__all__ = ["SimplexNoiseFn", "ReverseChain", "get_beta_schedule", "extract", "mean_flat", "normal_kl", "approx_standard_normal_cdf",
+__all__ = ["SimplexNoiseFn", "GaussNoiseFn", "ReverseChain", "get_beta_schedule", "extract", "mean_flat", "normal_kl", "approx_standard_normal_cdf",
            "discretised_gaussian_log_likelihood", "generate_simplex_noise", "random_noise",
            "GaussianDiffusionModel"]
 
@@ -140,6 +140,21 @@ class SimplexNoiseFn:
                                       self.in_channels)
 
 
+class GaussNoiseFn:
+    """The `noise_fn` of a noise="gauss" model, and the one detection_B installs: `lambda x, t: torch.randn_like(x)` until the
+    owner is seeded (GaussianDiffusionModel.seed_gauss); then the counter-based stream of DESIGN 9g in the forward-noise domain,
+    one fresh stream id per sample, step = t.  An object (not a lambda) so that a deep copy follows its own owner's seed and so
+    that `_run_chains` can recognise it and generate the forward noise inside the q-sample kernel."""
+
+    def __init__(self, owner):
+        self.owner = owner
+
+    def __call__(self, x, t):
+        if self.owner.gauss_seed is None:
+            return torch.randn_like(x)
+        return self.owner._seeded_normal(x, t, _lib.PHILOX_FORWARD)
+
+
 def plan_chain_slots(lengths, slots):
     """Longest-first list schedule of reverse chains on `slots` chain slots (host logic of `_run_chains`).
 
@@ -169,7 +184,7 @@ class ReverseChain:
     """Device-resident state of the reverse loop (GaussianDiffusion.py:351-357): x, t and a step counter
     live in HBM; one step = model forward + noise + ONE fused update launch + t -= 1."""
 
-    def __init__(self, owner, model, x, t_distance, denoise_fn, use_graph=None):
+    def __init__(self, owner, model, x, t_distance, denoise_fn, use_graph=None, stream_base=None):
         _lib.require_cuda(x, "ReverseChain")
         if not 0 <= int(t_distance) <= owner.num_timesteps:
             # extract() of the reference indexes the T-entry tables with t_distance - 1 and raises for anything else
@@ -206,6 +221,14 @@ class ReverseChain:
             self._draw_tables(self.remaining)
         self.reuse_key = self._reuse_key_of(owner, denoise_fn)
         self.capture_safe = capture_safe
+        # A seeded owner's gaussian step noise is generated inside the update kernel: no noise buffer, no ATen launch.
+        # The kernel reads the seed and this chain's per-sample stream ids from device memory, so a kept graph follows
+        # seed_gauss() and every reset() / slot refill without a recapture.
+        self.streams = None
+        if self._seeded_gauss(owner, fn, capture_safe):
+            self.streams = torch.empty((self.B,), dtype=torch.int32, device=x.device)
+            owner._gauss_seed_dev(x.device)                         # allocated now, not inside a capture
+            self._set_streams(stream_base)
         # HIP-graph replay of the step: on by default for the built-in UNetModel (every launch of a step is
         # stream-ordered, allocation-free C-ABI work) with a capture-safe noise source; ANODDPM_NO_GRAPH=1 forces
         # eager launches.  An explicit use_graph=True with an unsafe noise source is refused, not silently wrong.
@@ -248,12 +271,26 @@ class ReverseChain:
         return fn, capture_safe
 
     @staticmethod
+    def _seeded_gauss(owner, fn, capture_safe):
+        """The resolved noise request is the gaussian one ("gauss", "random", a gauss model's own "noise_fn") of a seeded owner."""
+        return capture_safe and not isinstance(fn, SimplexNoiseFn) and getattr(owner, "gauss_seed", None) is not None
+
+    @staticmethod
     def _reuse_key_of(owner, denoise_fn):
-        """Key under which a graph-replaying chain for this noise request may be restarted with reset() (None: never)."""
+        """Key under which a graph-replaying chain for this noise request may be restarted with reset() (None: never).  A graph
+        captured with torch.randn_like is never replayed for a seeded run, nor the reverse: the keys differ."""
         fn, capture_safe = ReverseChain._resolve_noise(owner, denoise_fn)
         if isinstance(fn, SimplexNoiseFn):
             return ("simplex", id(fn.simplex), fn.octave, fn.persistence, fn.frequency, fn.in_channels)
+        if ReverseChain._seeded_gauss(owner, fn, capture_safe):
+            return ("gauss", "seeded")
         return ("gauss",) if capture_safe else None
+
+    def _set_streams(self, stream_base):
+        """Sample b of a seeded chain draws from stream `stream_base + b`; None: B fresh ids from the owner's allocator."""
+        if stream_base is None:
+            stream_base = self.owner._take_streams(self.B)
+        self.streams.copy_(philox.stream_ids(stream_base, self.B))
 
     def _draw_tables(self, nsteps):
         """Every seed of the chain, drawn now in the order the per-step newSeed() calls would (numpy global stream), and the
@@ -275,7 +312,7 @@ class ReverseChain:
         self.table_setup_ms = 1000.0 * (time.perf_counter() - t0)
         self.table_setup_steps = nsteps
 
-    def reset(self, x, t_distance):
+    def reset(self, x, t_distance, stream_base=None):
         """Start another chain of the same batch shape on this chain's device buffers: the captured HIP graph (and the plan behind
         it) is reused instead of being built again -- the detection loops run hundreds of chains of one shape."""
         if tuple(x.shape) != tuple(self.x.shape) or x.device != self.x.device:
@@ -288,6 +325,8 @@ class ReverseChain:
         self.remaining = int(t_distance)
         if self.tables is not None:
             self._draw_tables(self.remaining)
+        if self.streams is not None:
+            self._set_streams(stream_base)
         if self.hip_model and self._graph_state == 2:
             # the replayed graph reads the packed weights of the plan it was captured with (NOT whatever _plan_for would pick
             # now -- ANODDPM_ARITH may have changed since): let THAT plan re-pack them if the parameters moved since
@@ -347,9 +386,11 @@ class ReverseChain:
                                                      channel=c, tables=self.tables[c:], table_sel=self.step_idx,
                                                      table_sel_scale=fn.in_channels)
                 noise = self.noise
+            elif self.streams is not None:
+                noise = None                                        # generated inside the update kernel
             else:
                 noise = o._denoise_noise(self.x, self.t, self.denoise_fn)
-            o._reverse_update(self.x, self.t, eps, noise, want_pred=False, out=self.x)     # in place
+            o._reverse_update(self.x, self.t, eps, noise, want_pred=False, out=self.x, gauss_streams=self.streams)     # in place
             check(lib().anoddpm_chain_advance(ptr(self.t), self.B, ptr(self.step_idx), current_stream()), "chain_advance")
 
     def finish(self):
@@ -460,7 +501,7 @@ class GaussianDiffusionModel:
     def __init__(self, img_size, betas, img_channels=1, loss_type="l2", loss_weight='none', noise="gauss"):
         super().__init__()
         if noise == "gauss":
-            self.noise_fn = lambda x, t: torch.randn_like(x)
+            self.noise_fn = GaussNoiseFn(self)
         else:
             self.simplex = Simplex_CLASS()
             if noise == "simplex_randParam":
@@ -501,6 +542,42 @@ class GaussianDiffusionModel:
         self.posterior_mean_coef1 = betas * np.sqrt(self.alphas_cumprod_prev) / (1.0 - self.alphas_cumprod)
         self.posterior_mean_coef2 = (1.0 - self.alphas_cumprod_prev) * np.sqrt(alphas) / (1.0 - self.alphas_cumprod)
         self._dev = {}
+        import os
+        env = os.environ.get("ANODDPM_GAUSS_SEED")
+        self.seed_gauss(int(env, 0) if env else None)
+
+    # ------------------------------------------------------------------ seeded gaussian noise
+    def seed_gauss(self, seed):
+        """Opt in to reproducible gaussian noise: with a 64-bit `seed` every gaussian draw of this instance -- the "gauss" /
+        "random" step noise, the gauss `noise_fn` -- comes from the counter-based stream of DESIGN 9g instead of torch's generator,
+        the reverse-step noise generated inside the update kernel.  Chain / sample c since this call draws from stream c, whatever
+        slot or batch it runs in.  `None` returns to torch.randn_like.  Both attributes are plain: they pickle and deep-copy."""
+        self.gauss_seed = None if seed is None else int(seed) & ((1 << 64) - 1)
+        self.gauss_next_stream = 0
+        if self.gauss_seed is not None:
+            # kept graphs read the seed through these device words: rewrite them in place
+            for dev, word in self.__dict__.get("_gauss_dev", {}).items():
+                word.copy_(philox.seed_tensor(self.gauss_seed, "cpu"))
+
+    def _take_streams(self, count):
+        """`count` consecutive stream ids from the allocator -> the first."""
+        base = self.gauss_next_stream
+        self.gauss_next_stream = (base + int(count)) & 0xFFFFFFFF
+        return base
+
+    def _gauss_seed_dev(self, device):
+        """The device word that holds the seed (one per device for the life of the instance: captured graphs point at it)."""
+        words = self.__dict__.setdefault("_gauss_dev", {})
+        if device not in words:
+            words[device] = philox.seed_tensor(self.gauss_seed, device)
+        return words[device]
+
+    def _seeded_normal(self, x, t, domain):
+        """Seeded stand-in for torch.randn_like(x) outside a chain: sample b from a fresh stream id, at step t[b]."""
+        _lib.require_cuda(x, "GaussianDiffusionModel seeded noise")
+        B = x.shape[0]
+        return philox.normal(self._gauss_seed_dev(x.device), x.shape, stream=self._take_streams(B), step=self._t64(t, x.device),
+                             domain=domain, T=self.num_timesteps)
 
     # ------------------------------------------------------------------ device plumbing
     def _tables(self, device):
@@ -532,8 +609,23 @@ class GaussianDiffusionModel:
                                      x.numel() // max(B, 1), self.num_timesteps, current_stream()), "q_sample")
         return out
 
-    def _reverse_update(self, x_t, t, eps, noise, want_pred=True, want_mean=False, out=None):
-        """One fused launch for GaussianDiffusion.py:287-288 + :314-317."""
+    def _q_sample_gauss(self, x, t, stream_base, want_noise=False):
+        """sample_q with the forward noise of streams `stream_base + b` generated inside the kernel -> (x_t, noise or None)."""
+        _lib.require_cuda(x, "GaussianDiffusionModel.sample_q")
+        tb = self._tables(x.device)
+        x, t = self._f32(x.detach()), self._t64(t, x.device)
+        out = torch.empty_like(x)
+        noise = torch.empty_like(x) if want_noise else None
+        B = x.shape[0]
+        check(lib().anoddpm_q_sample_gauss(ptr(out), ptr(noise), ptr(x), ptr(t), ptr(tb.sqrt_alphas_cumprod),
+                                           ptr(tb.sqrt_one_minus_alphas_cumprod), B, x.numel() // max(B, 1), self.num_timesteps,
+                                           ptr(self._gauss_seed_dev(x.device)), None, int(stream_base) & 0xFFFFFFFF,
+                                           current_stream()), "q_sample_gauss")
+        return out, noise
+
+    def _reverse_update(self, x_t, t, eps, noise, want_pred=True, want_mean=False, out=None, gauss_streams=None):
+        """One fused launch for GaussianDiffusion.py:287-288 + :314-317.  gauss_streams (device int32[B], with noise None): the
+        step noise is generated inside the launch from the seeded stream of those ids."""
         _lib.require_cuda(x_t, "GaussianDiffusionModel.sample_p")
         tb = self._tables(x_t.device)
         x_t, eps = self._f32(x_t.detach()), self._f32(eps.detach())
@@ -550,7 +642,11 @@ class GaussianDiffusionModel:
         a.c_coef1, a.c_coef2, a.c_sigma = tb.posterior_mean_coef1.data_ptr(), tb.posterior_mean_coef2.data_ptr(), tb.sigma.data_ptr()
         a.B, a.T = x_t.shape[0], self.num_timesteps
         a.n = x_t.numel() // max(x_t.shape[0], 1)
-        check(lib().anoddpm_p_sample_update(ctypes.byref(a), current_stream()), "p_sample_update")
+        if gauss_streams is not None:
+            check(lib().anoddpm_p_sample_update_gauss(ctypes.byref(a), ptr(self._gauss_seed_dev(x_t.device)), ptr(gauss_streams), 0,
+                                                      current_stream()), "p_sample_update_gauss")
+        else:
+            check(lib().anoddpm_p_sample_update(ctypes.byref(a), current_stream()), "p_sample_update")
         return x_prev, pred, mean
 
     # ------------------------------------------------------------------ reference API
@@ -609,6 +705,8 @@ class GaussianDiffusionModel:
     def _denoise_noise(self, x_t, t, denoise_fn):
         """Noise selection of sample_p (GaussianDiffusion.py:301-312)."""
         if type(denoise_fn) == str:
+            if denoise_fn in ("gauss", "random") and self.gauss_seed is not None:
+                return self._seeded_normal(x_t, t, _lib.PHILOX_REVERSE)
             if denoise_fn == "gauss":
                 return torch.randn_like(x_t)
             if denoise_fn == "noise_fn":
@@ -655,7 +753,7 @@ class GaussianDiffusionModel:
 
     p_sample_loop = forward_backward          # north-star alias
 
-    def _chain_for(self, model, x, t_distance, denoise_fn):
+    def _chain_for(self, model, x, t_distance, denoise_fn, stream_base=None):
         """A ReverseChain for (model, batch shape, noise source): chains that replay a captured graph are kept -- at most eight,
         oldest dropped first; they hold their model -- and restarted with reset() (same device buffers, same graph); anything
         else is built fresh."""
@@ -667,8 +765,8 @@ class GaussianDiffusionModel:
             # a kept chain replays the dropout-free inference graph: not for a model that has since been put in train() mode
             # with dropout > 0 (it gets a fresh eager chain below, which is not kept)
             if chain is not None and chain.model is model and not ReverseChain._draws_dropout(model):
-                return chain.reset(x, t_distance)
-        chain = ReverseChain(self, model, x, t_distance, denoise_fn)
+                return chain.reset(x, t_distance, stream_base)
+        chain = ReverseChain(self, model, x, t_distance, denoise_fn, stream_base=stream_base)
         if chain.use_graph and chain.reuse_key is not None:
             if len(cache) >= 8:
                 if x.is_cuda:
@@ -701,6 +799,7 @@ class GaussianDiffusionModel:
         `postprocess` / `postprocess_roi` travel like every other plain attribute (they are in `__dict__` once assigned)."""
         d = dict(self.__dict__)
         d.pop("_chains", None)
+        d.pop("_gauss_dev", None)
         d["_dev"] = {}
         return d
 
@@ -859,7 +958,9 @@ class GaussianDiffusionModel:
     # t_distance sweep are.  The mean / mse / threshold images and the segmentation counts of a setting come from one fused pass
     # (metrics.anomaly_maps).  RNG: the same generators are consumed (np.random for simplex seeds, torch's for randn), the forward
     # noise in upstream's order, but the reverse-step draws of different chains interleave differently from the serial loop, so
-    # outputs are equal in distribution, not sample-for-sample.
+    # unseeded outputs are equal in distribution, not sample-for-sample.  After seed_gauss() the gaussian draws of chain c are a
+    # function of (seed, stream id of c, timestep, pixel) alone: a sweep is then sample-for-sample the same whatever the
+    # slot count and the schedule are, up to the kernels' batch-dependent tiling (1e-4), and bit-identical at equal slot counts.
     def _avg_chains(self, model, x_0, t_distance, total_avg):
         """One setting: `total_avg` chains of the same length as one batch (all slots start and end together)."""
         _lib.require_cuda(x_0, "GaussianDiffusionModel.detection")
@@ -872,7 +973,10 @@ class GaussianDiffusionModel:
             return self._reverse_chain(model, x, int(t_distance), "gauss", None)      # sample_p default noise, :508
 
     def _forward_noise(self, x_0, t_distance, n):
-        """`n` draws of the forward noise of one setting, in upstream's order (:501-505, :556-560)."""
+        """`n` draws of the forward noise of one setting, in upstream's order (:501-505, :556-560).  None from the seeded gaussian
+        `noise_fn`: `_run_chains` then generates the forward noise of its chains inside the q-sample kernel."""
+        if self.gauss_seed is not None and isinstance(self.noise_fn, GaussNoiseFn):
+            return []
         t_tensor = torch.full((1,), int(t_distance), device=x_0.device, dtype=torch.int64)
         return [self.noise_fn(x_0, t_tensor).float() for _ in range(n)]
 
@@ -880,7 +984,9 @@ class GaussianDiffusionModel:
         """Reverse chains of ONE image with individual lengths, batched over `slots` chain slots.
 
         t_distances[c] / noise[c]: chain c is `sample_q(x_0, t_distances[c], noise[c])` followed by t_distances[c] steps of
-        `sample_p(model, x, t)` with the default gaussian step noise (GaussianDiffusion.py:501-512, 556-567).  Returns the final
+        `sample_p(model, x, t)` with the default gaussian step noise (GaussianDiffusion.py:501-512, 556-567).  On a seeded instance
+        (seed_gauss) chain c draws its step noise from stream `base + c`, `base` being the allocator position at the call, and
+        `noise=None` asks for the seeded forward noise of the same streams.  Returns the final
         images, [len(t_distances), C, H, W].  The schedule (which slot, which global step) is kept in `self.last_chain_schedule`."""
         import os
         _lib.require_cuda(x_0, "GaussianDiffusionModel.detection")
@@ -919,7 +1025,12 @@ class GaussianDiffusionModel:
             slots = min(cands, key=lambda g: plan_chain_slots(pos, min(g, len(pos)))[0] * (2 + min(g, len(pos))))
         G = max(1, min(int(slots), n))
         t_all = torch.tensor(lens, device=x_0.device, dtype=torch.int64)
-        x_start = self.sample_q(x_0.repeat(n, 1, 1, 1), t_all, noise)
+        seeded = self.gauss_seed is not None
+        base = self._take_streams(n) if seeded else None
+        if noise is None and seeded:
+            x_start, _ = self._q_sample_gauss(x_0.repeat(n, 1, 1, 1), t_all, base)
+        else:
+            x_start = self.sample_q(x_0.repeat(n, 1, 1, 1), t_all, noise)
         live = [c for c in range(n) if lens[c] > 0]
         for c in range(n):
             if lens[c] == 0:
@@ -950,7 +1061,7 @@ class GaussianDiffusionModel:
                     cache.pop(key)
             while True:
                 try:
-                    chain = self._chain_for(model, x_start[:1].expand(G, -1, -1, -1).contiguous(), 1, "gauss")
+                    chain = self._chain_for(model, x_start[:1].expand(G, -1, -1, -1).contiguous(), 1, "gauss", stream_base=base)
                     break
                 except torch.cuda.OutOfMemoryError:
                     if not auto or G == 1:
@@ -974,6 +1085,8 @@ class GaussianDiffusionModel:
                 for slot, c in refill.get(k, ()):
                     chain.x[slot].copy_(x_start[c])
                     chain.t[slot:slot + 1].fill_(lens[c] - 1)
+                    if seeded:
+                        chain.streams[slot:slot + 1].fill_(philox.signed32(base + c))
                 chain.step()
                 for slot, c in harvest.get(k, ()):
                     out[c].copy_(chain.x[slot])
@@ -1081,7 +1194,7 @@ class GaussianDiffusionModel:
             self.noise_fn = SimplexNoiseFn(self.simplex, octave=6, persistence=0.8, frequency=64)           # :547-550
         else:
             end = int(args["T"] * 0.8)
-            self.noise_fn = lambda x, t: torch.randn_like(x)
+            self.noise_fn = GaussNoiseFn(self)
         settings = list(range(50, end, 50))
         dists, noise = [], []
         for t_distance in settings:

@@ -126,6 +126,44 @@ int anoddpm_p_sample_update(const anoddpm_p_update_args *a, void *stream);
  * (The reference rebuilds t on the host every step, GaussianDiffusion.py:351-352.) */
 int anoddpm_chain_advance(int64_t *t, int32_t B, int32_t *step, void *stream);
 
+/* ------------------------------------------------------------------ seeded Gaussian noise */
+
+/* Counter-based standard normals: a sample is a pure function of (seed, stream, step, element index).
+ *   generator  Philox4x32-10 (Random123: multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85)
+ *   key        k0 = seed & 0xffffffff, k1 = seed >> 32
+ *   counter    (c0, c1, c2, c3) = (quad, stream, step, domain); quad = i >> 2, i the element index inside ONE sample
+ *   normals    u(w) = ((w >> 9) + 0.5) * 2^-23;  r = sqrtf(-2 logf(u(w0)));  elements 4 quad + 0 / 1 = r cos / sin(2 pi u(w1)),
+ *              elements 4 quad + 2 / 3 the same from (w2, w3).  A partial last quad uses its leading lanes.
+ *   domain     0 reverse-step noise, 1 forward / training noise, 2 plain fill.
+ * Key block, the same four arguments in every entry point below:
+ *   seed     [dev] one 64-bit seed
+ *   streams  [dev] int32[B] read as uint32: the stream of sample b; NULL: stream0 + b
+ *   stream0, domain
+ * Seed and stream ids are read on the DEVICE at run time: a captured graph that contains one of these launches follows a
+ * re-written seed or stream id on its next replay. */
+
+/* out: [dev] [B][n], uint32 words (kind 0) or fp32 normals (kind 1).  t: [dev] int64[B], the step of sample b, or NULL: step0 for
+ * every sample.  T > 0: a negative t[b] means t[b] + T, as in the update kernels; T == 0: t[b] is taken as it is. */
+int anoddpm_philox_fill(void *out, int32_t kind, int32_t B, int64_t n,
+                        const uint64_t *seed, const int32_t *streams, uint32_t stream0, uint32_t domain,
+                        const int64_t *t, uint32_t step0, int32_t T, void *stream);
+
+/* The same words on the HOST (no GPU): out[4 j + k] = word k of counter (quad0 + j, stream, step, domain), j < nquads. */
+int anoddpm_philox_bits_host(uint64_t seed, uint32_t stream, uint32_t step, uint32_t domain, uint32_t quad0, int64_t nquads,
+                             uint32_t *out);
+
+/* anoddpm_p_sample_update with the step noise generated in the kernel: a->noise must be NULL, the domain is 0, the step is the
+ * kernel's own normalised t[b].  Bit-identical to anoddpm_philox_fill (kind 1, same key, domain 0, T = a->T) followed by
+ * anoddpm_p_sample_update; 12 B/pixel and one launch instead of 4 + 16 B/pixel and two. */
+int anoddpm_p_sample_update_gauss(const anoddpm_p_update_args *a, const uint64_t *seed, const int32_t *streams, uint32_t stream0,
+                                  void *stream);
+
+/* anoddpm_q_sample with N generated in the kernel: out = ca[t[b]] * x + cb[t[b]] * N, domain 1, step = normalised t[b];
+ * noise_out ([dev] [B][n] or NULL) receives N.  Bit-identical to anoddpm_philox_fill (domain 1) + anoddpm_q_sample. */
+int anoddpm_q_sample_gauss(float *out, float *noise_out, const float *x, const int64_t *t, const float *ca, const float *cb,
+                           int32_t B, int64_t n, int32_t T,
+                           const uint64_t *seed, const int32_t *streams, uint32_t stream0, void *stream);
+
 /* ------------------------------------------------------------------ UNet ops ----------- */
 
 /* Operation codes for anoddpm_run_ops: one UNet forward is a flat list of these. */
