@@ -311,6 +311,7 @@ SYMBOLS = [
     "anoddpm_ssim", "anoddpm_ssim_workspace_bytes",
     "anoddpm_median2d", "anoddpm_erode2d", "anoddpm_small_components", "anoddpm_small_components_workspace_bytes",
     "anoddpm_philox_fill", "anoddpm_philox_bits_host", "anoddpm_p_sample_update_gauss", "anoddpm_q_sample_gauss",
+    "anoddpm_strided_update", "anoddpm_chain_advance_strided",
 ]
 
 _lib = None
@@ -369,6 +370,8 @@ def lib():
                                       c_void_p, ctypes.c_uint32, c_int32, c_void_p]
     L.anoddpm_philox_bits_host.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int64, c_void_p]
     L.anoddpm_p_sample_update_gauss.argtypes = [POINTER(PUpdateArgs), c_void_p, c_void_p, ctypes.c_uint32, c_void_p]
+    L.anoddpm_strided_update.argtypes = [POINTER(PUpdateArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p]
+    L.anoddpm_chain_advance_strided.argtypes = [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
     L.anoddpm_q_sample_gauss.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32,
                                          c_void_p, c_void_p, ctypes.c_uint32, c_void_p]
     L.anoddpm_igemm.argtypes = [POINTER(IgemmArgs), c_void_p]

@@ -183,34 +183,72 @@ struct StepCoef {
     float recip, recipm1, coef1, coef2, sigma;
 };
 
+// The strided sampler's operands, all read on the device at run time: the fp64 alphas_cumprod table, one stride word
+// and one eta word.  Unused (zero) in the ancestral instantiations.
+struct StridedArgs {
+    const double *acp;
+    const int32_t *stride;
+    const float *eta;
+};
+
+// Coefficients of one strided step from t to s = t - stride (Song et al., DDIM, eq. 12 / 16), fp64, each rounded to fp32 once:
+// out = {sqrt(a_s), sqrt(max(1 - a_s - var, 0)), sqrt(var)}, var = eta^2 (1 - a_s) / (1 - a_t) (1 - a_t / a_s), a_s = 1 for s < 0
+// (that step lands on x_0).  `ti` is the normalised, in-range timestep.  A bad sample or a stride < 1 poisons the first
+// coefficient, and with it every element of the sample, with NaN; it never reads outside the table.
+__device__ __forceinline__ void strided_coef(const StridedArgs &sa, long long ti, bool bad, float out[3])
+{
+    const long long stride = *sa.stride;
+    const double eta = (double)*sa.eta;
+    const bool poison = bad || stride < 1;
+    const long long si = poison ? -1 : ti - stride;
+    const double at = sa.acp[ti], as = si < 0 ? 1.0 : sa.acp[si];
+    const double var = (eta * eta) * ((1.0 - as) / (1.0 - at)) * (1.0 - at / as);
+    out[0] = poison ? __builtin_nanf("") : (float)sqrt(as);
+    out[1] = (float)sqrt(fmax((1.0 - as) - var, 0.0));
+    out[2] = (float)sqrt(var);
+}
+
+// STRIDED: coef1 / coef2 are the x_0 and direction coefficients, the direction is the eps consistent with the clipped x_0, and a
+// zero sigma adds no noise term at all.
+template <bool STRIDED>
 __device__ __forceinline__ float reverse_one(float xt, float e, float nz, const StepCoef &k, float *px0, float *pmean)
 {
-    float x0 = k.recip * xt - k.recipm1 * e;
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    const float mean = k.coef1 * x0 + k.coef2 * xt;
+    const float p = k.recip * xt;
+    const float raw = p - k.recipm1 * e;
+    const float x0 = fminf(fmaxf(raw, -1.0f), 1.0f);
+    float mean;
+    if (STRIDED) {
+        const float dir = x0 == raw ? e : (p - x0) / k.recipm1;
+        mean = k.coef1 * x0 + k.coef2 * dir;
+    } else {
+        mean = k.coef1 * x0 + k.coef2 * xt;
+    }
     *px0 = x0;
     *pmean = mean;
+    if (STRIDED && k.sigma == 0.0f) return mean;
     return mean + k.sigma * nz;
 }
 
+template <bool STRIDED>
 __device__ __forceinline__ void reverse_store4(const anoddpm_p_update_args &a, const StepCoef &k, int64_t i, const float4 nv)
 {
     const float4 xv = *reinterpret_cast<const float4 *>(a.x_t + i);
     const float4 ev = *reinterpret_cast<const float4 *>(a.eps + i);
     float4 o, p0, mu;
-    o.x = reverse_one(xv.x, ev.x, nv.x, k, &p0.x, &mu.x);
-    o.y = reverse_one(xv.y, ev.y, nv.y, k, &p0.y, &mu.y);
-    o.z = reverse_one(xv.z, ev.z, nv.z, k, &p0.z, &mu.z);
-    o.w = reverse_one(xv.w, ev.w, nv.w, k, &p0.w, &mu.w);
+    o.x = reverse_one<STRIDED>(xv.x, ev.x, nv.x, k, &p0.x, &mu.x);
+    o.y = reverse_one<STRIDED>(xv.y, ev.y, nv.y, k, &p0.y, &mu.y);
+    o.z = reverse_one<STRIDED>(xv.z, ev.z, nv.z, k, &p0.z, &mu.z);
+    o.w = reverse_one<STRIDED>(xv.w, ev.w, nv.w, k, &p0.w, &mu.w);
     *reinterpret_cast<float4 *>(a.x_prev + i) = o;
     if (a.pred_x0) *reinterpret_cast<float4 *>(a.pred_x0 + i) = p0;
     if (a.mean_out) *reinterpret_cast<float4 *>(a.mean_out + i) = mu;
 }
 
+template <bool STRIDED>
 __device__ __forceinline__ void reverse_store1(const anoddpm_p_update_args &a, const StepCoef &k, int64_t i, float nz)
 {
     float p0, mu;
-    const float o = reverse_one(a.x_t[i], a.eps[i], nz, k, &p0, &mu);
+    const float o = reverse_one<STRIDED>(a.x_t[i], a.eps[i], nz, k, &p0, &mu);
     a.x_prev[i] = o;
     if (a.pred_x0) a.pred_x0[i] = p0;
     if (a.mean_out) a.mean_out[i] = mu;
@@ -218,8 +256,10 @@ __device__ __forceinline__ void reverse_store1(const anoddpm_p_update_args &a, c
 
 // GAUSS: a.noise is NULL; the step noise comes from `key` at (stream of sample b, step = normalised t[b]).  It is generated at
 // t == 0 too, where sigma is 0: mean + 0 * nz keeps the sign-of-zero behaviour of the unfused pair.
-template <int VEC, bool GAUSS>
-__global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a, PhiloxKey key)
+// STRIDED: the coefficients come from `sa` (thread 0 forms them in fp64, once per workgroup) instead of c_coef1 / c_coef2 /
+// c_sigma; where sigma is 0 the noise is neither read nor generated.
+template <int VEC, bool GAUSS, bool STRIDED>
+__global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a, PhiloxKey key, StridedArgs sa)
 {
     const int b = blockIdx.y;
     long long ti = a.t[b];
@@ -230,22 +270,32 @@ __global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a, 
     StepCoef k;
     k.recip = bad ? __builtin_nanf("") : a.c_recip[ti];
     k.recipm1 = a.c_recipm1[ti];
-    k.coef1 = a.c_coef1[ti];
-    k.coef2 = a.c_coef2[ti];
-    k.sigma = nonzero ? a.c_sigma[ti] : 0.0f;        // (t != 0).float() * exp(0.5*logvar)
+    if constexpr (STRIDED) {
+        __shared__ float coef[3];
+        if (threadIdx.x == 0) strided_coef(sa, ti, bad, coef);
+        __syncthreads();
+        k.coef1 = coef[0];
+        k.coef2 = coef[1];
+        k.sigma = coef[2];
+    } else {
+        k.coef1 = a.c_coef1[ti];
+        k.coef2 = a.c_coef2[ti];
+        k.sigma = nonzero ? a.c_sigma[ti] : 0.0f;    // (t != 0).float() * exp(0.5*logvar)
+    }
+    const bool noisy = !STRIDED || k.sigma != 0.0f;
     const int64_t base = (int64_t)b * a.n;
     if (GAUSS) {
         const PhiloxSample ps = philox_sample(key, b, (uint32_t)ti);
         const int64_t nq = (a.n + 3) >> 2;
         for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
-            float z[4];
-            philox_normals(ps, (uint32_t)q, z);
+            float z[4] = {0.f, 0.f, 0.f, 0.f};
+            if (noisy) philox_normals(ps, (uint32_t)q, z);
             if (VEC == 4) {
-                reverse_store4(a, k, base + 4 * q, make_float4(z[0], z[1], z[2], z[3]));
+                reverse_store4<STRIDED>(a, k, base + 4 * q, make_float4(z[0], z[1], z[2], z[3]));
             } else {
 #pragma unroll
                 for (int l = 0; l < 4; ++l)
-                    if (4 * q + l < a.n) reverse_store1(a, k, base + 4 * q + l, z[l]);
+                    if (4 * q + l < a.n) reverse_store1<STRIDED>(a, k, base + 4 * q + l, z[l]);
             }
         }
         return;
@@ -253,10 +303,10 @@ __global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a, 
     for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC; i < a.n; i += (int64_t)gridDim.x * 256 * VEC) {
         if (VEC == 4) {
             float4 nv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (a.noise) nv = *reinterpret_cast<const float4 *>(a.noise + base + i);
-            reverse_store4(a, k, base + i, nv);
+            if (a.noise && noisy) nv = *reinterpret_cast<const float4 *>(a.noise + base + i);
+            reverse_store4<STRIDED>(a, k, base + i, nv);
         } else {
-            reverse_store1(a, k, base + i, a.noise ? a.noise[base + i] : 0.0f);
+            reverse_store1<STRIDED>(a, k, base + i, a.noise && noisy ? a.noise[base + i] : 0.0f);
         }
     }
 }
@@ -265,6 +315,16 @@ __global__ void chain_advance_kernel(int64_t *t, int B, int32_t *step)
 {
     const int i = threadIdx.x;
     if (i < B) t[i] -= 1;
+    if (i == 0 && step) *step += 1;
+}
+
+__global__ void chain_advance_strided_kernel(int64_t *t, int B, int32_t *step, const int32_t *stride)
+{
+    const int i = threadIdx.x;
+    if (i < B) {
+        const long long next = (long long)t[i] - (long long)*stride;
+        t[i] = next < 0 ? 0 : next;
+    }
     if (i == 0 && step) *step += 1;
 }
 
@@ -600,47 +660,72 @@ extern "C" int anoddpm_q_sample_gauss(float *out, float *noise_out, const float 
     return anoddpm::check_launch("q_sample_gauss");
 }
 
-// key == nullptr: anoddpm_p_sample_update; else the step noise is generated in the kernel
-static int p_update_launch(const anoddpm_p_update_args *a, const PhiloxKey *key, void *stream, const char *who)
+template <bool GAUSS, bool STRIDED>
+static void p_update_dispatch(bool v4, unsigned gx, const anoddpm_p_update_args &a, const PhiloxKey &key, const StridedArgs &sa,
+                              void *stream)
+{
+    if (v4)
+        hipLaunchKernelGGL((p_update_kernel<4, GAUSS, STRIDED>), dim3(gx, a.B), dim3(256), 0, anoddpm::as_stream(stream), a, key, sa);
+    else
+        hipLaunchKernelGGL((p_update_kernel<1, GAUSS, STRIDED>), dim3(gx, a.B), dim3(256), 0, anoddpm::as_stream(stream), a, key, sa);
+}
+
+// key == nullptr: the noise tensor a->noise (or none); else the step noise is generated in the kernel.  sa == nullptr: the
+// ancestral update from the c_coef1 / c_coef2 / c_sigma tables; else the strided sampler's, which ignores those three.
+static int p_update_launch(const anoddpm_p_update_args *a, const PhiloxKey *key, const StridedArgs *sa, void *stream, const char *who)
 {
     ANODDPM_REQUIRE(a, "%s: null argument struct", who);
     ANODDPM_REQUIRE(a->B >= 0 && a->n >= 0 && a->T > 0, "%s: bad sizes", who);
     if (a->B == 0 || a->n == 0) return ANODDPM_OK;
     ANODDPM_REQUIRE(a->x_prev && a->x_t && a->eps && a->t, "%s: null pointer", who);
-    ANODDPM_REQUIRE(a->c_recip && a->c_recipm1 && a->c_coef1 && a->c_coef2 && a->c_sigma, "%s: null table", who);
+    ANODDPM_REQUIRE(a->c_recip && a->c_recipm1, "%s: null table", who);
+    if (sa)
+        ANODDPM_REQUIRE(sa->acp && sa->stride && sa->eta, "%s: null alphas_cumprod / stride / eta", who);
+    else
+        ANODDPM_REQUIRE(a->c_coef1 && a->c_coef2 && a->c_sigma, "%s: null table", who);
     ANODDPM_REQUIRE(a->B <= 65535, "%s: B > 65535", who);
     const bool v4 = (a->n % 4 == 0) && aligned16(a->x_prev) && aligned16(a->x_t) && aligned16(a->eps) &&
                     (!a->noise || aligned16(a->noise)) && (!a->pred_x0 || aligned16(a->pred_x0)) &&
                     (!a->mean_out || aligned16(a->mean_out));
+    const StridedArgs no_stride = {};
     if (key) {
         if (const int rc = philox_key_check(key->seed, a->n, who)) return rc;
         ANODDPM_REQUIRE(!a->noise, "%s: a noise tensor was given as well", who);
         const unsigned gx = grid_x((a->n + 3) / 4);
-        if (v4)
-            hipLaunchKernelGGL((p_update_kernel<4, true>), dim3(gx, a->B), dim3(256), 0, anoddpm::as_stream(stream), *a, *key);
+        if (sa)
+            p_update_dispatch<true, true>(v4, gx, *a, *key, *sa, stream);
         else
-            hipLaunchKernelGGL((p_update_kernel<1, true>), dim3(gx, a->B), dim3(256), 0, anoddpm::as_stream(stream), *a, *key);
+            p_update_dispatch<true, false>(v4, gx, *a, *key, no_stride, stream);
         return anoddpm::check_launch(who);
     }
     const unsigned gx = grid_x(v4 ? a->n / 4 : a->n);
     const PhiloxKey none = {};
-    if (v4)
-        hipLaunchKernelGGL((p_update_kernel<4, false>), dim3(gx, a->B), dim3(256), 0, anoddpm::as_stream(stream), *a, none);
+    if (sa)
+        p_update_dispatch<false, true>(v4, gx, *a, none, *sa, stream);
     else
-        hipLaunchKernelGGL((p_update_kernel<1, false>), dim3(gx, a->B), dim3(256), 0, anoddpm::as_stream(stream), *a, none);
+        p_update_dispatch<false, false>(v4, gx, *a, none, no_stride, stream);
     return anoddpm::check_launch(who);
 }
 
 extern "C" int anoddpm_p_sample_update(const anoddpm_p_update_args *a, void *stream)
 {
-    return p_update_launch(a, nullptr, stream, "p_sample_update");
+    return p_update_launch(a, nullptr, nullptr, stream, "p_sample_update");
 }
 
 extern "C" int anoddpm_p_sample_update_gauss(const anoddpm_p_update_args *a, const uint64_t *seed, const int32_t *streams,
                                              uint32_t stream0, void *stream)
 {
     const PhiloxKey key = {seed, streams, stream0, 0u};       // domain 0: reverse-step noise
-    return p_update_launch(a, &key, stream, "p_sample_update_gauss");
+    return p_update_launch(a, &key, nullptr, stream, "p_sample_update_gauss");
+}
+
+extern "C" int anoddpm_strided_update(const anoddpm_p_update_args *a, const double *alphas_cumprod, const int32_t *stride,
+                                      const float *eta, const uint64_t *seed, const int32_t *streams, uint32_t stream0, void *stream)
+{
+    const StridedArgs sa = {alphas_cumprod, stride, eta};
+    if (!seed) return p_update_launch(a, nullptr, &sa, stream, "strided_update");
+    const PhiloxKey key = {seed, streams, stream0, 0u};       // domain 0, as the ancestral update: the keying is the same
+    return p_update_launch(a, &key, &sa, stream, "strided_update");
 }
 
 extern "C" int anoddpm_chain_advance(int64_t *t, int32_t B, int32_t *step, void *stream)
@@ -649,6 +734,14 @@ extern "C" int anoddpm_chain_advance(int64_t *t, int32_t B, int32_t *step, void 
     hipLaunchKernelGGL(chain_advance_kernel, dim3(1), dim3(B < 64 ? 64 : ((B + 63) / 64) * 64), 0,
                        anoddpm::as_stream(stream), t, B, step);
     return anoddpm::check_launch("chain_advance");
+}
+
+extern "C" int anoddpm_chain_advance_strided(int64_t *t, int32_t B, int32_t *step, const int32_t *stride, void *stream)
+{
+    ANODDPM_REQUIRE(t && stride && B >= 0 && B <= 1024, "chain_advance_strided: bad arguments");
+    hipLaunchKernelGGL(chain_advance_strided_kernel, dim3(1), dim3(B < 64 ? 64 : ((B + 63) / 64) * 64), 0,
+                       anoddpm::as_stream(stream), t, B, step, stride);
+    return anoddpm::check_launch("chain_advance_strided");
 }
 
 extern "C" int anoddpm_vlb_terms(const anoddpm_vlb_args *a, void *stream)

@@ -31,7 +31,7 @@ from . import _lib, philox
 from ._lib import LossArgs, PUpdateArgs, VlbArgs, check, current_stream, lib, ptr
 from .simplex import Simplex_CLASS, perm_tables
 
-__all__ = ["SimplexNoiseFn", "GaussNoiseFn", "ReverseChain", "get_beta_schedule", "extract", "mean_flat", "normal_kl", "approx_standard_normal_cdf",
+__all__ = ["SimplexNoiseFn", "GaussNoiseFn", "ReverseChain", "StridedSampler", "get_beta_schedule", "extract", "mean_flat", "normal_kl", "approx_standard_normal_cdf",
            "discretised_gaussian_log_likelihood", "generate_simplex_noise", "random_noise",
            "GaussianDiffusionModel"]
 
@@ -155,6 +155,73 @@ class GaussNoiseFn:
         return self.owner._seeded_normal(x, t, _lib.PHILOX_FORWARD)
 
 
+class StridedSampler:
+    """Opt-in reverse sampler that strides over timesteps (Song et al., "Denoising Diffusion Implicit Models", eq. 12 and 16;
+    DESIGN 9h); immutable.  `stride` >= 1: a step goes from t to t - stride, so a chain of t_distance d visits d-1, d-1-stride, ...
+    and takes ceil(d / stride) steps; the step that would pass t = 0 lands on the predicted x_0.  `eta` in [0, 1] scales the step
+    noise; 0 is deterministic.  The UNet sees the original timestep values, so a trained checkpoint is used as it is.
+
+    This is a DIFFERENT sampler, not a faster spelling of the reference's: at stride 1, eta 1 the mean is algebraically the
+    reference's posterior mean, but the variance is the posterior variance, not the reference's fixed-large `model_variance`.
+    What a stride does to detection quality (AUC, Dice) has not been measured."""
+    __slots__ = ("stride", "eta")
+
+    def __init__(self, stride, eta=0.0):
+        if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1 or stride > 2 ** 31 - 1:
+            raise ValueError(f"StridedSampler: stride must be an integer >= 1, got {stride!r}")
+        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or not 0.0 <= eta <= 1.0:
+            raise ValueError(f"StridedSampler: eta must be a number in [0, 1], got {eta!r}")
+        object.__setattr__(self, "stride", int(stride))
+        object.__setattr__(self, "eta", float(eta))
+
+    @classmethod
+    def parse(cls, text):
+        """"<stride>[,<eta>]", the form of the ANODDPM_SAMPLER environment variable."""
+        parts = [p.strip() for p in str(text).split(",")]
+        try:
+            if not 1 <= len(parts) <= 2:
+                raise ValueError
+            return cls(int(parts[0], 10), float(parts[1]) if len(parts) == 2 else 0.0)
+        except ValueError:
+            raise ValueError(f"ANODDPM_SAMPLER={text!r}: expected '<stride>[,<eta>]' with an integer stride >= 1 and "
+                             "0 <= eta <= 1") from None
+
+    def steps(self, t_distance):
+        """Reverse steps of a chain of `t_distance` timesteps: ceil(t_distance / stride)."""
+        return -(-int(t_distance) // self.stride)
+
+    def timesteps(self, t_distance):
+        """The timesteps such a chain visits: t_distance - 1, t_distance - 1 - stride, ... down to the last one >= 0."""
+        return list(range(int(t_distance) - 1, -1, -self.stride))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("StridedSampler is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("StridedSampler is immutable")
+
+    def _key(self):
+        return (self.stride, self.eta)
+
+    def __eq__(self, other):
+        return isinstance(other, StridedSampler) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"StridedSampler(stride={self.stride!r}, eta={self.eta!r})"
+
+    def __reduce__(self):
+        return StridedSampler, self._key()
+
+
+def _check_sampler(sampler):
+    if sampler is not None and not isinstance(sampler, StridedSampler):
+        raise TypeError(f"sampler must be None or a StridedSampler, got {type(sampler).__name__}")
+    return sampler
+
+
 def plan_chain_slots(lengths, slots):
     """Longest-first list schedule of reverse chains on `slots` chain slots (host logic of `_run_chains`).
 
@@ -182,9 +249,10 @@ def plan_chain_slots(lengths, slots):
 
 class ReverseChain:
     """Device-resident state of the reverse loop (GaussianDiffusion.py:351-357): x, t and a step counter
-    live in HBM; one step = model forward + noise + ONE fused update launch + t -= 1."""
+    live in HBM; one step = model forward + noise + ONE fused update launch + t -= 1.  With a `sampler` (StridedSampler) the
+    update is the strided one, t -= stride (floored at 0), and `remaining` counts ceil(t_distance / stride) steps."""
 
-    def __init__(self, owner, model, x, t_distance, denoise_fn, use_graph=None, stream_base=None):
+    def __init__(self, owner, model, x, t_distance, denoise_fn, use_graph=None, stream_base=None, sampler=None):
         _lib.require_cuda(x, "ReverseChain")
         if not 0 <= int(t_distance) <= owner.num_timesteps:
             # extract() of the reference indexes the T-entry tables with t_distance - 1 and raises for anything else
@@ -197,7 +265,10 @@ class ReverseChain:
         self.x = owner._f32(x.detach()).clone()
         self.t = torch.full((self.B,), t_distance - 1, device=x.device, dtype=torch.int64)
         self.step_idx = torch.zeros(1, device=x.device, dtype=torch.int32)
-        self.remaining = int(t_distance)
+        self.sampler = _check_sampler(sampler)
+        self.remaining = int(t_distance) if sampler is None else sampler.steps(t_distance)
+        if sampler is not None:
+            owner._sampler_words(x.device, sampler)                 # allocated and written now, not inside a capture
         # a train()-mode model with dropout draws a fresh mask per forward from the host generator (UNet.py:192): it goes
         # through model.forward (eager), not through the captured inference plan
         self.hip_model = hasattr(model, "forward_hip") and not self._draws_dropout(model)
@@ -219,7 +290,7 @@ class ReverseChain:
             # room for the permutation tables of a full-length chain, so that reset() can start another chain on the same buffers
             self.tables = torch.empty((max(self.remaining, owner.num_timesteps) * fn.in_channels, 512), dtype=torch.int16, device=x.device)
             self._draw_tables(self.remaining)
-        self.reuse_key = self._reuse_key_of(owner, denoise_fn)
+        self.reuse_key = self._reuse_key_of(owner, denoise_fn, sampler)
         self.capture_safe = capture_safe
         # A seeded owner's gaussian step noise is generated inside the update kernel: no noise buffer, no ATen launch.
         # The kernel reads the seed and this chain's per-sample stream ids from device memory, so a kept graph follows
@@ -276,15 +347,19 @@ class ReverseChain:
         return capture_safe and not isinstance(fn, SimplexNoiseFn) and getattr(owner, "gauss_seed", None) is not None
 
     @staticmethod
-    def _reuse_key_of(owner, denoise_fn):
+    def _reuse_key_of(owner, denoise_fn, sampler=None):
         """Key under which a graph-replaying chain for this noise request may be restarted with reset() (None: never).  A graph
-        captured with torch.randn_like is never replayed for a seeded run, nor the reverse: the keys differ."""
+        captured with torch.randn_like is never replayed for a seeded run, nor the reverse: the keys differ.  Likewise an
+        ancestral graph and a strided one (tag "strided"); stride and eta are NOT in the key -- the strided launches read them
+        from device words, so one strided graph serves every stride."""
         fn, capture_safe = ReverseChain._resolve_noise(owner, denoise_fn)
         if isinstance(fn, SimplexNoiseFn):
-            return ("simplex", id(fn.simplex), fn.octave, fn.persistence, fn.frequency, fn.in_channels)
-        if ReverseChain._seeded_gauss(owner, fn, capture_safe):
-            return ("gauss", "seeded")
-        return ("gauss",) if capture_safe else None
+            key = ("simplex", id(fn.simplex), fn.octave, fn.persistence, fn.frequency, fn.in_channels)
+        elif ReverseChain._seeded_gauss(owner, fn, capture_safe):
+            key = ("gauss", "seeded")
+        else:
+            key = ("gauss",) if capture_safe else None
+        return key + ("strided",) if key is not None and sampler is not None else key
 
     def _set_streams(self, stream_base):
         """Sample b of a seeded chain draws from stream `stream_base + b`; None: B fresh ids from the owner's allocator."""
@@ -312,9 +387,14 @@ class ReverseChain:
         self.table_setup_ms = 1000.0 * (time.perf_counter() - t0)
         self.table_setup_steps = nsteps
 
-    def reset(self, x, t_distance, stream_base=None):
+    def reset(self, x, t_distance, stream_base=None, sampler=None):
         """Start another chain of the same batch shape on this chain's device buffers: the captured HIP graph (and the plan behind
-        it) is reused instead of being built again -- the detection loops run hundreds of chains of one shape."""
+        it) is reused instead of being built again -- the detection loops run hundreds of chains of one shape.  A strided chain
+        may be handed another `sampler` (None: keep its own): the kept graph follows the re-written stride / eta words."""
+        if sampler is not None:
+            if self.sampler is None:
+                raise ValueError("ReverseChain.reset: an ancestral chain cannot be restarted as a strided one")
+            self.sampler = _check_sampler(sampler)
         if tuple(x.shape) != tuple(self.x.shape) or x.device != self.x.device:
             raise ValueError("ReverseChain.reset: shape / device differ from the chain's buffers")
         if not 0 <= int(t_distance) <= self.owner.num_timesteps:
@@ -322,7 +402,9 @@ class ReverseChain:
         self.x.copy_(self.owner._f32(x.detach()))
         self.t.fill_(int(t_distance) - 1)
         self.step_idx.zero_()
-        self.remaining = int(t_distance)
+        self.remaining = int(t_distance) if self.sampler is None else self.sampler.steps(t_distance)
+        if self.sampler is not None:
+            self.owner._sampler_words(self.x.device, self.sampler)
         if self.tables is not None:
             self._draw_tables(self.remaining)
         if self.streams is not None:
@@ -334,6 +416,9 @@ class ReverseChain:
         return self
 
     def step(self):
+        if self.sampler is not None:
+            # host-side comparison; a copy only when another strided call on this owner re-wrote the words since (never in a capture)
+            self.owner._sampler_words(self.x.device, self.sampler)
         if self.use_graph and lib().anoddpm_prof_active() == 0:
             if self._graph_state == 2:
                 self.graph.replay()
@@ -390,6 +475,12 @@ class ReverseChain:
                 noise = None                                        # generated inside the update kernel
             else:
                 noise = o._denoise_noise(self.x, self.t, self.denoise_fn)
+            if self.sampler is not None:
+                words = o._sampler_words(self.x.device, None)
+                o._strided_update(self.x, self.t, eps, noise, None, want_pred=False, out=self.x, gauss_streams=self.streams)
+                check(lib().anoddpm_chain_advance_strided(ptr(self.t), self.B, ptr(self.step_idx), ptr(words.stride),
+                                                          current_stream()), "chain_advance_strided")
+                return
             o._reverse_update(self.x, self.t, eps, noise, want_pred=False, out=self.x, gauss_streams=self.streams)     # in place
             check(lib().anoddpm_chain_advance(ptr(self.t), self.B, ptr(self.step_idx), current_stream()), "chain_advance")
 
@@ -418,6 +509,23 @@ class _DeviceTables:
         self.posterior_log_variance_clipped = up(owner.posterior_log_variance_clipped)
         # exp(0.5*log_variance) evaluated by the same fp32 torch expression the reference uses (:317)
         self.sigma = torch.exp(0.5 * torch.from_numpy(model_logvar).float()).to(device)
+
+
+class _SamplerWords:
+    """What the strided launches read on one device: the fp64 alphas_cumprod table and the stride / eta words (kept for the life
+    of the instance: captured graphs point at them), with a host copy of what the words hold."""
+
+    def __init__(self, owner, device):
+        self.acp = torch.from_numpy(np.ascontiguousarray(owner.alphas_cumprod, dtype=np.float64)).to(device)
+        self.stride = torch.zeros(1, dtype=torch.int32, device=device)      # 0 until written: a launch before that gives NaN
+        self.eta = torch.zeros(1, dtype=torch.float32, device=device)
+        self.held = None
+
+    def write(self, sampler):
+        if sampler != self.held:
+            self.stride.copy_(torch.tensor([sampler.stride], dtype=torch.int32))
+            self.eta.copy_(torch.tensor([sampler.eta], dtype=torch.float32))
+            self.held = sampler
 
 
 class _FusedLoss(torch.autograd.Function):
@@ -497,6 +605,10 @@ class GaussianDiffusionModel:
     # like one image or like x_0): see _attach_postprocessed.  Plain attributes: pickled and deep-copied with the instance.
     postprocess = None
     postprocess_roi = None
+    # opt-in strided reverse sampler (StridedSampler; None: the reference's ancestral sampler, and none of the strided code runs).
+    # Read by ReverseChain / reverse_chain / forward_backward and the detection loops unless they are handed `sampler=`; also set at
+    # construction from ANODDPM_SAMPLER="<stride>[,<eta>]".  A plain attribute like `postprocess`.
+    sampler = None
 
     def __init__(self, img_size, betas, img_channels=1, loss_type="l2", loss_weight='none', noise="gauss"):
         super().__init__()
@@ -545,6 +657,9 @@ class GaussianDiffusionModel:
         import os
         env = os.environ.get("ANODDPM_GAUSS_SEED")
         self.seed_gauss(int(env, 0) if env else None)
+        env = os.environ.get("ANODDPM_SAMPLER")
+        if env:
+            self.sampler = StridedSampler.parse(env)
 
     # ------------------------------------------------------------------ seeded gaussian noise
     def seed_gauss(self, seed):
@@ -578,6 +693,53 @@ class GaussianDiffusionModel:
         B = x.shape[0]
         return philox.normal(self._gauss_seed_dev(x.device), x.shape, stream=self._take_streams(B), step=self._t64(t, x.device),
                              domain=domain, T=self.num_timesteps)
+
+    # ------------------------------------------------------------------ strided sampler
+    def _sampler_words(self, device, sampler):
+        """The device's _SamplerWords, holding `sampler`'s stride and eta (None: as they are).  Never called inside a capture with
+        a sampler that differs from what the words hold."""
+        words = self.__dict__.setdefault("_sampler_dev", {})
+        device = torch.device(device)
+        w = words.get(device)
+        if w is None:
+            w = words[device] = _SamplerWords(self, device)
+        if sampler is not None:
+            w.write(_check_sampler(sampler))
+        return w
+
+    def _strided_update(self, x_t, t, eps, noise, sampler, want_pred=True, want_mean=False, out=None, gauss_streams=None):
+        """One fused launch of the strided step (anoddpm_strided_update), the counterpart of `_reverse_update`.  `sampler` None:
+        the stride / eta words are used as they are (a chain wrote them before its step).  -> (x_prev, pred_x_0, mean)."""
+        _lib.require_cuda(x_t, "GaussianDiffusionModel.sample_p_strided")
+        tb = self._tables(x_t.device)
+        words = self._sampler_words(x_t.device, sampler)
+        x_t, eps = self._f32(x_t.detach()), self._f32(eps.detach())
+        if noise is not None:
+            noise = self._f32(noise.detach())
+        t = self._t64(t, x_t.device)
+        a = PUpdateArgs()
+        x_prev = out if out is not None else torch.empty_like(x_t)
+        pred = torch.empty_like(x_t) if want_pred else None
+        mean = torch.empty_like(x_t) if want_mean else None
+        a.x_prev, a.pred_x0, a.mean_out = x_prev.data_ptr(), pred.data_ptr() if want_pred else None, mean.data_ptr() if want_mean else None
+        a.x_t, a.eps, a.noise, a.t = x_t.data_ptr(), eps.data_ptr(), noise.data_ptr() if noise is not None else None, t.data_ptr()
+        a.c_recip, a.c_recipm1 = tb.sqrt_recip_alphas_cumprod.data_ptr(), tb.sqrt_recipm1_alphas_cumprod.data_ptr()
+        a.B, a.T = x_t.shape[0], self.num_timesteps
+        a.n = x_t.numel() // max(x_t.shape[0], 1)
+        seed = ptr(self._gauss_seed_dev(x_t.device)) if gauss_streams is not None else None
+        check(lib().anoddpm_strided_update(ctypes.byref(a), ptr(words.acp), ptr(words.stride), ptr(words.eta), seed,
+                                           ptr(gauss_streams), 0, current_stream()), "strided_update")
+        return x_prev, pred, mean
+
+    def sample_p_strided(self, model, x_t, t, sampler, denoise_fn="gauss"):
+        """One step of the strided sampler from t to t - sampler.stride: model -> noise -> ONE fused launch.  The counterpart of
+        `sample_p`; see StridedSampler for what this sampler is and is not.  With eta == 0 no noise is drawn."""
+        if _check_sampler(sampler) is None:
+            raise TypeError("sample_p_strided: a StridedSampler is required")
+        eps = model(x_t, t)
+        noise = self._denoise_noise(x_t, t, denoise_fn) if sampler.eta != 0.0 else None
+        sample, pred, _ = self._strided_update(x_t, t, eps, noise, sampler)
+        return {"sample": sample, "pred_x_0": pred}
 
     # ------------------------------------------------------------------ device plumbing
     def _tables(self, device):
@@ -723,8 +885,10 @@ class GaussianDiffusionModel:
         sample, pred, _ = self._reverse_update(x_t, t, eps, noise)
         return {"sample": sample, "pred_x_0": pred}
 
-    def forward_backward(self, model, x, see_whole_sequence="half", t_distance=None, denoise_fn="gauss"):
-        """GaussianDiffusion.py:320-359.  `t` lives on the device for the whole chain."""
+    def forward_backward(self, model, x, see_whole_sequence="half", t_distance=None, denoise_fn="gauss", sampler=None):
+        """GaussianDiffusion.py:320-359.  `t` lives on the device for the whole chain.  `sampler` (else `self.sampler`): a
+        StridedSampler runs the reverse half in ceil(t_distance / stride) steps, and `seq` then holds one image per step."""
+        sampler = _check_sampler(sampler) if sampler is not None else self.sampler
         assert see_whole_sequence == "whole" or see_whole_sequence == "half" or see_whole_sequence == None
 
         if t_distance == 0:
@@ -748,25 +912,25 @@ class GaussianDiffusionModel:
                 seq.append(x.cpu().detach())
 
         with torch.no_grad():
-            x = self._reverse_chain(model, x, int(t_distance), denoise_fn, seq if see_whole_sequence else None)
+            x = self._reverse_chain(model, x, int(t_distance), denoise_fn, seq if see_whole_sequence else None, sampler)
         return x.detach() if not see_whole_sequence else seq
 
     p_sample_loop = forward_backward          # north-star alias
 
-    def _chain_for(self, model, x, t_distance, denoise_fn, stream_base=None):
+    def _chain_for(self, model, x, t_distance, denoise_fn, stream_base=None, sampler=None):
         """A ReverseChain for (model, batch shape, noise source): chains that replay a captured graph are kept -- at most eight,
         oldest dropped first; they hold their model -- and restarted with reset() (same device buffers, same graph); anything
         else is built fresh."""
         cache = self.__dict__.setdefault("_chains", {})
-        want = ReverseChain._reuse_key_of(self, denoise_fn)
+        want = ReverseChain._reuse_key_of(self, denoise_fn, sampler)
         if want is not None:
             key = (id(model), tuple(x.shape), str(x.device), want)
             chain = cache.get(key)
             # a kept chain replays the dropout-free inference graph: not for a model that has since been put in train() mode
             # with dropout > 0 (it gets a fresh eager chain below, which is not kept)
             if chain is not None and chain.model is model and not ReverseChain._draws_dropout(model):
-                return chain.reset(x, t_distance, stream_base)
-        chain = ReverseChain(self, model, x, t_distance, denoise_fn, stream_base=stream_base)
+                return chain.reset(x, t_distance, stream_base, sampler)
+        chain = ReverseChain(self, model, x, t_distance, denoise_fn, stream_base=stream_base, sampler=sampler)
         if chain.use_graph and chain.reuse_key is not None:
             if len(cache) >= 8:
                 if x.is_cuda:
@@ -775,10 +939,11 @@ class GaussianDiffusionModel:
             cache[(id(model), tuple(x.shape), str(x.device), chain.reuse_key)] = chain
         return chain
 
-    def _reverse_chain(self, model, x, t_distance, denoise_fn, seq):
-        """t = t_distance-1 ... 0 of sample_p with a device-resident timestep (no per-step H2D)."""
-        chain = self._chain_for(model, x, t_distance, denoise_fn)
-        for _ in range(t_distance):
+    def _reverse_chain(self, model, x, t_distance, denoise_fn, seq, sampler=None):
+        """t = t_distance-1 ... 0 of sample_p with a device-resident timestep (no per-step H2D); with a `sampler` the
+        ceil(t_distance / stride) strided steps."""
+        chain = self._chain_for(model, x, t_distance, denoise_fn, sampler=sampler)
+        for _ in range(chain.remaining):
             chain.step()
             if seq is not None:
                 seq.append(chain.x.cpu().detach())
@@ -800,6 +965,7 @@ class GaussianDiffusionModel:
         d = dict(self.__dict__)
         d.pop("_chains", None)
         d.pop("_gauss_dev", None)
+        d.pop("_sampler_dev", None)
         d["_dev"] = {}
         return d
 
@@ -811,10 +977,12 @@ class GaussianDiffusionModel:
             new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
-    def reverse_chain(self, model, x_t, t_distance, denoise_fn="gauss"):
+    def reverse_chain(self, model, x_t, t_distance, denoise_fn="gauss", sampler=None):
         """Stepping form of the reverse loop of forward_backward (:351-357): returns a ReverseChain whose
-        .step() performs one sample_p on the device-resident state (bench.py times K of these)."""
-        return ReverseChain(self, model, x_t, int(t_distance), denoise_fn)
+        .step() performs one sample_p on the device-resident state (bench.py times K of these).  `sampler` (else `self.sampler`):
+        a StridedSampler makes each step a strided one."""
+        sampler = _check_sampler(sampler) if sampler is not None else self.sampler
+        return ReverseChain(self, model, x_t, int(t_distance), denoise_fn, sampler=sampler)
 
     def sample_q(self, x_0, t, noise):
         """q(x_t | x_0), GaussianDiffusion.py:361-371 -- one fused launch."""
@@ -942,7 +1110,7 @@ class GaussianDiffusionModel:
             x = self.sample_q(x_0, t_tensor, noise_fn(x_0, t_tensor).float())
             x_noised = x.clone().detach()
             with torch.no_grad():
-                x = self._reverse_chain(model, x, t_distance, noise_fn, None)
+                x = self._reverse_chain(model, x, t_distance, noise_fn, None, self.sampler)
             mse = ((x_0 - x).square() * 2) - 1
             mse_threshold = mse > 0
             mse_threshold = (mse_threshold.float() * 2) - 1
@@ -961,8 +1129,9 @@ class GaussianDiffusionModel:
     # unseeded outputs are equal in distribution, not sample-for-sample.  After seed_gauss() the gaussian draws of chain c are a
     # function of (seed, stream id of c, timestep, pixel) alone: a sweep is then sample-for-sample the same whatever the
     # slot count and the schedule are, up to the kernels' batch-dependent tiling (1e-4), and bit-identical at equal slot counts.
-    def _avg_chains(self, model, x_0, t_distance, total_avg):
+    def _avg_chains(self, model, x_0, t_distance, total_avg, sampler=None):
         """One setting: `total_avg` chains of the same length as one batch (all slots start and end together)."""
+        sampler = _check_sampler(sampler) if sampler is not None else self.sampler
         _lib.require_cuda(x_0, "GaussianDiffusionModel.detection")
         if x_0.shape[0] != 1:
             raise ValueError("detection loops take one image (upstream stores each chain into output[avg], :514)")
@@ -970,7 +1139,7 @@ class GaussianDiffusionModel:
         noise = torch.cat([self.noise_fn(x_0, t_tensor).float() for _ in range(total_avg)])
         x = self.sample_q(x_0.repeat(total_avg, 1, 1, 1), t_tensor.repeat(total_avg), noise)
         with torch.no_grad():
-            return self._reverse_chain(model, x, int(t_distance), "gauss", None)      # sample_p default noise, :508
+            return self._reverse_chain(model, x, int(t_distance), "gauss", None, sampler)      # sample_p default noise, :508
 
     def _forward_noise(self, x_0, t_distance, n):
         """`n` draws of the forward noise of one setting, in upstream's order (:501-505, :556-560).  None from the seeded gaussian
@@ -980,20 +1149,24 @@ class GaussianDiffusionModel:
         t_tensor = torch.full((1,), int(t_distance), device=x_0.device, dtype=torch.int64)
         return [self.noise_fn(x_0, t_tensor).float() for _ in range(n)]
 
-    def _run_chains(self, model, x_0, t_distances, noise, slots=None):
+    def _run_chains(self, model, x_0, t_distances, noise, slots=None, sampler=None):
         """Reverse chains of ONE image with individual lengths, batched over `slots` chain slots.
 
         t_distances[c] / noise[c]: chain c is `sample_q(x_0, t_distances[c], noise[c])` followed by t_distances[c] steps of
         `sample_p(model, x, t)` with the default gaussian step noise (GaussianDiffusion.py:501-512, 556-567).  On a seeded instance
         (seed_gauss) chain c draws its step noise from stream `base + c`, `base` being the allocator position at the call, and
         `noise=None` asks for the seeded forward noise of the same streams.  Returns the final
-        images, [len(t_distances), C, H, W].  The schedule (which slot, which global step) is kept in `self.last_chain_schedule`."""
+        images, [len(t_distances), C, H, W].  The schedule (which slot, which global step) is kept in `self.last_chain_schedule`.
+        `sampler` (else `self.sampler`): with a StridedSampler chain c takes ceil(t_distances[c] / stride) strided steps, and the
+        schedule counts those."""
         import os
         _lib.require_cuda(x_0, "GaussianDiffusionModel.detection")
         if x_0.shape[0] != 1:
             raise ValueError("detection loops take one image (upstream stores each chain into output[avg], :514)")
+        sampler = _check_sampler(sampler) if sampler is not None else self.sampler
         n = len(t_distances)
         lens = [int(d) for d in t_distances]
+        steps = lens if sampler is None else [sampler.steps(l) for l in lens]      # reverse steps of each chain
         out = torch.empty((n,) + tuple(x_0.shape[1:]), device=x_0.device, dtype=torch.float32)
         if n == 0:
             return out
@@ -1015,7 +1188,7 @@ class GaussianDiffusionModel:
             # slot count among the quantisation-free sizes whose longest-first schedule is cheapest -- and whose plan fits: a
             # slot costs the activation buffers of one image (about 0.8 GB at 256^2 / base 128, scaled by pixels x base width;
             # 512^2 models at batch 16 are 50 GB), so sizes that would take more than half of the free device memory are skipped
-            pos = [l for l in lens if l > 0] or [1]
+            pos = [l for l in steps if l > 0] or [1]
             per_slot = 24.0 * 4.0 * float(getattr(model, "model_channels", 128)) * x_0.shape[-1] * x_0.shape[-2]
             free = torch.cuda.mem_get_info(x_0.device)[0] if x_0.is_cuda else float("inf")
             cands = [g for g in (16, 12, 8) if g <= max(n, 8) and (g == 8 or g * per_slot <= 0.5 * free)]
@@ -1035,8 +1208,8 @@ class GaussianDiffusionModel:
         for c in range(n):
             if lens[c] == 0:
                 out[c].copy_(x_start[c])                               # no reverse step: the noised image itself
-        makespan, place = plan_chain_slots([lens[c] for c in live], G)
-        self.last_chain_schedule = {"slots": G, "steps": makespan, "chain_steps": sum(lens),
+        makespan, place = plan_chain_slots([steps[c] for c in live], G)
+        self.last_chain_schedule = {"slots": G, "steps": makespan, "chain_steps": sum(steps),
                                     "place": {live[i]: place[i] for i in range(len(live))}}
         if makespan == 0:
             return out
@@ -1045,8 +1218,8 @@ class GaussianDiffusionModel:
         for i, (slot, start) in enumerate(place):
             c = live[i]
             refill.setdefault(start, []).append((slot, c))
-            harvest.setdefault(start + lens[c] - 1, []).append((slot, c))
-            last_busy[slot] = max(last_busy[slot], start + lens[c])
+            harvest.setdefault(start + steps[c] - 1, []).append((slot, c))
+            last_busy[slot] = max(last_busy[slot], start + steps[c])
         with torch.no_grad():
             # kept slot chains of this model at OTHER slot counts are superseded (each holds a plan + captured graph: 3.4 GB per
             # four images at config 2): drop them before the new plan is allocated (round-5 advisor finding)
@@ -1061,21 +1234,22 @@ class GaussianDiffusionModel:
                     cache.pop(key)
             while True:
                 try:
-                    chain = self._chain_for(model, x_start[:1].expand(G, -1, -1, -1).contiguous(), 1, "gauss", stream_base=base)
+                    chain = self._chain_for(model, x_start[:1].expand(G, -1, -1, -1).contiguous(), 1, "gauss", stream_base=base,
+                                            sampler=sampler)
                     break
                 except torch.cuda.OutOfMemoryError:
                     if not auto or G == 1:
                         raise
                     G = max(1, G // 2)                                   # the estimate was too optimistic: fewer slots, new schedule
                     torch.cuda.empty_cache()
-                    makespan, place = plan_chain_slots([lens[c] for c in live], G)
+                    makespan, place = plan_chain_slots([steps[c] for c in live], G)
                     self.last_chain_schedule.update(slots=G, steps=makespan, place={live[i]: place[i] for i in range(len(live))})
                     refill, harvest, last_busy = {}, {}, [0] * G
                     for i, (slot, start) in enumerate(place):
                         c = live[i]
                         refill.setdefault(start, []).append((slot, c))
-                        harvest.setdefault(start + lens[c] - 1, []).append((slot, c))
-                        last_busy[slot] = max(last_busy[slot], start + lens[c])
+                        harvest.setdefault(start + steps[c] - 1, []).append((slot, c))
+                        last_busy[slot] = max(last_busy[slot], start + steps[c])
             chain.slot_chain = True
             chain.remaining = makespan
             for slot in range(G):
@@ -1090,8 +1264,9 @@ class GaussianDiffusionModel:
                 chain.step()
                 for slot, c in harvest.get(k, ()):
                     out[c].copy_(chain.x[slot])
-                    if last_busy[slot] == k + 1 and k + 1 < makespan:
+                    if last_busy[slot] == k + 1 and k + 1 < makespan and sampler is None:
                         # nothing left for this slot: it idles on its last image with a timestep that stays >= 0 to the end
+                        # (a strided chain's advance floors t at 0 by itself)
                         chain.t[slot:slot + 1].fill_(makespan - k - 2)
             chain.finish()
         return out

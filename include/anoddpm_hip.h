@@ -158,6 +158,28 @@ int anoddpm_philox_bits_host(uint64_t seed, uint32_t stream, uint32_t step, uint
 int anoddpm_p_sample_update_gauss(const anoddpm_p_update_args *a, const uint64_t *seed, const int32_t *streams, uint32_t stream0,
                                   void *stream);
 
+/* One step of the strided, DDIM-style sampler (Song et al., "Denoising Diffusion Implicit Models", eq. 12 and 16), the
+ * same launch shape as anoddpm_p_sample_update: from t = t[b] to s = t - *stride, with a_t = alphas_cumprod[t] and a_s = 1 for s < 0,
+ *   var     = eta^2 * (1 - a_s) / (1 - a_t) * (1 - a_t / a_s)            fp64, once per workgroup; the three coefficients
+ *   c_x0, c_dir, sigma = sqrt(a_s), sqrt(max(1 - a_s - var, 0)), sqrt(var)        are each rounded to fp32 once
+ *   pred_x0 = clamp(c_recip[t]*x_t - c_recipm1[t]*eps, -1, 1)            (bit-identical to anoddpm_p_sample_update's)
+ *   e'      = eps where the clamp did not bind, (c_recip[t]*x_t - pred_x0) / c_recipm1[t] where it did
+ *   mean    = c_x0*pred_x0 + c_dir*e'
+ *   x_prev  = mean + sigma*noise ;  with sigma == 0 x_prev = mean and the noise is neither read nor generated
+ * a: the struct of anoddpm_p_sample_update; c_coef1, c_coef2 and c_sigma are ignored (may be NULL).
+ * alphas_cumprod [dev] fp64[a->T]; stride [dev] one int32 >= 1; eta [dev] one float in [0, 1].  Stride and eta are read on the
+ * DEVICE at run time: a captured graph follows a re-written word on its next replay.  A stride < 1 read there gives a NaN sample,
+ * as an out-of-range t[b] does; neither reads out of bounds.
+ * seed == NULL: the noise is a->noise, or none when that is NULL too.  Otherwise it is generated in the kernel from the key block
+ * (seed, streams, stream0) exactly as in anoddpm_p_sample_update_gauss -- domain 0, step = normalised t[b] -- and a->noise must
+ * be NULL. */
+int anoddpm_strided_update(const anoddpm_p_update_args *a, const double *alphas_cumprod, const int32_t *stride, const float *eta,
+                           const uint64_t *seed, const int32_t *streams, uint32_t stream0, void *stream);
+
+/* anoddpm_chain_advance for the strided sampler: t[b] = max(t[b] - *stride, 0) for all b, *step += 1; stride [dev] one int32.
+ * The floor keeps idle and finished chain slots inside the tables. */
+int anoddpm_chain_advance_strided(int64_t *t, int32_t B, int32_t *step, const int32_t *stride, void *stream);
+
 /* anoddpm_q_sample with N generated in the kernel: out = ca[t[b]] * x + cb[t[b]] * N, domain 1, step = normalised t[b];
  * noise_out ([dev] [B][n] or NULL) receives N.  Bit-identical to anoddpm_philox_fill (domain 1) + anoddpm_q_sample. */
 int anoddpm_q_sample_gauss(float *out, float *noise_out, const float *x, const int64_t *t, const float *ca, const float *cb,
