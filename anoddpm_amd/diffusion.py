@@ -247,28 +247,49 @@ def plan_chain_slots(lengths, slots):
     return makespan, place
 
 
+def choose_slots(steps, n, per_slot_bytes, free_bytes):
+    """Slot count of an automatic sweep of `n` chains of `steps` reverse steps (zeros ignored); the caller clamps it to `n`.  A batched
+    step costs about (2 + G) image-units (a batch-independent floor worth two images): the slot count among the
+    quantisation-free sizes whose longest-first schedule is cheapest -- and whose plan fits: a slot costs `per_slot_bytes` (the activation
+    buffers of one image: about 0.8 GB at 256^2 / base 128; 512^2 models at batch 16 are 50 GB), and sizes that would take more than
+    half of `free_bytes`, the free device memory, are skipped."""
+    pos = [l for l in steps if l > 0] or [1]
+    cands = [g for g in (16, 12, 8) if g <= max(n, 8) and (g == 8 or g * per_slot_bytes <= 0.5 * free_bytes)]
+    while cands[-1] > 1 and cands[-1] * per_slot_bytes > 0.5 * free_bytes:
+        cands.append(cands[-1] // 2)                                 # even eight images do not fit: 4, 2, 1 slots
+    cands = [g for g in cands if g * per_slot_bytes <= 0.5 * free_bytes] or [1]
+    return min(cands, key=lambda g: plan_chain_slots(pos, min(g, len(pos)))[0] * (2 + min(g, len(pos))))
+
+
+def slot_events(place, steps, slots):
+    """What the stepping loop does at each global step of a `plan_chain_slots` schedule; steps[i]: length of chain i.
+    -> (refill {step: [(slot, i)]}: chains that start, harvest {step: [(slot, i)]}: chains that take their last step,
+    last_busy[slot]: the first global step at which the slot has nothing left to do, 0 for a slot without a chain)."""
+    refill, harvest, last_busy = {}, {}, [0] * slots
+    for i, (slot, start) in enumerate(place):
+        refill.setdefault(start, []).append((slot, i))
+        harvest.setdefault(start + steps[i] - 1, []).append((slot, i))
+        last_busy[slot] = max(last_busy[slot], start + steps[i])
+    return refill, harvest, last_busy
+
+
 class ReverseChain:
     """Device-resident state of the reverse loop (GaussianDiffusion.py:351-357): x, t and a step counter
     live in HBM; one step = model forward + noise + ONE fused update launch + t -= 1.  With a `sampler` (StridedSampler) the
     update is the strided one, t -= stride (floored at 0), and `remaining` counts ceil(t_distance / stride) steps."""
 
     def __init__(self, owner, model, x, t_distance, denoise_fn, use_graph=None, stream_base=None, sampler=None):
+        """Everything a chain allocates, once; `_start` (shared with reset()) then begins the chain itself."""
         _lib.require_cuda(x, "ReverseChain")
-        if not 0 <= int(t_distance) <= owner.num_timesteps:
-            # extract() of the reference indexes the T-entry tables with t_distance - 1 and raises for anything else
-            raise IndexError(f"t_distance {t_distance} is out of range for a {owner.num_timesteps}-step schedule")
         self.owner, self.model, self.denoise_fn = owner, model, denoise_fn
         import os
         self.graph = None
         self._graph_state = 0          # 0: next step eager (warm-up), 1: capture, 2: replay
         self.B = x.shape[0]
-        self.x = owner._f32(x.detach()).clone()
-        self.t = torch.full((self.B,), t_distance - 1, device=x.device, dtype=torch.int64)
-        self.step_idx = torch.zeros(1, device=x.device, dtype=torch.int32)
+        self.x = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+        self.t = torch.empty((self.B,), device=x.device, dtype=torch.int64)
+        self.step_idx = torch.empty(1, device=x.device, dtype=torch.int32)
         self.sampler = _check_sampler(sampler)
-        self.remaining = int(t_distance) if sampler is None else sampler.steps(t_distance)
-        if sampler is not None:
-            owner._sampler_words(x.device, sampler)                 # allocated and written now, not inside a capture
         # a train()-mode model with dropout draws a fresh mask per forward from the host generator (UNet.py:192): it goes
         # through model.forward (eager), not through the captured inference plan
         self.hip_model = hasattr(model, "forward_hip") and not self._draws_dropout(model)
@@ -282,14 +303,11 @@ class ReverseChain:
         # host every step (newSeed(), GaussianDiffusion.py:102) and uploads a table: captured once, every replay
         # would reuse the first step's seed.  Those run eagerly.
         fn, capture_safe = self._resolve_noise(owner, denoise_fn)
-        self._last_seed = None
-        self.reuse_key = None
         if isinstance(fn, SimplexNoiseFn):
             self.simplex_fn = fn
             self.noise = torch.empty_like(self.x)
             # room for the permutation tables of a full-length chain, so that reset() can start another chain on the same buffers
-            self.tables = torch.empty((max(self.remaining, owner.num_timesteps) * fn.in_channels, 512), dtype=torch.int16, device=x.device)
-            self._draw_tables(self.remaining)
+            self.tables = torch.empty((owner.num_timesteps * fn.in_channels, 512), dtype=torch.int16, device=x.device)
         self.reuse_key = self._reuse_key_of(owner, denoise_fn, sampler)
         self.capture_safe = capture_safe
         # A seeded owner's gaussian step noise is generated inside the update kernel: no noise buffer, no ATen launch.
@@ -299,7 +317,7 @@ class ReverseChain:
         if self._seeded_gauss(owner, fn, capture_safe):
             self.streams = torch.empty((self.B,), dtype=torch.int32, device=x.device)
             owner._gauss_seed_dev(x.device)                         # allocated now, not inside a capture
-            self._set_streams(stream_base)
+        self._start(x, t_distance, stream_base)
         # HIP-graph replay of the step: on by default for the built-in UNetModel (every launch of a step is
         # stream-ordered, allocation-free C-ABI work) with a capture-safe noise source; ANODDPM_NO_GRAPH=1 forces
         # eager launches.  An explicit use_graph=True with an unsafe noise source is refused, not silently wrong.
@@ -397,7 +415,19 @@ class ReverseChain:
             self.sampler = _check_sampler(sampler)
         if tuple(x.shape) != tuple(self.x.shape) or x.device != self.x.device:
             raise ValueError("ReverseChain.reset: shape / device differ from the chain's buffers")
+        self._start(x, t_distance, stream_base)
+        if self.hip_model and self._graph_state == 2:
+            # the replayed graph reads the packed weights of the plan it was captured with (NOT whatever _plan_for would pick
+            # now -- ANODDPM_ARITH may have changed since): let THAT plan re-pack them if the parameters moved since
+            self._plan.refresh_weights()
+        return self
+
+    def _start(self, x, t_distance, stream_base):
+        """Begin a chain of `t_distance` timesteps from `x` on this chain's buffers.  The order is fixed: `_draw_tables` consumes
+        the global numpy stream and `_set_streams` the owner's stream allocator.  Never runs inside a capture: the sampler
+        words are allocated and written here."""
         if not 0 <= int(t_distance) <= self.owner.num_timesteps:
+            # extract() of the reference indexes the T-entry tables with t_distance - 1 and raises for anything else
             raise IndexError(f"t_distance {t_distance} is out of range for a {self.owner.num_timesteps}-step schedule")
         self.x.copy_(self.owner._f32(x.detach()))
         self.t.fill_(int(t_distance) - 1)
@@ -409,11 +439,6 @@ class ReverseChain:
             self._draw_tables(self.remaining)
         if self.streams is not None:
             self._set_streams(stream_base)
-        if self.hip_model and self._graph_state == 2:
-            # the replayed graph reads the packed weights of the plan it was captured with (NOT whatever _plan_for would pick
-            # now -- ANODDPM_ARITH may have changed since): let THAT plan re-pack them if the parameters moved since
-            self._plan.refresh_weights()
-        return self
 
     def step(self):
         if self.sampler is not None:
@@ -1184,18 +1209,9 @@ class GaussianDiffusionModel:
             raise ValueError("_run_chains: slots must be >= 1")
         auto = slots is None
         if auto:
-            # a batched step costs about (2 + G) image-units (a batch-independent floor worth two images): take the
-            # slot count among the quantisation-free sizes whose longest-first schedule is cheapest -- and whose plan fits: a
-            # slot costs the activation buffers of one image (about 0.8 GB at 256^2 / base 128, scaled by pixels x base width;
-            # 512^2 models at batch 16 are 50 GB), so sizes that would take more than half of the free device memory are skipped
-            pos = [l for l in steps if l > 0] or [1]
             per_slot = 24.0 * 4.0 * float(getattr(model, "model_channels", 128)) * x_0.shape[-1] * x_0.shape[-2]
             free = torch.cuda.mem_get_info(x_0.device)[0] if x_0.is_cuda else float("inf")
-            cands = [g for g in (16, 12, 8) if g <= max(n, 8) and (g == 8 or g * per_slot <= 0.5 * free)]
-            while cands[-1] > 1 and cands[-1] * per_slot > 0.5 * free:
-                cands.append(cands[-1] // 2)                             # even eight images do not fit: 4, 2, 1 slots
-            cands = [g for g in cands if g * per_slot <= 0.5 * free] or [1]
-            slots = min(cands, key=lambda g: plan_chain_slots(pos, min(g, len(pos)))[0] * (2 + min(g, len(pos))))
+            slots = choose_slots(steps, n, per_slot, free)
         G = max(1, min(int(slots), n))
         t_all = torch.tensor(lens, device=x_0.device, dtype=torch.int64)
         seeded = self.gauss_seed is not None
@@ -1205,25 +1221,14 @@ class GaussianDiffusionModel:
         else:
             x_start = self.sample_q(x_0.repeat(n, 1, 1, 1), t_all, noise)
         live = [c for c in range(n) if lens[c] > 0]
+        live_steps = [steps[c] for c in live]
         for c in range(n):
             if lens[c] == 0:
                 out[c].copy_(x_start[c])                               # no reverse step: the noised image itself
-        makespan, place = plan_chain_slots([steps[c] for c in live], G)
-        self.last_chain_schedule = {"slots": G, "steps": makespan, "chain_steps": sum(steps),
-                                    "place": {live[i]: place[i] for i in range(len(live))}}
-        if makespan == 0:
-            return out
-        refill, harvest = {}, {}
-        last_busy = [0] * G                                            # first global step at which a slot has nothing left to do
-        for i, (slot, start) in enumerate(place):
-            c = live[i]
-            refill.setdefault(start, []).append((slot, c))
-            harvest.setdefault(start + steps[c] - 1, []).append((slot, c))
-            last_busy[slot] = max(last_busy[slot], start + steps[c])
-        with torch.no_grad():
+        cache = self.__dict__.setdefault("_chains", {})
+        while live:                                                    # until a chain AND its plan for G slots are secured
             # kept slot chains of this model at OTHER slot counts are superseded (each holds a plan + captured graph: 3.4 GB per
             # four images at config 2): drop them before the new plan is allocated (round-5 advisor finding)
-            cache = self.__dict__.get("_chains", {})
             stale = [k for k, ch in cache.items() if getattr(ch, "slot_chain", False) and k[0] == id(model)
                      and k[1][1:] == tuple(x_start.shape[1:]) and k[1][0] != G]
             if stale:
@@ -1232,38 +1237,41 @@ class GaussianDiffusionModel:
                 torch.cuda.synchronize(x_start.device)
                 for key in stale:
                     cache.pop(key)
-            while True:
-                try:
+            try:
+                with torch.no_grad():
                     chain = self._chain_for(model, x_start[:1].expand(G, -1, -1, -1).contiguous(), 1, "gauss", stream_base=base,
                                             sampler=sampler)
-                    break
-                except torch.cuda.OutOfMemoryError:
-                    if not auto or G == 1:
-                        raise
-                    G = max(1, G // 2)                                   # the estimate was too optimistic: fewer slots, new schedule
-                    torch.cuda.empty_cache()
-                    makespan, place = plan_chain_slots([steps[c] for c in live], G)
-                    self.last_chain_schedule.update(slots=G, steps=makespan, place={live[i]: place[i] for i in range(len(live))})
-                    refill, harvest, last_busy = {}, {}, [0] * G
-                    for i, (slot, start) in enumerate(place):
-                        c = live[i]
-                        refill.setdefault(start, []).append((slot, c))
-                        harvest.setdefault(start + steps[c] - 1, []).append((slot, c))
-                        last_busy[slot] = max(last_busy[slot], start + steps[c])
-            chain.slot_chain = True
+                    chain.slot_chain = True
+                    if chain.hip_model:
+                        model._plan_for(G, x_start.shape[2], x_start.device)     # the large allocation: not left to the first step
+                break
+            except torch.cuda.OutOfMemoryError:
+                if not auto or G == 1:
+                    raise
+            # the estimate was too optimistic: halve the slots (the next turn drops the chain just kept as superseded).  Here, outside
+            # the `except` block, the traceback no longer pins the failed allocations: emptying the cache returns them to the device
+            torch.cuda.empty_cache()
+            G //= 2
+        makespan, place = plan_chain_slots(live_steps, G)
+        self.last_chain_schedule = {"slots": G, "steps": makespan, "chain_steps": sum(steps), "place": dict(zip(live, place))}
+        if not live:
+            return out
+        refill, harvest, last_busy = slot_events(place, live_steps, G)
+        with torch.no_grad():
             chain.remaining = makespan
             for slot in range(G):
-                if last_busy[slot] == 0:                                # fewer chains than slots cannot happen (G <= n); kept for safety
+                if last_busy[slot] == 0:                                # no chain (n counts the zero-length ones): a valid timestep to idle on
                     chain.t[slot:slot + 1].fill_(makespan - 1)
             for k in range(makespan):
-                for slot, c in refill.get(k, ()):
+                for slot, i in refill.get(k, ()):
+                    c = live[i]
                     chain.x[slot].copy_(x_start[c])
                     chain.t[slot:slot + 1].fill_(lens[c] - 1)
                     if seeded:
                         chain.streams[slot:slot + 1].fill_(philox.signed32(base + c))
                 chain.step()
-                for slot, c in harvest.get(k, ()):
-                    out[c].copy_(chain.x[slot])
+                for slot, i in harvest.get(k, ()):
+                    out[live[i]].copy_(chain.x[slot])
                     if last_busy[slot] == k + 1 and k + 1 < makespan and sampler is None:
                         # nothing left for this slot: it idles on its last image with a timestep that stays >= 0 to the end
                         # (a strided chain's advance floors t at 0 by itself)
@@ -1271,33 +1279,24 @@ class GaussianDiffusionModel:
             chain.finish()
         return out
 
-    def _detection_record(self, x_0, output, mask, extra):
-        from . import metrics
-        maps, counts = metrics.anomaly_maps(x_0, output, mask, threshold=0.5)
-        rec = dict(extra)
-        rec.update(output=output, mean=maps["mean"], mse=maps["mse_img"], threshold=maps["thr_img"],
-                   counts=counts)
-        rec["auc"] = rec["auc_status"] = None                       # filled by _attach_auc when there is a mask
-        rec["ap"] = rec["best_dice"] = rec["best_threshold"] = None
-        rec["ssim"] = None                                          # filled by _attach_ssim
-        return rec, maps
-
     @staticmethod
-    def _attach_auc(records, sqerrs, mask):
-        """detection.py:230-231 for every setting of a sweep in ONE batched launch: `auc` (fp64 device scalar; NaN when the mask has
-        one class only or when `auc_status`, the kernel's status word, is non-zero) per record, and from the same launch and the
-        same sort `ap` (average precision), `best_dice` (the largest Dice over all thresholds; both fp64 device scalars, NaN when
-        the mask has no positive or the status is non-zero) and `best_threshold` (fp32 device scalar: the highest threshold that
-        reaches it).  Never raises, never synchronises."""
-        if mask is None or not records:
-            return
+    def _scatter_scores(records, mask, scores, suffix):
+        """ONE batched ROC launch (metrics.curve_scores) on `scores` [R, ...], one segment per record -> the [R] status words, and in
+        the records `auc`, `ap`, `best_dice` (fp64 device scalars; NaN when the class they need is empty or the status is non-zero)
+        and `best_threshold` (fp32: the highest threshold that reaches the best Dice), each + suffix.  Never raises or synchronises."""
         from . import metrics
-        o = metrics._roc_launch(mask, torch.stack([s.reshape(-1) for s in sqerrs]), batched=True, curve=False, pr=True)
-        status = o["status"]
-        auc, ap, best = (metrics._nan_where_status(o[k], status) for k in ("auc", "ap", "best_dice"))
+        o = metrics.curve_scores(mask, scores, batched=True)
         for j, rec in enumerate(records):
-            rec["auc"], rec["auc_status"] = auc[j], status[j]
-            rec["ap"], rec["best_dice"], rec["best_threshold"] = ap[j], best[j], o["best_threshold"][j]
+            for k in ("auc", "ap", "best_dice", "best_threshold"):
+                rec[k + suffix] = o[k][j]
+        return o["status"]
+
+    def _attach_auc(self, records, sqerrs, mask):
+        """detection.py:230-231 for every setting of a sweep, with `ap` / `best_dice` from the same launch (`_scatter_scores`) and `auc_status`."""
+        if mask is not None and records:
+            status = self._scatter_scores(records, mask, torch.stack([s.reshape(-1) for s in sqerrs]), "")
+            for j, rec in enumerate(records):
+                rec["auc_status"] = status[j]
 
     @staticmethod
     def _attach_ssim(records, x_0):
@@ -1328,12 +1327,24 @@ class GaussianDiffusionModel:
         for j, rec in enumerate(records):
             rec["sqerr_pp"] = filtered[j]
             rec["auc_pp"] = rec["ap_pp"] = rec["best_dice_pp"] = rec["best_threshold_pp"] = None
-        if mask is None:
-            return
-        o = metrics._roc_launch(mask, filtered.reshape(len(records), -1), batched=True, curve=False, pr=True)
-        auc, ap, best = (metrics._nan_where_status(o[k], o["status"]) for k in ("auc", "ap", "best_dice"))
-        for j, rec in enumerate(records):
-            rec["auc_pp"], rec["ap_pp"], rec["best_dice_pp"], rec["best_threshold_pp"] = auc[j], ap[j], best[j], o["best_threshold"][j]
+        if mask is not None:
+            self._scatter_scores(records, mask, filtered.reshape(len(records), -1), "_pp")
+
+    def _score_settings(self, settings, outputs, total_avg, x_0, mask):
+        """The end of detection_A / detection_B: settings[j] (the keys that name a setting) owns the `total_avg` chains
+        outputs[j * total_avg:(j + 1) * total_avg]; one record per setting, in that order, scored -> `self.last_detection`.  A
+        score stays None where nothing fills it (`_attach_auc` needs a mask, `_attach_ssim` images of the window's size)."""
+        from . import metrics
+        self.last_detection, sqerrs = [], []
+        for j, extra in enumerate(settings):
+            output = outputs[j * total_avg:(j + 1) * total_avg].clone()
+            maps, counts = metrics.anomaly_maps(x_0, output, mask, threshold=0.5)
+            self.last_detection.append(dict(extra, output=output, mean=maps["mean"], mse=maps["mse_img"], threshold=maps["thr_img"], counts=counts,
+                                            auc=None, auc_status=None, ap=None, best_dice=None, best_threshold=None, ssim=None))
+            sqerrs.append(maps["sqerr"])
+        self._attach_auc(self.last_detection, sqerrs, mask)
+        self._attach_ssim(self.last_detection, x_0)
+        self._attach_postprocessed(self.last_detection, sqerrs, mask, x_0)
 
     def detection_A(self, model, x_0, args, file, mask, total_avg=2):
         """GaussianDiffusion.py:480-529: simplex frequencies 2^7..2^1 x t_distance 50..0.6T step 50, `total_avg` chains each -- all
@@ -1349,14 +1360,7 @@ class GaussianDiffusionModel:
                 dists += [t_distance] * total_avg
                 noise += self._forward_noise(x_0, t_distance, total_avg)
         outputs = self._run_chains(model, x_0, dists, torch.cat(noise) if noise else None)
-        self.last_detection, sqerrs = [], []
-        for j, extra in enumerate(settings):
-            rec, maps = self._detection_record(x_0, outputs[j * total_avg:(j + 1) * total_avg].clone(), mask, extra)
-            self.last_detection.append(rec)
-            sqerrs.append(maps["sqerr"])
-        self._attach_auc(self.last_detection, sqerrs, mask)
-        self._attach_ssim(self.last_detection, x_0)
-        self._attach_postprocessed(self.last_detection, sqerrs, mask, x_0)
+        self._score_settings(settings, outputs, total_avg, x_0, mask)
 
     def detection_B(self, model, x_0, args, file, mask, denoise_fn="gauss", total_avg=5):
         """GaussianDiffusion.py:531-594: t_distance 50..end step 50 with gaussian or 6-octave simplex forward noise,
@@ -1376,14 +1380,5 @@ class GaussianDiffusionModel:
             dists += [t_distance] * total_avg
             noise += self._forward_noise(x_0, t_distance, total_avg)
         outputs = self._run_chains(model, x_0, dists, torch.cat(noise) if noise else None)
-        dice_coeff = []
-        self.last_detection, sqerrs = [], []
-        for j, t_distance in enumerate(settings):
-            rec, maps = self._detection_record(x_0, outputs[j * total_avg:(j + 1) * total_avg].clone(), mask, {"t_distance": t_distance})
-            self.last_detection.append(rec)
-            sqerrs.append(maps["sqerr"])
-            dice_coeff.append(None)                                 # evaluation.heatmap() returns None (evaluation.py:12-22)
-        self._attach_auc(self.last_detection, sqerrs, mask)
-        self._attach_ssim(self.last_detection, x_0)
-        self._attach_postprocessed(self.last_detection, sqerrs, mask, x_0)
-        return dice_coeff
+        self._score_settings([{"t_distance": t_distance} for t_distance in settings], outputs, total_avg, x_0, mask)
+        return [None] * len(settings)                               # evaluation.heatmap() returns None (evaluation.py:12-22)

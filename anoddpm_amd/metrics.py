@@ -50,7 +50,7 @@ import torch
 from . import _lib
 from ._lib import AnomalyArgs, ComponentsArgs, ErodeArgs, MedianArgs, RocArgs, SsimArgs, check, current_stream, lib
 
-__all__ = ["anomaly_maps", "anomaly_metrics", "roc_auc", "roc_points", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "median_filter", "erode_mask",
+__all__ = ["anomaly_maps", "anomaly_metrics", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "median_filter", "erode_mask",
            "remove_small_components", "PostProcess", "postprocess_maps", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
 
@@ -221,8 +221,14 @@ def roc_points(mask, score, batched=None):
     return res
 
 
-def _nan_where_status(x, status):
-    return torch.where(status != 0, torch.full_like(x, float("nan")), x)
+def curve_scores(mask, score, batched):
+    """Every score of a map from ONE launch and one sort (arguments as `_roc_launch`): a dict of [S] device tensors, no host
+    synchronisation -- `auc`, `ap`, `best_dice` (fp64; NaN where `status`, the kernel's int32 word, is non-zero or the class they
+    need is empty), `best_threshold` (fp32) and `best_counts` (int64 [S, 2]: tp and fp at that threshold)."""
+    o = _roc_launch(mask, score, batched, curve=False, pr=True)
+    out = {k: torch.where(o["status"] != 0, torch.full_like(o[k], float("nan")), o[k]) for k in ("auc", "ap", "best_dice")}
+    out.update(best_threshold=o["best_threshold"], best_counts=o["best_counts"], status=o["status"])
+    return out
 
 
 def average_precision(mask, score, batched=None, return_status=False):
@@ -231,9 +237,8 @@ def average_precision(mask, score, batched=None, return_status=False):
     tensor without a host synchronisation.  NaN where the segment has no positive: sklearn returns 0.0 after a warning there,
     which would silently pull down a mean over slices, most of which have no lesion.  1.0 where it has no negative.  NaN where
     the inputs break the precondition (`return_status=True` also returns the [S] int32 status words)."""
-    o = _roc_launch(mask, score, _is_batched(score, batched), curve=False, pr=True)
-    ap = _nan_where_status(o["ap"], o["status"])
-    return (ap, o["status"]) if return_status else ap
+    o = curve_scores(mask, score, _is_batched(score, batched))
+    return (o["ap"], o["status"]) if return_status else o["ap"]
 
 
 def best_dice(mask, score, batched=None):
@@ -242,9 +247,8 @@ def best_dice(mask, score, batched=None):
     no host synchronisation: `dice` [S] fp64, `threshold` [S] fp32 (the highest one when several reach it), `tp` / `fp` [S] int64
     at that threshold (precision, recall and IoU there follow from them and P), `status` [S] int32.  `dice` is NaN where the
     segment has no positive and where the status is non-zero."""
-    o = _roc_launch(mask, score, _is_batched(score, batched), curve=False, pr=True)
-    return {"dice": _nan_where_status(o["best_dice"], o["status"]), "threshold": o["best_threshold"],
-            "tp": o["best_counts"][:, 0], "fp": o["best_counts"][:, 1], "status": o["status"]}
+    o = curve_scores(mask, score, _is_batched(score, batched))
+    return {"dice": o["best_dice"], "threshold": o["best_threshold"], "tp": o["best_counts"][:, 0], "fp": o["best_counts"][:, 1], "status": o["status"]}
 
 
 def pr_points(mask, score, batched=None):
@@ -550,7 +554,7 @@ def anomaly_metrics(real, recon, mask, threshold=0.5, postprocess=None, roi=None
     components below `postprocess.min_size` pixels (`maps["pred_pp"]`), counted by the same pass as `dice` / `precision` /
     `recall`.  The inputs must be `[..., H, W]` images then."""
     maps, counts = anomaly_maps(real, recon, mask, threshold)
-    roc = _roc_launch(mask, maps["sqerr"], batched=False, curve=False, pr=True) if mask is not None else None
+    roc = curve_scores(mask, maps["sqerr"], batched=False) if mask is not None else None
     ss = ssim(real, maps["mean"]) if real.dim() == 4 and min(real.shape[-2:]) >= 7 and real.numel() > 0 else None
     c = counts.cpu()
     r = {k: float(v) for k, v in _ratios(c).items() if k != "dice_per_image"}
@@ -558,12 +562,7 @@ def anomaly_metrics(real, recon, mask, threshold=0.5, postprocess=None, roi=None
     mse = float(c[:, 9].sum()) / n_total
     r["mse"] = mse
     r["PSNR"] = float(20.0 * torch.log10(torch.tensor(float(c[:, 10].max())) / torch.sqrt(torch.tensor(mse)))) if mse > 0 else float("inf")
-    r["AUC_status"] = int(roc["status"].cpu()[0]) if roc is not None else 0
-    r["AUC"] = float(roc["auc"].cpu()[0]) if roc is not None and r["AUC_status"] == 0 else float("nan")
-    for key, src in (("AP", "ap"), ("best_dice", "best_dice"), ("best_threshold", "best_threshold")):
-        r[key] = float(roc[src].cpu()[0]) if roc is not None and r["AUC_status"] == 0 else float("nan")
-    if r["best_dice"] != r["best_dice"]:
-        r["best_threshold"] = float("nan")                           # no positive: no threshold is better than another
+    _curve_floats(r, roc, "")
     r["SSIM"] = float(ss.mean().cpu()) if ss is not None else float("nan")
     r["maps"] = maps
     if postprocess is not None:
@@ -571,22 +570,27 @@ def anomaly_metrics(real, recon, mask, threshold=0.5, postprocess=None, roi=None
     return r
 
 
+def _curve_floats(r, roc, suffix):
+    """`AUC`, `AP`, `best_dice`, `best_threshold` (+ suffix) and `AUC<suffix>_status` of `r` as Python numbers from `roc`, the
+    `curve_scores` of one segment (None without a mask: NaN, status 0)."""
+    st = r["AUC" + suffix + "_status"] = int(roc["status"].cpu()[0]) if roc is not None else 0
+    for key, src in (("AUC", "auc"), ("AP", "ap"), ("best_dice", "best_dice"), ("best_threshold", "best_threshold")):
+        r[key + suffix] = float(roc[src].cpu()[0]) if roc is not None and st == 0 else float("nan")
+    if r["best_dice" + suffix] != r["best_dice" + suffix]:
+        r["best_threshold" + suffix] = float("nan")                  # no positive: no threshold is better than another
+
+
 def _add_postprocessed(r, real, mask, threshold, pp, roi):
     """The `_pp` keys of `anomaly_metrics`."""
     maps = r["maps"]
     sq = postprocess_maps(maps["sqerr"], pp, real=real, roi=roi)
     pred, _ = _small_components(sq, float(threshold), pp.min_size, pp.connectivity)
-    roc = _roc_launch(mask, sq, batched=False, curve=False, pr=True) if mask is not None else None
+    roc = curve_scores(mask, sq, batched=False) if mask is not None else None
     _, counts = anomaly_maps(torch.zeros_like(pred), pred, mask, threshold=0.5, want=())    # (pred - 0)^2 > 0.5 is pred itself
     ratios = _ratios(counts.cpu())
     for key in ("dice", "precision", "recall"):
         r[key + "_pp"] = float(ratios[key])
-    st = int(roc["status"].cpu()[0]) if roc is not None else 0
-    r["AUC_pp_status"] = st
-    for key, src in (("AUC_pp", "auc"), ("AP_pp", "ap"), ("best_dice_pp", "best_dice"), ("best_threshold_pp", "best_threshold")):
-        r[key] = float(roc[src].cpu()[0]) if roc is not None and st == 0 else float("nan")
-    if r["best_dice_pp"] != r["best_dice_pp"]:
-        r["best_threshold_pp"] = float("nan")
+    _curve_floats(r, roc, "_pp")
     maps["sqerr_pp"], maps["pred_pp"] = sq, pred
 
 

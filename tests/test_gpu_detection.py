@@ -292,6 +292,49 @@ def test_out_of_range_t_distance_raises_like_extract():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# The automatic slot count is an estimate: when the plan for it does not fit, the sweep halves it and goes on.  The plan build is
+# made to fail on the host (a Python exception from a patched `_plan_for`: nothing is allocated, the device is not involved).
+
+OOM_DISTS = [3, 4, 5, 6] * 5                                        # 20 chains: the automatic choice is above 8 slots
+
+
+def _oom_sweep(monkeypatch, slots, fail_first_plan):
+    """One seeded `_run_chains` sweep of OOM_DISTS on a fresh tiny model -> (d, images, batch sizes `_plan_for` was asked for)."""
+    _, m, d = tiny()
+    d.seed_gauss(11)
+    real, asked = m._plan_for, []
+
+    def plan_for(B, S, device):
+        asked.append(B)
+        if fail_first_plan and len(asked) == 1:
+            raise torch.cuda.OutOfMemoryError("simulated")
+        return real(B, S, device)
+    monkeypatch.setattr(m, "_plan_for", plan_for)
+    torch.manual_seed(3)
+    x_0 = torch.rand(1, 1, 32, 32, device=DEV) * 2 - 1
+    return d, d._run_chains(m, x_0, OOM_DISTS, None, slots=slots), asked
+
+
+def test_automatic_slot_count_is_halved_when_the_plan_does_not_fit(monkeypatch):
+    chosen = _oom_sweep(monkeypatch, None, False)[0].last_chain_schedule["slots"]
+    assert chosen > 8 and chosen % 2 == 0
+    d, out, asked = _oom_sweep(monkeypatch, None, True)
+    sched = d.last_chain_schedule
+    assert asked[0] == chosen and set(asked[1:]) == {chosen // 2}       # the plan is built where the retry guards it
+    assert sched["slots"] == chosen // 2 and sched["chain_steps"] == sum(OOM_DISTS) and sorted(sched["place"]) == list(range(len(OOM_DISTS)))
+    assert [k[1][0] for k in d._chains] == [chosen // 2]                 # the chain of the abandoned batch size is not kept
+    assert torch.isfinite(out).all()
+    # seeded sweeps are bit-identical at equal slot counts: the retry leaves no trace in the images
+    d2, ref, _ = _oom_sweep(monkeypatch, chosen // 2, False)
+    assert d2.last_chain_schedule == sched and torch.equal(out, ref)
+
+
+def test_explicit_slot_count_propagates_a_failed_plan_build(monkeypatch):
+    with pytest.raises(torch.cuda.OutOfMemoryError):
+        _oom_sweep(monkeypatch, 8, True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # The slot-batched loops against the REFERENCE's serial loops (tests/golden/detection_loops_kat.npz, make_golden.py:
 # gen_detection_loops): the reference ran detection_B / detection_A on CPU with torch.randn_like replaced by a keyed stream
 # (tests/golden/keyed.py: the value depends on (chain in upstream's loop order, t)); here the same keyed values are handed to

@@ -340,3 +340,46 @@ def test_chain_slot_schedule():
         plan_chain_slots([3, 0], 2)
     with pytest.raises(ValueError):
         plan_chain_slots([3], 0)
+
+
+def test_choose_slots_is_the_sweeps_slot_policy():
+    """diffusion.choose_slots: the batch size of every automatic detection call, at the 256^2 / base-128 model's 0.75 GiB per slot:
+    16 / 12 / 8 by the cheapest longest-first schedule among those that fit in half of the free memory, 4 / 2 / 1 below that."""
+    from anoddpm_amd.diffusion import choose_slots
+    GiB = float(2 ** 30)
+    per_slot = 24 * 4 * 128 * 256 * 256
+    free = [float("inf")] + [g * GiB for g in (64, 30, 20, 12, 6, 3, 1.5, 0.1)]
+    det_a = [t for _ in range(7) for t in range(50, 600, 50) for _ in range(2)]
+    sweeps = ((det_a, [16, 16, 16, 12, 8, 4, 2, 1, 1]),                                              # detection_A, T = 1000
+              ([t for t in range(50, 800, 50) for _ in range(5)], [12, 12, 12, 12, 8, 4, 2, 1, 1]),  # detection_B gauss
+              ([t for t in range(50, 600, 50) for _ in range(5)], [16, 16, 16, 12, 8, 4, 2, 1, 1]),  # detection_B octave
+              ([10, 20, 30], [8, 8, 8, 8, 8, 4, 2, 1, 1]), ([5] * 9, [8, 8, 8, 8, 8, 4, 2, 1, 1]),   # the caller clamps to n afterwards
+              ([7] * 13, [8, 8, 8, 8, 8, 4, 2, 1, 1]))
+    assert len(det_a) == 154 and len(sweeps[1][0]) == 75 and len(sweeps[2][0]) == 55
+    for steps, want in sweeps:
+        assert [choose_slots(steps, len(steps), per_slot, f) for f in free] == want, steps[:3]
+    # zero-length chains take no slot time: ignored, whatever their number (n stays the caller's chain count)
+    holes = [s for t in det_a for s in (t, 0)]
+    assert [choose_slots(holes, len(holes), per_slot, f) for f in free] == sweeps[0][1]
+    assert choose_slots([10, 0, 20, 0, 30], 5, per_slot, 20 * GiB) == 8
+    # nothing but zero-length chains: scheduled like one chain of one step
+    for f in free:
+        assert choose_slots([0, 0, 0], 3, per_slot, f) == choose_slots([1], 3, per_slot, f)
+    assert [choose_slots([0, 0, 0], 3, per_slot, f) for f in free] == [8, 8, 8, 8, 8, 4, 2, 1, 1]
+
+
+def test_slot_events_of_a_schedule():
+    """diffusion.slot_events: the refill / harvest tables and the per-slot end the stepping loop reads, from plan_chain_slots."""
+    from anoddpm_amd.diffusion import plan_chain_slots, slot_events
+    for lengths, slots in (([d for d in range(50, 800, 50) for _ in range(5)], 16), ([d for d in range(50, 600, 50) for _ in range(2)] * 7, 16),
+                           ([7, 3, 3, 1], 2), ([5], 4), ([], 3)):
+        _, place = plan_chain_slots(lengths, slots)
+        refill, harvest, last_busy = slot_events(place, lengths, slots)
+        for events, at in ((refill, lambda start, L: start), (harvest, lambda start, L: start + L - 1)):
+            seen = sorted((i, k, slot) for k, ev in events.items() for slot, i in ev)
+            assert seen == [(i, at(start, L), slot) for i, (L, (slot, start)) in enumerate(zip(lengths, place))]     # each chain exactly once
+        ends = [0] * slots
+        for L, (slot, start) in zip(lengths, place):
+            ends[slot] = max(ends[slot], start + L)
+        assert last_busy == ends
+    assert slot_events(plan_chain_slots([5], 4)[1], [5], 4) == ({0: [(0, 0)]}, {4: [(0, 0)]}, [5, 0, 0, 0])     # a slot without a chain: 0
