@@ -3,20 +3,37 @@
 // EMA loop (UNet.py:423-427) and clip_grad_norm_ (diffusion_training.py:104).  HBM-bound:
 // reads p,g,m,v,ema and writes p,m,v,ema = 36 B per parameter.
 #include "common.h"
+#include <math.h>
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void adamw_one(const anoddpm_adamw_args &a, float gs, float bc1, float bc2, float g, float &p, float &m, float &v, float &e)
+// What the kernel reads: the buffers and the step's constants.  The public struct carries the caller's doubles; every derived
+// constant is formed from them in double on the host and rounded to fp32 ONCE (torch.optim.AdamW does the same with its Python
+// doubles).  Formed in fp32 from fp32 hyper-parameters they are 1e-5 off: 1.0f - 0.999f = 0.000999987, 1.0f - powf(0.999f, 2) is
+// 1.95e-5 low, 1.0f - 0.9999f is 1.66e-4 high -- hundreds to thousands of fp32 roundings (tests/test_gpu_optim.py).
+struct adamw_dev {
+    float *p, *m, *v, *ema;
+    const float *g;
+    const float *grad_scale;
+    int64_t n;
+    float decay_mul;                // 1 - lr * weight_decay
+    float beta1, omb1, beta2, omb2; // beta, 1 - beta
+    float sqrt_bc2, eps;            // sqrt(1 - beta2^step)
+    float step_size;                // lr / (1 - beta1^step)
+    float ema_decay, om_decay;      // decay, 1 - decay
+};
+
+__device__ __forceinline__ void adamw_one(const adamw_dev &a, float gs, float g, float &p, float &m, float &v, float &e)
 {
     g *= gs;
-    p = p * (1.0f - a.lr * a.weight_decay);                     // decoupled weight decay
-    m = a.beta1 * m + (1.0f - a.beta1) * g;
-    v = a.beta2 * v + (1.0f - a.beta2) * g * g;
-    const float denom = sqrtf(v) / sqrtf(bc2) + a.eps;
-    p = p - (a.lr / bc1) * (m / denom);
-    e = e * a.ema_decay + p * (1.0f - a.ema_decay);
+    p = p * a.decay_mul;                                        // decoupled weight decay
+    m = a.beta1 * m + a.omb1 * g;
+    v = a.beta2 * v + a.omb2 * g * g;
+    const float denom = sqrtf(v) / a.sqrt_bc2 + a.eps;
+    p = p - a.step_size * (m / denom);
+    e = e * a.ema_decay + p * a.om_decay;
 }
 
 // Shaped after tools/hbm_patterns.hip: a workgroup owns a contiguous range of `per` 16-byte quads (contiguous ownership keeps the
@@ -24,7 +41,7 @@ __device__ __forceinline__ void adamw_one(const anoddpm_adamw_args &a, float gs,
 // 2.6 GB later), ADAM_UNROLL quads per stream in flight.  Per-element arithmetic is unchanged (bit-identical to the scalar form).
 constexpr int ADAM_UNROLL = 2;
 
-__global__ __launch_bounds__(256) void adamw_ema_kernel(anoddpm_adamw_args a, float bc1, float bc2, int64_t per)
+__global__ __launch_bounds__(256) void adamw_ema_kernel(adamw_dev a, int64_t per)
 {
     const float gs = a.grad_scale ? *a.grad_scale : 1.0f;
     const int64_t n4 = a.n >> 2;
@@ -48,7 +65,7 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(anoddpm_adamw_args a, fl
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float pp = p[u][k], mm = m[u][k], vv = v[u][k], ee = e[u][k];
-                adamw_one(a, gs, bc1, bc2, g[u][k], pp, mm, vv, ee);
+                adamw_one(a, gs, g[u][k], pp, mm, vv, ee);
                 p[u][k] = pp; m[u][k] = mm; v[u][k] = vv; e[u][k] = ee;
             }
             P[i + u * 256] = p[u];
@@ -62,7 +79,7 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(anoddpm_adamw_args a, fl
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float pp = p[k], mm = m[k], vv = v[k], ee = e[k];
-            adamw_one(a, gs, bc1, bc2, g[k], pp, mm, vv, ee);
+            adamw_one(a, gs, g[k], pp, mm, vv, ee);
             p[k] = pp; m[k] = mm; v[k] = vv; e[k] = ee;
         }
         P[i] = p; M[i] = m; V[i] = v;
@@ -72,7 +89,7 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(anoddpm_adamw_args a, fl
     if (blockIdx.x == 0 && threadIdx.x < (a.n & 3)) {
         const int64_t t = (n4 << 2) + threadIdx.x;
         float p = a.p[t], m = a.m[t], v = a.v[t], e = a.ema ? a.ema[t] : 0.f;
-        adamw_one(a, gs, bc1, bc2, a.g[t], p, m, v, e);
+        adamw_one(a, gs, a.g[t], p, m, v, e);
         a.p[t] = p; a.m[t] = m; a.v[t] = v;
         if (a.ema) a.ema[t] = e;
     }
@@ -143,17 +160,24 @@ extern "C" int anoddpm_adamw_ema(const anoddpm_adamw_args *a, void *stream)
 {
     ANODDPM_REQUIRE(a && a->p && a->m && a->v && a->g && a->n >= 0 && a->step >= 1, "adamw_ema: bad arguments");
     if (a->n == 0) return ANODDPM_OK;
-    const float bc1 = 1.0f - powf(a->beta1, (float)a->step);
-    const float bc2 = 1.0f - powf(a->beta2, (float)a->step);
     ANODDPM_REQUIRE(((uintptr_t)a->p | (uintptr_t)a->m | (uintptr_t)a->v | (uintptr_t)a->g | (uintptr_t)a->ema) % 16 == 0,
                     "adamw_ema: buffers must be 16-byte aligned");
+    const double bc1 = 1.0 - pow(a->beta1, (double)a->step), bc2 = 1.0 - pow(a->beta2, (double)a->step);
+    adamw_dev k;
+    k.p = a->p; k.m = a->m; k.v = a->v; k.ema = a->ema; k.g = a->g; k.grad_scale = a->grad_scale; k.n = a->n;
+    k.decay_mul = (float)(1.0 - a->lr * a->weight_decay);
+    k.beta1 = (float)a->beta1; k.omb1 = (float)(1.0 - a->beta1);
+    k.beta2 = (float)a->beta2; k.omb2 = (float)(1.0 - a->beta2);
+    k.sqrt_bc2 = (float)sqrt(bc2); k.eps = (float)a->eps;
+    k.step_size = (float)(a->lr / bc1);
+    k.ema_decay = (float)a->ema_decay; k.om_decay = (float)(1.0 - a->ema_decay);
     // ~16 workgroups per CU, each owning a contiguous range of at least one unrolled trip
     const int64_t n4 = a->n >> 2;
     int64_t per = (n4 + 4095) / 4096;
     const int64_t trip = 256 * ADAM_UNROLL;
     per = per < trip ? trip : ((per + trip - 1) / trip) * trip;
     const int64_t blocks = n4 > 0 ? (n4 + per - 1) / per : 1;
-    hipLaunchKernelGGL(adamw_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, anoddpm::as_stream(stream), *a, bc1, bc2, per);
+    hipLaunchKernelGGL(adamw_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, anoddpm::as_stream(stream), k, per);
     return anoddpm::check_launch("adamw_ema");
 }
 

@@ -286,6 +286,7 @@ class FusedAdamWEMA:
         a.ema = self.ema_flat.flat_param.data_ptr() if self.ema_flat is not None else None
         a.grad_scale = scale_ptr
         a.n = f.numel
+        # the caller's doubles, unrounded: the entry point derives 1 - beta, 1 - beta^step, ... in double (an fp32 1 - 0.999 is 1.3e-5 off)
         a.lr, a.beta1, a.beta2, a.eps = self.lr, self.betas[0], self.betas[1], self.eps
         a.weight_decay, a.ema_decay, a.step = self.wd, self.ema_decay, self.step_count
         check(lib().anoddpm_adamw_ema(ctypes.byref(a), stream), "adamw_ema")

@@ -542,13 +542,16 @@ int anoddpm_prof_list(int32_t *codes, float *ms, int32_t cap);
 
 /* Fused AdamW + EMA over a flat fp32 parameter buffer (diffusion_training.py:75,105,107 and
  * UNet.py:423-427): decoupled weight decay, bias-corrected moments, then
- * ema = decay*ema + (1-decay)*p.  grad_scale multiplies g first (global-norm clip factor). */
+ * ema = decay*ema + (1-decay)*p.  grad_scale multiplies g first (global-norm clip factor).
+ * The hyper-parameters are doubles: the constants the kernel multiplies by (1 - beta, 1 - beta^step, 1 - ema_decay,
+ * 1 - lr*weight_decay, lr / (1 - beta1^step)) are formed from them in double and rounded to fp32 once, as torch.optim.AdamW
+ * forms them from its Python floats. */
 typedef struct {
     float *p, *m, *v, *ema;
     const float *g;
     const float *grad_scale;        /* [dev] fp32 scalar or NULL */
     int64_t n;
-    float lr, beta1, beta2, eps, weight_decay, ema_decay;
+    double lr, beta1, beta2, eps, weight_decay, ema_decay;
     int32_t step;                   /* 1-based */
 } anoddpm_adamw_args;
 

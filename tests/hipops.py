@@ -415,3 +415,32 @@ def gn_silu_backward(srcs, da, gamma, beta, mean, rstd, *, act=1, a_mode=0, acc_
     check(lib().anoddpm_gn_silu_backward(ctypes.byref(st), current_stream()), "gn_silu_backward")
     torch.cuda.synchronize()
     return dx, dgamma, dbeta
+
+
+def _addr(x):
+    """A device address from a tensor, a raw integer address (an offset pointer of an argument check) or None."""
+    return x if x is None or isinstance(x, int) else x.data_ptr()
+
+
+def adamw_ema(p, m, v, g, ema=None, grad_scale=None, *, n, step, lr, betas, eps, wd, decay, raw=False):
+    """anoddpm_adamw_ema in place on the first n elements.  p, m, v, g, ema, grad_scale: fp32 cuda tensors, raw addresses or None.
+    raw: return the entry point's status instead of raising on an error."""
+    from anoddpm_amd._lib import AdamwArgs
+    a = AdamwArgs()
+    a.p, a.m, a.v, a.g, a.ema, a.grad_scale = _addr(p), _addr(m), _addr(v), _addr(g), _addr(ema), _addr(grad_scale)
+    a.n, a.step = n, step
+    a.lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.ema_decay = lr, betas[0], betas[1], eps, wd, decay
+    rc = lib().anoddpm_adamw_ema(ctypes.byref(a), current_stream())
+    if raw:
+        return rc
+    check(rc, "adamw_ema")
+    torch.cuda.synchronize()
+
+
+def sumsq(g, n, out, workspace, max_norm, raw=False):
+    """anoddpm_sumsq: out[0..2] = {sum of squares, norm, clip factor} of the first n elements of g (workspace: >= 2048 doubles)."""
+    rc = lib().anoddpm_sumsq(_addr(g), n, _addr(out), _addr(workspace), float(max_norm), current_stream())
+    if raw:
+        return rc
+    check(rc, "sumsq")
+    torch.cuda.synchronize()
