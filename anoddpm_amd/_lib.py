@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ANODDPM_LIB_TAG=<tag>: load lib/libanoddpm_hip_<tag>.so instead -- a second build of the same sources with other compiler flags
 # (ANODDPM_BUILD_TAG / ANODDPM_EXTRA_FLAGS of anoddpm_amd.build), for A/B measurements of one gpurun session.  Same ABI, same checks.
 SO_PATH = os.path.join(_HERE, "lib", "libanoddpm_hip%s.so" % ("_" + os.environ["ANODDPM_LIB_TAG"] if os.environ.get("ANODDPM_LIB_TAG") else ""))
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 OP_IGEMM, OP_GN_STATS, OP_SOFTMAX, OP_RESAMPLE, OP_LINEAR, OP_POSEMB, OP_STEM, OP_LAYOUT, OP_CHAN_STATS, OP_GN_FINALIZE, OP_HEAD = range(1, 12)
 (OP_WGRAD3, OP_WGRAD1, OP_GN_BWD, OP_PACK, OP_SOFTMAX_BWD, OP_TRANSPOSE, OP_LINEAR_BWD, OP_STEM_BWD, OP_HEAD_BWD,
@@ -278,6 +278,20 @@ class ComponentsArgs(Structure):
                 ("min_size", c_int32), ("connectivity", c_int32), ("level", c_float)]
 
 
+class ComponentAreasArgs(Structure):
+    _fields_ = [("src", c_void_p), ("area", c_void_p), ("counts", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64),
+                ("src_stride", c_int64), ("S", c_int32), ("H", c_int32), ("W", c_int32), ("connectivity", c_int32), ("level", c_float)]
+
+
+class ProArgs(Structure):
+    _fields_ = [("score", c_void_p), ("area", c_void_p), ("region_counts", c_void_p), ("mask", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_int64),
+                ("aupro", c_void_p), ("counts", c_void_p), ("status", c_void_p),
+                ("curve_fps", c_void_p), ("curve_pro", c_void_p), ("curve_thr", c_void_p), ("curve_len", c_void_p),
+                ("curve_cap", c_int64), ("score_stride", c_int64), ("area_stride", c_int64), ("mask_stride", c_int64),
+                ("limit", c_double), ("S", c_int32), ("planes_per_segment", c_int32), ("H", c_int32), ("W", c_int32)]
+
+
 PHILOX_REVERSE, PHILOX_FORWARD, PHILOX_FILL = 0, 1, 2                                   # the `domain` word of the philox counter
 ANOMALY_NCOUNTS = 12
 ANOMALY_BLOCKS = 64
@@ -292,7 +306,7 @@ _STRUCTS = [SimplexArgs, PUpdateArgs, IgemmArgs, GnArgs, SoftmaxArgs, ResampleAr
             PosembArgs, StemArgs, LayoutArgs, Op, AdamwArgs, ChanStatsArgs, GnFinalizeArgs, HeadArgs, AnomalyArgs, VlbArgs, WgradArgs, GnBwdArgs,
             Wgrad1Args, PackArgs, SoftmaxBwdArgs, TransposeArgs, LinearBwdArgs, StemBwdArgs, HeadBwdArgs, ColsumFoldArgs,
             MriSliceArgs, ResizeArgs, AttentionArgs, PackBatchArgs, LinearBwdBatchArgs, LossArgs, DropoutArgs, RocArgs, SsimArgs,
-            MedianArgs, ErodeArgs, ComponentsArgs]
+            ComponentAreasArgs, ProArgs, MedianArgs, ErodeArgs, ComponentsArgs]
 
 # every symbol include/anoddpm_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -310,6 +324,7 @@ SYMBOLS = [
     "anoddpm_loss_forward", "anoddpm_loss_backward", "anoddpm_dropout", "anoddpm_roc_auc", "anoddpm_roc_workspace_bytes",
     "anoddpm_ssim", "anoddpm_ssim_workspace_bytes",
     "anoddpm_median2d", "anoddpm_erode2d", "anoddpm_small_components", "anoddpm_small_components_workspace_bytes",
+    "anoddpm_component_areas", "anoddpm_pro_auc", "anoddpm_pro_workspace_bytes",
     "anoddpm_philox_fill", "anoddpm_philox_bits_host", "anoddpm_p_sample_update_gauss", "anoddpm_q_sample_gauss",
     "anoddpm_strided_update", "anoddpm_chain_advance_strided",
 ]
@@ -410,6 +425,10 @@ def lib():
     L.anoddpm_small_components.argtypes = [POINTER(ComponentsArgs), c_void_p]
     L.anoddpm_small_components_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
     L.anoddpm_small_components_workspace_bytes.restype = c_int64
+    L.anoddpm_component_areas.argtypes = [POINTER(ComponentAreasArgs), c_void_p]
+    L.anoddpm_pro_auc.argtypes = [POINTER(ProArgs), c_void_p]
+    L.anoddpm_pro_workspace_bytes.argtypes = [c_int32, c_int64]
+    L.anoddpm_pro_workspace_bytes.restype = c_int64
     L.anoddpm_vlb_terms.argtypes = [POINTER(VlbArgs), c_void_p]
     L.anoddpm_dropout.argtypes = [POINTER(DropoutArgs), c_void_p]
     L.anoddpm_loss_forward.argtypes = [POINTER(LossArgs), c_void_p]

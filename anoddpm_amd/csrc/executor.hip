@@ -93,7 +93,7 @@ extern "C" int anoddpm_ablate_build(void)
 #endif
 }
 
-extern "C" int anoddpm_abi_version(void) { return 30; }
+extern "C" int anoddpm_abi_version(void) { return 31; }
 
 extern "C" const char *anoddpm_last_error(void) { return g_err; }
 
@@ -232,9 +232,11 @@ extern "C" int anoddpm_struct_size(int32_t which)
         case 33: return (int)sizeof(anoddpm_dropout_args);
         case 34: return (int)sizeof(anoddpm_roc_args);
         case 35: return (int)sizeof(anoddpm_ssim_args);
-        case 36: return (int)sizeof(anoddpm_median_args);
-        case 37: return (int)sizeof(anoddpm_erode_args);
-        case 38: return (int)sizeof(anoddpm_components_args);
+        case 36: return (int)sizeof(anoddpm_component_areas_args);
+        case 37: return (int)sizeof(anoddpm_pro_args);
+        case 38: return (int)sizeof(anoddpm_median_args);
+        case 39: return (int)sizeof(anoddpm_erode_args);
+        case 40: return (int)sizeof(anoddpm_components_args);
         default: return -1;
     }
 }

@@ -27,6 +27,10 @@
 // A label never grows and always names a pixel of the same component, so a stale read costs a retry, never a wrong answer; no
 // workgroup waits on another, and the launch boundaries are the only ordering between workgroups.  The result is a set and two
 // integers: independent of the order the atomics land in.
+//
+// Component areas (anoddpm_component_areas, the first half of the per-region overlap score of csrc/pro.hip).  The same link,
+// flatten and sizes launches between a clear of its own (one counter per plane instead of two) and a final launch that writes
+// size[root] at every foreground pixel, 0 elsewhere, and counts the roots of each plane.
 #include <math.h>
 #include "common.h"
 
@@ -264,6 +268,34 @@ __global__ __launch_bounds__(THREADS) void cc_filter_kernel(anoddpm_components_a
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- component areas
+__global__ __launch_bounds__(THREADS) void cc_areas_clear_kernel(anoddpm_component_areas_args a, int *label, int *size, int bpp)
+{
+    const int hw = a.H * a.W;
+    const Pixel q = pixel_of(bpp, hw);
+    if (!q.valid) return;
+    label[q.idx] = a.src[q.plane * a.src_stride + q.p] > a.level ? q.idx : -1;
+    size[q.idx] = 0;
+    if (q.p == 0) a.counts[q.plane] = 0;
+}
+
+__global__ __launch_bounds__(THREADS) void cc_areas_kernel(anoddpm_component_areas_args a, const int *__restrict__ label,
+                                                           const int *__restrict__ size, int bpp)
+{
+    __shared__ int s_found;
+    const Pixel q = pixel_of(bpp, a.H * a.W);
+    if (threadIdx.x == 0) s_found = 0;
+    __syncthreads();
+    if (q.valid) {
+        const int root = label[q.idx];
+        a.area[q.idx] = root >= 0 ? size[root] : 0;
+        if (root == q.idx) atomicAdd(&s_found, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_found)
+        atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + q.plane), (unsigned long long)s_found);
+}
+
 // one workgroup per (plane, tile): a 1-D grid
 bool tiles_ok(int32_t S, int32_t H, int32_t W)
 {
@@ -343,4 +375,33 @@ extern "C" int anoddpm_small_components(const anoddpm_components_args *a, void *
     hipLaunchKernelGGL(cc_size_kernel, grid, block, 0, s, *a, label, size, bpp);
     hipLaunchKernelGGL(cc_filter_kernel, grid, block, 0, s, *a, label, size, bpp);
     return check_launch("small_components");
+}
+
+extern "C" int anoddpm_component_areas(const anoddpm_component_areas_args *a, void *stream)
+{
+    using namespace anoddpm;
+    ANODDPM_REQUIRE(a != nullptr, "component_areas: null args");
+    ANODDPM_REQUIRE(a->src && a->area && a->counts && a->workspace, "component_areas: null pointer");
+    const int64_t need = anoddpm_small_components_workspace_bytes(a->S, a->H, a->W);
+    ANODDPM_REQUIRE(need > 0, "component_areas: S, H, W must be >= 1 and S * H * W below 2^31");
+    ANODDPM_REQUIRE(a->connectivity == 1 || a->connectivity == 2, "component_areas: connectivity must be 1 (4 neighbours) or 2 (8 neighbours)");
+    const int64_t hw = (int64_t)a->H * a->W;
+    ANODDPM_REQUIRE(a->S == 1 || a->src_stride >= hw, "component_areas: planes overlap (src_stride < H*W)");
+    ANODDPM_REQUIRE(a->workspace_bytes >= need, "component_areas: workspace too small");
+    int *label = static_cast<int *>(a->workspace);
+    int *size = label + (int64_t)a->S * hw;
+    const int bpp = (int)((hw + THREADS - 1) / THREADS);
+    const dim3 grid((unsigned)((int64_t)a->S * bpp)), block(THREADS);
+    hipStream_t s = as_stream(stream);
+    anoddpm_components_args c = {};                                  // what the shared phases read: H, W, connectivity
+    c.S = a->S;
+    c.H = a->H;
+    c.W = a->W;
+    c.connectivity = a->connectivity;
+    hipLaunchKernelGGL(cc_areas_clear_kernel, grid, block, 0, s, *a, label, size, bpp);
+    hipLaunchKernelGGL(cc_link_kernel, grid, block, 0, s, c, label, bpp);
+    hipLaunchKernelGGL(cc_flatten_kernel, grid, block, 0, s, c, label, bpp);
+    hipLaunchKernelGGL(cc_size_kernel, grid, block, 0, s, c, label, size, bpp);
+    hipLaunchKernelGGL(cc_areas_kernel, grid, block, 0, s, *a, label, size, bpp);
+    return check_launch("component_areas");
 }

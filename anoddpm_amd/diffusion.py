@@ -630,6 +630,9 @@ class GaussianDiffusionModel:
     # like one image or like x_0): see _attach_postprocessed.  Plain attributes: pickled and deep-copied with the instance.
     postprocess = None
     postprocess_roi = None
+    # opt-in per-region overlap score of the detection records: a false-positive-rate limit in (0, 1] (0.3 in the literature); see
+    # _attach_pro.  A plain attribute like `postprocess`.
+    pro_limit = None
     # opt-in strided reverse sampler (StridedSampler; None: the reference's ancestral sampler, and none of the strided code runs).
     # Read by ReverseChain / reverse_chain / forward_backward and the detection loops unless they are handed `sampler=`; also set at
     # construction from ANODDPM_SAMPLER="<stride>[,<eta>]".  A plain attribute like `postprocess`.
@@ -1330,6 +1333,29 @@ class GaussianDiffusionModel:
         if mask is not None:
             self._scatter_scores(records, mask, filtered.reshape(len(records), -1), "_pp")
 
+    def _attach_pro(self, records, sqerrs, mask):
+        """Opt-in (`self.pro_limit`): `aupro`, the area under the per-region overlap curve up to that false-positive rate
+        (metrics.aupro: all planes of a setting's squared-error map one segment, regions with 8 neighbours), and `aupro_pp` on
+        `sqerr_pp` when post-processing is on -- ONE component launch on the mask every setting shares and ONE PRO launch over
+        all maps.  fp64 device scalars, NaN as `auc`; None without a mask.  Without `self.pro_limit` the records keep exactly
+        their keys.  Never synchronises."""
+        if self.pro_limit is None or not records:
+            return
+        from . import metrics
+        pp = "sqerr_pp" in records[0]
+        for rec in records:
+            rec["aupro"] = None
+            if pp:
+                rec["aupro_pp"] = None
+        if mask is None:
+            return
+        maps = list(sqerrs) + ([rec["sqerr_pp"] for rec in records] if pp else [])
+        val = metrics.aupro(mask, torch.stack(maps), limit=self.pro_limit, batched=True)
+        for j, rec in enumerate(records):
+            rec["aupro"] = val[j]
+            if pp:
+                rec["aupro_pp"] = val[len(records) + j]
+
     def _score_settings(self, settings, outputs, total_avg, x_0, mask):
         """The end of detection_A / detection_B: settings[j] (the keys that name a setting) owns the `total_avg` chains
         outputs[j * total_avg:(j + 1) * total_avg]; one record per setting, in that order, scored -> `self.last_detection`.  A
@@ -1345,6 +1371,7 @@ class GaussianDiffusionModel:
         self._attach_auc(self.last_detection, sqerrs, mask)
         self._attach_ssim(self.last_detection, x_0)
         self._attach_postprocessed(self.last_detection, sqerrs, mask, x_0)
+        self._attach_pro(self.last_detection, sqerrs, mask)
 
     def detection_A(self, model, x_0, args, file, mask, total_avg=2):
         """GaussianDiffusion.py:480-529: simplex frequencies 2^7..2^1 x t_distance 50..0.6T step 50, `total_avg` chains each -- all

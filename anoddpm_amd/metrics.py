@@ -40,6 +40,13 @@ on the device (csrc/postproc.hip), batched over all maps of a sweep, bit for bit
 synchronisation.  `PostProcess` holds the settings; `anomaly_metrics(..., postprocess=pp)` and the detection records add `_pp`
 results beside the raw ones.  Everything is opt-in: without it nothing changes.
 
+Per-region overlap (Bergmann et al., "The MVTec Anomaly Detection Dataset", IJCV 2021; the reference has no counterpart).  Every
+score above is pixel-wise, so one large lesion decides it; the PRO curve gives every connected ground-truth region the same weight
+and AUPRO integrates it up to a false-positive rate of 0.3.  `component_areas` (csrc/postproc.hip) gives every mask pixel the size
+of its region, `aupro` sorts `(score, area)` pairs and walks the curve in ONE launch per batch (`anoddpm_pro_auc`, csrc/pro.hip: one
+workgroup per segment, fp64 sums in a fixed order -- same input, same bits), `pro_points` returns the curve, `AUPRO` a Python float.
+`anomaly_metrics_pro(..., pro_limit=0.3)` and `GaussianDiffusionModel.pro_limit` add it to their results; unset, nothing changes.
+
 `anomaly_metrics` is the native entry: everything the metric loop needs from one launch and one 96-byte D2H copy (plus the AUC launch).
 The individual functions accept the reference's arguments; they use the fused pass when handed device tensors of
 the shapes the reference passes and raise `AnoddpmError` otherwise (no CPU path)."""
@@ -48,10 +55,10 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import AnomalyArgs, ComponentsArgs, ErodeArgs, MedianArgs, RocArgs, SsimArgs, check, current_stream, lib
+from ._lib import AnomalyArgs, ComponentAreasArgs, ComponentsArgs, ErodeArgs, MedianArgs, ProArgs, RocArgs, SsimArgs, check, current_stream, lib
 
-__all__ = ["anomaly_maps", "anomaly_metrics", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "median_filter", "erode_mask",
-           "remove_small_components", "PostProcess", "postprocess_maps", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
+__all__ = ["anomaly_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "median_filter", "erode_mask",
+           "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "aupro", "pro_points", "AUPRO", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
 
 NC = _lib.ANOMALY_NCOUNTS
@@ -538,6 +545,117 @@ def postprocess_maps(sqerr, pp, real=None, roi=None):
     return (out.reshape(S, C, H, W) * roi.reshape(shape)).reshape(out.shape)
 
 
+# ---------------------------------------------------------------------------------- per-region overlap (PRO / AUPRO) on the device
+def _check_connectivity(connectivity, what):
+    if connectivity not in (1, 2):
+        raise ValueError(f"{what}: connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got {connectivity!r}")
+
+
+def component_areas(mask, connectivity=2, level=0.0, batched=None):
+    """The size of every pixel's connected component of `plane > level`, per H x W plane of mask ([S, ..., H, W]; batching as
+    `median_filter`, every dimension before the last two a stack of independent planes): `lab, m = scipy.ndimage.label(plane >
+    level, structure); numpy.bincount(lab.ravel())[lab]` with 0 on the background.  connectivity 2: 8 neighbours (the choice of
+    the PRO score), 1: 4 neighbours.  Returns `(areas, counts)`: int32 shaped like mask and int64 shaped like mask without its
+    last two dimensions (the `m` of every plane), device tensors, no host synchronisation, the same bits every run."""
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError("component_areas: mask must be a device tensor")
+    _check_connectivity(connectivity, "component_areas")
+    S, C, H, W = _planes(mask, _is_batched(mask, batched), "component_areas")
+    xt = _f32c(mask, "component_areas(mask)")
+    dev = xt.device
+    nbytes = lib().anoddpm_small_components_workspace_bytes(S * C, H, W)
+    if nbytes < 0:
+        raise ValueError(f"component_areas: {tuple(mask.shape)} has 2^31 pixels or more")
+    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    areas = torch.empty(tuple(mask.shape), dtype=torch.int32, device=dev)
+    counts = torch.empty(tuple(mask.shape[:-2]), dtype=torch.int64, device=dev)
+    a = ComponentAreasArgs()
+    a.src, a.area, a.counts, a.workspace, a.workspace_bytes = xt.data_ptr(), areas.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes
+    a.src_stride, a.S, a.H, a.W = H * W, S * C, H, W
+    a.connectivity, a.level = int(connectivity), float(level)
+    with torch.cuda.device(dev):
+        check(lib().anoddpm_component_areas(ctypes.byref(a), current_stream()), "component_areas")
+    return areas, counts
+
+
+def _pro_launch(mask, score, limit, connectivity, batched, curve):
+    """One `anoddpm_component_areas` run on the mask and one `anoddpm_pro_auc` launch.  score: [S, ..., H, W] when batched, else
+    one segment [..., H, W]; every plane of `score[s]` belongs to segment s.  mask: like score, or the shape of one segment (its
+    areas are computed once and shared).  Returns a dict of device tensors; nothing is copied to the host."""
+    if not isinstance(score, torch.Tensor) or not isinstance(mask, torch.Tensor):
+        raise TypeError("pro: mask and score must be device tensors")
+    if isinstance(limit, bool) or not 0.0 < float(limit) <= 1.0:
+        raise ValueError(f"pro: limit must be in (0, 1], got {limit!r}")
+    _check_connectivity(connectivity, "pro")
+    S, C, H, W = _planes(score, batched, "pro")
+    n = C * H * W
+    if mask.numel() not in (n, S * n) or tuple(mask.shape[-2:]) != (H, W):
+        raise ValueError(f"pro: mask {tuple(mask.shape)} is neither the shape of score {tuple(score.shape)} nor of one segment")
+    sc, n, s_stride = _segments(score, S, "pro(score)")
+    shared = mask.numel() == n and S > 1
+    mk = _f32c(mask, "pro(mask)")
+    if mk.device != sc.device:
+        raise ValueError("pro: mask and score are on different devices")
+    dev = sc.device
+    nbytes = lib().anoddpm_pro_workspace_bytes(S, n)
+    if nbytes < 0:
+        raise ValueError(f"pro: segment length {n} is outside [1, 2^31)")
+    areas, regions = component_areas(mk.reshape(-1, H, W), connectivity, batched=True)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    out = {"aupro": torch.empty((S,), dtype=torch.float64, device=dev),
+           "counts": torch.empty((S, 4), dtype=torch.int64, device=dev),
+           "status": torch.empty((S,), dtype=torch.int32, device=dev), "n": n}
+    a = ProArgs()
+    a.score, a.area, a.region_counts, a.mask = sc.data_ptr(), areas.data_ptr(), regions.data_ptr(), mk.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    a.aupro, a.counts, a.status = out["aupro"].data_ptr(), out["counts"].data_ptr(), out["status"].data_ptr()
+    a.score_stride, a.area_stride, a.mask_stride = s_stride, (0 if shared else n), (0 if shared else n)
+    a.limit, a.S, a.planes_per_segment, a.H, a.W = float(limit), S, C, H, W
+    if curve:
+        cap = n                                                      # a segment has at most n distinct scores
+        out["fps"] = torch.empty((S, cap), dtype=torch.int32, device=dev)
+        out["pro"] = torch.empty((S, cap), dtype=torch.float64, device=dev)
+        out["thresholds"] = torch.empty((S, cap), dtype=torch.float32, device=dev)
+        out["len"] = torch.empty((S,), dtype=torch.int32, device=dev)
+        a.curve_fps, a.curve_pro, a.curve_thr = out["fps"].data_ptr(), out["pro"].data_ptr(), out["thresholds"].data_ptr()
+        a.curve_len, a.curve_cap = out["len"].data_ptr(), cap
+    with torch.cuda.device(dev):
+        check(lib().anoddpm_pro_auc(ctypes.byref(a), current_stream()), "pro_auc")
+    return out
+
+
+def aupro(mask, score, limit=0.3, connectivity=2, batched=None, return_status=False):
+    """Area under the per-region overlap curve up to the false-positive rate `limit`, divided by `limit` (Bergmann et al., IJCV
+    2021), of every segment: score `[S, ..., H, W]` (`batched`; the default is `roc_auc`'s), all planes of `score[s]` one segment
+    -- several planes pool a data set into one curve -- and mask of the same shape or of one segment's shape (shared by all
+    segments).  A region is a connected component of one mask plane (`connectivity` 2: 8 neighbours); for every distinct score v
+    the curve holds `FPR = fps / N` over the pixels outside every region and `PRO` = the mean over the regions of the fraction
+    of the region with `score >= v`.  Returns an `[S]` fp64 device tensor without a host synchronisation, the same bits every
+    run.  NaN where the mask has no region or no background, and where the inputs break the precondition of `roc_auc`
+    (`return_status=True` also returns the [S] int32 status words)."""
+    o = _pro_launch(mask, score, limit, connectivity, _is_batched(score, batched), curve=False)
+    val = torch.where(o["status"] != 0, torch.full_like(o["aupro"], float("nan")), o["aupro"])
+    return (val, o["status"]) if return_status else val
+
+
+def pro_points(mask, score, limit=0.3, connectivity=2, batched=None):
+    """Every point of the per-region overlap curve, per segment (arguments as `aupro`): one per distinct score, from the highest
+    threshold down and without the `(0, 0)` point in front.  A list of dicts with `fps` (int64 counts; `FPR = fps / N`), `pro`
+    (fp64), `thresholds` (fp32), `K` (regions), `N`, `P` (pixels outside / inside the regions) and `aupro` (Python numbers).
+    Copies to the host; raises ValueError for inputs outside the precondition."""
+    o = _pro_launch(mask, score, limit, connectivity, _is_batched(score, batched), curve=True)
+    status, lens, counts, val = o["status"].cpu(), o["len"].cpu(), o["counts"].cpu(), o["aupro"].cpu()
+    for s, st in enumerate(status.tolist()):
+        if st:
+            raise ValueError(f"pro: segment {s}: {_roc_status_text(st)} (scores must be finite and >= 0, masks 0 or 1)")
+    res = []
+    for s, L in enumerate(lens.tolist()):
+        res.append({"fps": o["fps"][s, :L].cpu().numpy().astype("int64"), "pro": o["pro"][s, :L].cpu().numpy(),
+                    "thresholds": o["thresholds"][s, :L].cpu().numpy(), "K": int(counts[s, 0]), "N": int(counts[s, 1]),
+                    "P": int(counts[s, 2]), "aupro": float(val[s])})
+    return res
+
+
 def anomaly_metrics(real, recon, mask, threshold=0.5, postprocess=None, roi=None):
     """dice / IoU / precision / recall / FPR / mse / PSNR of detection.py:229-250 from one launch, the AUC of
     detection.py:230-231 (the whole batch flattened into one curve, evaluation.py:81) from a second one -- which also gives `AP`
@@ -568,6 +686,38 @@ def anomaly_metrics(real, recon, mask, threshold=0.5, postprocess=None, roi=None
     if postprocess is not None:
         _add_postprocessed(r, real, mask, threshold, postprocess, roi)
     return r
+
+
+def anomaly_metrics_pro(real, recon, mask, threshold=0.5, postprocess=None, roi=None, pro_limit=0.3):
+    """`anomaly_metrics` with the per-region overlap score beside its results -- a function of its own, so that `anomaly_metrics`
+    keeps its signature, its keys and its launches.  `pro_limit` (a false-positive rate in (0, 1], 0.3 in the literature) ADDS
+    `AUPRO` (`aupro` of the whole batch pooled into one curve, as `AUC` is), `AUPRO_regions` (the mask's connected regions, 8
+    neighbours) and `AUPRO_status`, and with `postprocess` also `AUPRO_pp` on the filtered map, all from one component run on
+    the mask and one PRO launch; NaN as `AUC`.  The inputs must be `[..., H, W]` images.  `pro_limit=None`: exactly
+    `anomaly_metrics(...)`, no key and no launch more."""
+    r = anomaly_metrics(real, recon, mask, threshold, postprocess, roi)
+    if pro_limit is not None:
+        _add_pro(r, mask, pro_limit)
+    return r
+
+
+def _add_pro(r, mask, limit):
+    """The `AUPRO` keys of `anomaly_metrics_pro`: one launch over the raw and, when it exists, the filtered map (one shared mask)."""
+    maps = r["maps"]
+    names = ["AUPRO"] + (["AUPRO_pp"] if "sqerr_pp" in maps else [])
+    r["AUPRO_regions"], r["AUPRO_status"] = 0, 0
+    for k in names:
+        r[k] = float("nan")
+    if mask is None:
+        return
+    sq = maps["sqerr"]
+    scores = torch.stack([sq, maps["sqerr_pp"].reshape(sq.shape)]) if len(names) == 2 else sq.unsqueeze(0)
+    o = _pro_launch(mask, scores, limit, 2, batched=True, curve=False)
+    status, counts, val = o["status"].cpu(), o["counts"].cpu(), o["aupro"].cpu()
+    r["AUPRO_regions"], r["AUPRO_status"] = int(counts[0, 0]), int(status[0])
+    for j, k in enumerate(names):
+        if int(status[j]) == 0:
+            r[k] = float(val[j])
 
 
 def _curve_floats(r, roc, suffix):
@@ -709,6 +859,14 @@ def PR_curve(real_mask, square_error):
     if isinstance(real_mask, torch.Tensor):
         return precision_recall_curve(real_mask.detach().cpu().numpy().flatten(), square_error.detach().cpu().numpy().flatten())
     return precision_recall_curve(real_mask.flatten(), square_error.flatten())
+
+
+def AUPRO(real_mask, square_error, limit=0.3):
+    """Area under the per-region overlap curve of the mask's connected regions (8 neighbours) up to the false-positive rate
+    `limit`, normalised to [0, 1] (Bergmann et al., IJCV 2021), as a Python float: `aupro` with all planes of the inputs pooled
+    into one curve.  NaN without a region or without background; ValueError for inputs outside the precondition of `ROC_AUC`.
+    Device tensors only: the reference has no host implementation to fall back to."""
+    return pro_points(real_mask, square_error, limit=limit, batched=False)[0]["aupro"]
 
 
 def AUC_score(fpr, tpr):

@@ -687,6 +687,80 @@ typedef struct anoddpm_ssim_args {
 int anoddpm_ssim(const anoddpm_ssim_args *a, void *stream);
 int64_t anoddpm_ssim_workspace_bytes(int32_t S, int32_t C, int32_t H, int32_t W);   /* HOST function; -1 for a dimension < 1 or S*C*tiles >= 2^31 */
 
+/* ------------------------------------------------------------------ per-region overlap (PRO) curve and AUPRO of anomaly maps
+ * The localisation score of Bergmann et al., "The MVTec Anomaly Detection Dataset", IJCV 2021: every connected ground-truth
+ * region counts the same whatever its size, and the curve is integrated up to a false-positive rate `limit` (0.3 there).  The
+ * reference has no counterpart.  Two entry points: the areas of the mask's regions, then the sort and the curve.
+ *
+ * anoddpm_component_areas: area[p] = pixel count of the connected component of (plane > level) that holds pixel p, 0 on the
+ *   background -- numpy.bincount(lab.ravel())[lab] with lab, m = scipy.ndimage.label(plane > level, structure) and area 0 where
+ *   lab == 0; counts[p] = m.  S planes of H x W at src + p * src_stride; connectivity 1: 4 neighbours, 2: 8 neighbours (the
+ *   published choice).  The union-find of anoddpm_small_components (link, flatten, sizes) between a clear and a final launch
+ *   of its own: five launches.  Integers only: independent of the order the atomics land in, same bits every run.
+ *   workspace  [dev] anoddpm_small_components_workspace_bytes(S, H, W) bytes (declared with the post-processing entry points
+ *              below, like anoddpm_small_components)
+ *
+ * anoddpm_pro_auc: S segments of m = planes_per_segment planes of H x W (n = m*H*W < 2^31 elements; m > 1 pools a data set
+ *   into one curve).  A region is a component of one plane; components never link across planes.  With
+ *     K = regions of the segment's planes, P = pixels inside a region (area != 0), N = n - P,
+ *   the curve has one point per distinct score v, from the highest down, for the prediction score >= v:
+ *     fps(v) = negatives predicted (an integer), FPR(v) = fps(v) / N (one fp64 division),
+ *     PRO(v) = min(1, (sum over positives p with score(p) >= v of 1 / area(p)) / K)  -- the mean over the regions of the fraction
+ *              of the region that is predicted; the clamp only removes an excess of an ulp.
+ *   aupro[s] = the trapezoid area under the polyline (0, 0), (FPR, PRO)... for FPR <= limit, the segment that crosses the limit
+ *   cut there by linear interpolation (a point exactly at the limit needs none), divided by limit.  NaN when K == 0 or N == 0.
+ *   The sums of 1 / area are formed by a workgroup-wide fp64 scan in sorted order and the integral by a fixed-order sum: no
+ *   atomics on floating-point values, same input, same bits, whatever else the launch holds.
+ *   score      fp32, finite and >= 0 (-0.0 counts as +0.0), segment s at score + s * score_stride (>= n)
+ *   area       int32 from anoddpm_component_areas, segment s at area + s * area_stride; area_stride 0 = one mask shared by
+ *              every segment (a sweep's maps share their mask: its areas are computed once)
+ *   region_counts  int64 per plane from anoddpm_component_areas: planes s*m ... s*m + m-1 belong to segment s (0 ... m-1 for
+ *              every segment when area_stride is 0); K is folded from them inside the launch
+ *   mask       optional: the fp32 mask the areas came from, at mask + s * mask_stride (0 = shared), only checked: a value other
+ *              than 0 / 1 sets ANODDPM_ROC_BAD_MASK.  Scores that break the precondition set ANODDPM_ROC_NAN / _INF /
+ *              _NEGATIVE in status[s]; the other outputs of such a segment are not meaningful, other segments are untouched
+ *   counts[s]  {K, N, P, number of distinct scores}
+ *   curve_*    optional (all four or none): every point of the curve without the (0, 0) point: curve_fps [S][curve_cap] int32,
+ *              curve_pro [S][curve_cap] fp64, curve_thr [S][curve_cap] fp32, curve_len[s]; more than curve_cap points: the
+ *              first curve_cap, the full count and ANODDPM_ROC_CURVE_TRUNCATED, as for anoddpm_roc_auc
+ *   workspace  [dev] anoddpm_pro_workspace_bytes(S, n) bytes (keys and areas twice, one fp64 per curve point)
+ * One workgroup per segment, one launch, no allocation, no host synchronisation: capturable in a hipGraph. */
+typedef struct anoddpm_component_areas_args {
+    const float *src;               /* [dev] */
+    int32_t *area;                  /* [dev] [S][H][W] */
+    int64_t *counts;                /* [dev] [S] */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    int64_t src_stride;
+    int32_t S, H, W;
+    int32_t connectivity;
+    float level;
+} anoddpm_component_areas_args;
+
+typedef struct anoddpm_pro_args {
+    const float *score;             /* [dev] */
+    const int32_t *area;            /* [dev] */
+    const int64_t *region_counts;   /* [dev] [S * planes_per_segment], or [planes_per_segment] when area_stride == 0 */
+    const float *mask;              /* [dev] or NULL */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    double *aupro;                  /* [dev] [S] */
+    int64_t *counts;                /* [dev] [S][4] */
+    int32_t *status;                /* [dev] [S] */
+    int32_t *curve_fps;             /* [dev] [S][curve_cap] or NULL */
+    double *curve_pro;              /* [dev] [S][curve_cap] or NULL */
+    float *curve_thr;               /* [dev] [S][curve_cap] or NULL */
+    int32_t *curve_len;             /* [dev] [S] or NULL */
+    int64_t curve_cap;
+    int64_t score_stride, area_stride, mask_stride;
+    double limit;                   /* 0 < limit <= 1 */
+    int32_t S, planes_per_segment, H, W;
+} anoddpm_pro_args;
+
+int anoddpm_component_areas(const anoddpm_component_areas_args *a, void *stream);
+int anoddpm_pro_auc(const anoddpm_pro_args *a, void *stream);
+int64_t anoddpm_pro_workspace_bytes(int32_t S, int64_t n);   /* HOST function; -1 for S < 1, n < 1 or n >= 2^31 */
+
 /* ------------------------------------------------------------------ post-processing of anomaly maps before they are scored
  * The three steps published brain-MRI anomaly-segmentation pipelines apply between the squared error and AP / Dice (the
  * reference has no counterpart: it scores the raw map).  All three select or count, so each output equals scipy's bit for bit.
