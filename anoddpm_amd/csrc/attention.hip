@@ -51,16 +51,23 @@ __global__ __launch_bounds__(AT_NT) void attention_kernel(const anoddpm_attentio
 #pragma unroll
         for (int g = 0; g < CHQ; ++g) dst[g] = *reinterpret_cast<const f32x4 *>(kp + g * 16);
     };
+    // ch = 512: four accumulators over interleaved channel groups, added pairwise.  One running sum of 512 products rounds
+    // like eps * 128 steps * |partial sum|: with logits on a common offset of 100 (every product of one sign) that put P at
+    // 3.7e-5 of its maximum, 3.9 times the error of a blocked fp32 sum and 0.97 of the bar of tests/test_gpu_attention.py.
+    constexpr int NACC = CHQ >= 32 ? 4 : 1;
     auto score_tile = [&](const f32x4 (&kk)[CHQ], int jt) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc[NACC];
+#pragma unroll
+        for (int c = 0; c < NACC; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int g = 0; g < CHQ; ++g) {
             const f32x4 qa = *reinterpret_cast<const f32x4 *>(Qs + l16 * QP + g * 16 + kq * 4);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[e], kk[g][e], acc, 0, 0, 0);
+            for (int e = 0; e < 4; ++e) acc[g % NACC] = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[e], kk[g][e], acc[g % NACC], 0, 0, 0);
         }
+        if constexpr (NACC == 4) acc[0] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) S[(kq * 4 + r) * SP + jt * 16 + l16] = acc[r] * a.scale;
+        for (int r = 0; r < 4; ++r) S[(kq * 4 + r) * SP + jt * 16 + l16] = acc[0][r] * a.scale;
     };
     if (wave < nkt) load_k(kb[0], wave);
     __syncthreads();                                                // Q staged

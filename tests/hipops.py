@@ -268,6 +268,21 @@ def attention_fused(qkv, heads, want_probs=False):
     return out, probs
 
 
+def softmax_rows_backward(p, dp):
+    """anoddpm_softmax_rows_backward: dp [..., L] <- p o (dp - rowsum(p o dp)), in place on a guarded copy of dp.  Returns the
+    result and what the launch left of the L NaN floats behind the last row."""
+    from anoddpm_amd._lib import SoftmaxBwdArgs
+    L = p.shape[-1]
+    rows = p.numel() // L
+    buf = torch.full((rows * L + L,), float("nan"), device=p.device)
+    buf[:rows * L] = dp.reshape(-1)
+    st = SoftmaxBwdArgs()
+    st.p, st.dp, st.rows, st.L = p.data_ptr(), buf.data_ptr(), rows, L
+    check(lib().anoddpm_softmax_rows_backward(ctypes.byref(st), current_stream()), "softmax_rows_backward")
+    torch.cuda.synchronize()
+    return buf[:rows * L].reshape(p.shape), buf[rows * L:]
+
+
 def resample(x, mode, gn=None):
     """x NHWC.  mode 1 nearest x2, 2 average 2x2; with gn = (scale, shift) [B][C] mode 2 also returns the pooled ACTIVATED tensor."""
     B, H, W, C = x.shape
