@@ -336,6 +336,10 @@ __global__ void chain_advance_strided_kernel(int64_t *t, int B, int32_t *step, c
 // means are fp64 partial sums folded in a fixed order.
 constexpr int VLB_BLOCKS = 64;
 
+// torch.clamp(x, -1, 1): a NaN stays a NaN (fminf / fmaxf return the other operand, which would turn the NaN of an out-of-range
+// t, or of a NaN model output, into -1 and a finite term).
+__device__ __forceinline__ float clamp_unit(float x) { return x != x ? x : fminf(fmaxf(x, -1.0f), 1.0f); }
+
 __device__ __forceinline__ float approx_cdf(float x)
 {
     // 0.5 * (1 + tanh(sqrt(2/pi) * (x + 0.044715 * x^3)))          GaussianDiffusion.py:56-61
@@ -361,7 +365,7 @@ __global__ __launch_bounds__(256) void vlb_kernel(anoddpm_vlb_args a, double *__
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
         const float xt = a.xt[base + i], x0 = a.x0[base + i], e = a.eps[base + i];
         float pred = recip * xt - recipm1 * e;                   // :228-230
-        pred = fminf(fmaxf(pred, -1.0f), 1.0f);                  // :287
+        pred = clamp_unit(pred);                                 // :287
         const float mean = coef1 * pred + coef2 * xt;            // :253-267 (model mean)
         const float tmean = coef1 * x0 + coef2 * xt;             // true posterior mean
         float term;
@@ -457,7 +461,7 @@ __device__ __forceinline__ float approx_cdf_grad(float x)
 __device__ __forceinline__ float vlb_element(const VlbCoef &k, float x0, float xt, float e, float *dterm_deps)
 {
     const float raw = k.recip * xt - k.recipm1 * e;
-    const float pred = fminf(fmaxf(raw, -1.0f), 1.0f);
+    const float pred = clamp_unit(raw);
     const float dpred = (raw >= -1.0f && raw <= 1.0f) ? -k.recipm1 : 0.0f;
     const float mean = k.coef1 * pred + k.coef2 * xt;
     float term, dmean;
