@@ -130,6 +130,19 @@ def _roc_status_text(status):
     return ", ".join(t for bit, t in _ROC_STATUS_TEXT if status & bit)
 
 
+def _raise_on_status(prefix, status):
+    """ValueError for the first segment of `status` (host tensor of the kernels' words) that is non-zero."""
+    for s, st in enumerate(status.tolist()):
+        if st:
+            raise ValueError(f"{prefix}: segment {s}: {_roc_status_text(st)} (scores must be finite and >= 0, masks 0 or 1)")
+
+
+def _curve_arrays(o, names, s, L):
+    """The first L points of segment s of the launch's curve arrays `names` on the host; the counts `fps` / `tps` as int64."""
+    arrays = {k: o[k][s, :L].cpu().numpy() for k in names}
+    return {k: a.astype("int64") if k in ("fps", "tps") else a for k, a in arrays.items()}
+
+
 def _segments(x, S, name):
     """x as fp32 rows of a [S, n] view with unit element stride: (tensor that owns the memory, n, row stride in elements)."""
     _lib.require_cuda(x, name)
@@ -217,15 +230,9 @@ def roc_points(mask, score, batched=None):
     `P`, `N`, `twoU` (Python numbers).  Copies to the host; raises ValueError for inputs outside the precondition."""
     o = _roc_launch(mask, score, _is_batched(score, batched), curve=True)
     status, lens, counts, auc = o["status"].cpu(), o["len"].cpu(), o["counts"].cpu(), o["auc"].cpu()
-    for s, st in enumerate(status.tolist()):
-        if st:
-            raise ValueError(f"roc: segment {s}: {_roc_status_text(st)} (scores must be finite and >= 0, masks 0 or 1)")
-    res = []
-    for s, L in enumerate(lens.tolist()):
-        res.append({"fps": o["fps"][s, :L].cpu().numpy().astype("int64"), "tps": o["tps"][s, :L].cpu().numpy().astype("int64"),
-                    "thresholds": o["thresholds"][s, :L].cpu().numpy(), "auc": float(auc[s]),
-                    "P": int(counts[s, 0]), "N": int(counts[s, 1]), "twoU": int(counts[s, 2])})
-    return res
+    _raise_on_status("roc", status)
+    return [dict(_curve_arrays(o, ("fps", "tps", "thresholds"), s, L), auc=float(auc[s]),
+                 P=int(counts[s, 0]), N=int(counts[s, 1]), twoU=int(counts[s, 2])) for s, L in enumerate(lens.tolist())]
 
 
 def curve_scores(mask, score, batched):
@@ -265,17 +272,11 @@ def pr_points(mask, score, batched=None):
     inputs outside the precondition."""
     o = _roc_launch(mask, score, _is_batched(score, batched), curve=True, pr=True)
     status, lens, counts = o["status"].cpu(), o["len"].cpu(), o["counts"].cpu()
-    for s, st in enumerate(status.tolist()):
-        if st:
-            raise ValueError(f"pr: segment {s}: {_roc_status_text(st)} (scores must be finite and >= 0, masks 0 or 1)")
+    _raise_on_status("pr", status)
     ap, bd, bt, bc = o["ap"].cpu(), o["best_dice"].cpu(), o["best_threshold"].cpu(), o["best_counts"].cpu()
-    res = []
-    for s, L in enumerate(lens.tolist()):
-        res.append({"fps": o["fps"][s, :L].cpu().numpy().astype("int64"), "tps": o["tps"][s, :L].cpu().numpy().astype("int64"),
-                    "thresholds": o["thresholds"][s, :L].cpu().numpy(), "P": int(counts[s, 0]), "N": int(counts[s, 1]),
-                    "ap": float(ap[s]), "best_dice": float(bd[s]), "best_threshold": float(bt[s]),
-                    "best_tp": int(bc[s, 0]), "best_fp": int(bc[s, 1])})
-    return res
+    return [dict(_curve_arrays(o, ("fps", "tps", "thresholds"), s, L), P=int(counts[s, 0]), N=int(counts[s, 1]),
+                 ap=float(ap[s]), best_dice=float(bd[s]), best_threshold=float(bt[s]),
+                 best_tp=int(bc[s, 0]), best_fp=int(bc[s, 1])) for s, L in enumerate(lens.tolist())]
 
 
 # ---------------------------------------------------------------------------------- SSIM on the device
@@ -439,14 +440,18 @@ def erode_mask(x, iterations=3, level=0.0):
     return out
 
 
+def _check_connectivity(connectivity, what):
+    if connectivity not in (1, 2):
+        raise ValueError(f"{what}: connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got {connectivity!r}")
+
+
 def _small_components(x, level, min_size, connectivity):
     """One `anoddpm_small_components` run on the planes of x > level: (fp32 0 / 1 map shaped like x, int64 counts [..., 2])."""
     if not isinstance(x, torch.Tensor):
         raise TypeError("remove_small_components: pred must be a device tensor")
     if int(min_size) != min_size or min_size < 0:
         raise ValueError(f"remove_small_components: min_size must be an integer >= 0, got {min_size!r}")
-    if connectivity not in (1, 2):
-        raise ValueError(f"remove_small_components: connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got {connectivity!r}")
+    _check_connectivity(connectivity, "remove_small_components")
     S, C, H, W = _planes(x, False, "remove_small_components")
     xt = _f32c(x, "remove_small_components(pred)")
     dev = xt.device
@@ -546,11 +551,6 @@ def postprocess_maps(sqerr, pp, real=None, roi=None):
 
 
 # ---------------------------------------------------------------------------------- per-region overlap (PRO / AUPRO) on the device
-def _check_connectivity(connectivity, what):
-    if connectivity not in (1, 2):
-        raise ValueError(f"{what}: connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got {connectivity!r}")
-
-
 def component_areas(mask, connectivity=2, level=0.0, batched=None):
     """The size of every pixel's connected component of `plane > level`, per H x W plane of mask ([S, ..., H, W]; batching as
     `median_filter`, every dimension before the last two a stack of independent planes): `lab, m = scipy.ndimage.label(plane >
@@ -645,15 +645,9 @@ def pro_points(mask, score, limit=0.3, connectivity=2, batched=None):
     Copies to the host; raises ValueError for inputs outside the precondition."""
     o = _pro_launch(mask, score, limit, connectivity, _is_batched(score, batched), curve=True)
     status, lens, counts, val = o["status"].cpu(), o["len"].cpu(), o["counts"].cpu(), o["aupro"].cpu()
-    for s, st in enumerate(status.tolist()):
-        if st:
-            raise ValueError(f"pro: segment {s}: {_roc_status_text(st)} (scores must be finite and >= 0, masks 0 or 1)")
-    res = []
-    for s, L in enumerate(lens.tolist()):
-        res.append({"fps": o["fps"][s, :L].cpu().numpy().astype("int64"), "pro": o["pro"][s, :L].cpu().numpy(),
-                    "thresholds": o["thresholds"][s, :L].cpu().numpy(), "K": int(counts[s, 0]), "N": int(counts[s, 1]),
-                    "P": int(counts[s, 2]), "aupro": float(val[s])})
-    return res
+    _raise_on_status("pro", status)
+    return [dict(_curve_arrays(o, ("fps", "pro", "thresholds"), s, L), K=int(counts[s, 0]), N=int(counts[s, 1]),
+                 P=int(counts[s, 2]), aupro=float(val[s])) for s, L in enumerate(lens.tolist())]
 
 
 def anomaly_metrics(real, recon, mask, threshold=0.5, postprocess=None, roi=None):

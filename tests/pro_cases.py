@@ -25,6 +25,7 @@ SMALL = ("plane16", "plane32", "odd40x33", "tiny5x7", "ties4", "ties8", "all_equ
          "border", "pooled4", "mask_all0", "mask_all1", "first_beyond", "at_limit", "limit1", "neg_zero", "shared3")
 LARGE = ("pooled3x64", "map256")                             # the only workload-sized cases: summarised in the fixture
 STATUS = ("nan_score", "negative_score", "bad_mask")
+RAGGED = "ragged50x100"                                      # no fixture entry: the expected values are computed at test time
 
 
 def tolerance(n):
@@ -137,6 +138,18 @@ def make_case(name):
         mask = _blobs(rng, 256, 256, 9, 40)[None]
         mask[0, 100, 200] = 1
         score = _scores(rng, mask)[None]
+    elif name == RAGGED:
+        # n = 5000: the wave chunk is 320, so waves 0 to 14 scatter one full unrolled group of 256 and then ONE slice of 64, and
+        # wave 15 has 200 elements (three slices and a slice of 8).  Regions of 1, 6, 62, 200 and 600 pixels, three of them side
+        # by side in the rows 10 to 24, and eight score levels: equal keys carry different areas on both sides of the chunk
+        # borders there, and only a stable payload order gives the right bits
+        mask = np.zeros((1, 50, 100), np.float32)
+        mask[0, 2, 3] = 1
+        mask[0, 46:48, 90:93] = 1
+        mask[0, 10:41, 60:62] = 1
+        mask[0, 5:45, 5:10] = 1
+        mask[0, 5:25, 20:50] = 1
+        score = _scores(rng, mask, levels=8)[None]
     else:
         raise KeyError(name)
     return np.ascontiguousarray(mask), np.ascontiguousarray(score), limit, conn

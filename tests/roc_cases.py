@@ -61,6 +61,16 @@ def make_case(name):
     return mask, score
 
 
+RAGGED_N = 5000                                              # no fixture entry: the expected values are computed at test time
+
+
+def make_ragged():
+    """(mask, score) of RAGGED_N elements with about 100 distinct scores.  The wave chunk is 320: waves 0 to 14 scatter one full
+    unrolled group of 256 and then ONE slice of 64, wave 15 has 200 elements (three slices and a slice of 8); the ties cross every
+    chunk border (tests/test_roc_reference.py checks that)."""
+    return _variant("round64", np.random.default_rng(400), RAGGED_N, 0.1)
+
+
 def make_batch():
     """([55, 256^2] masks, [55, 256^2] scores): different contents per segment, one all-zero mask."""
     kinds = ("continuous", "round64", "zero_bg", "round1024", "round4")

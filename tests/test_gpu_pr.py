@@ -97,6 +97,13 @@ def test_maps_and_long_segment_match_fixture(kat, name):
     assert rc.sha_curve(prec, rec, thr) == str(kat[f"{name}_curve_sha"][0])
 
 
+def test_chunk_with_a_ragged_second_scatter_group():
+    from anoddpm_amd import metrics
+    mask, score = rc.make_ragged()
+    assert score.size == 5000 and 0 < mask.sum() < mask.size
+    _same_as_restatement(metrics.pr_points(_dev(mask), _dev(score))[0], pc.pr_numpy(mask, score), "ragged")
+
+
 def test_batch_of_55_strided_rows_and_shared_mask(kat):
     from anoddpm_amd import metrics
     masks, scores = rc.make_batch()

@@ -107,6 +107,15 @@ def test_curve_and_aupro_against_exact_and_kernel_order(kat, name):
         assert (pts[0]["K"] == 0) if name == "mask_all0" else (pts[0]["N"] == 0 and pts[0]["K"] == 1)
 
 
+def test_chunk_with_a_ragged_second_scatter_group_keeps_the_payload_order():
+    mask, score, limit, conn = pc.make_case(pc.RAGGED)
+    p = _points(mask, score, limit, conn)[0]
+    pc.check_against_exact(p, pc.pro_exact(mask, score[0], limit, conn), pc.RAGGED)
+    order = pc.pro_fp64(mask, score[0], limit, conn)
+    assert _bits(p["pro"], order["pro"])
+    assert _bits(np.float64(p["aupro"]), np.float64(order["aupro"])), (p["aupro"], order["aupro"])
+
+
 def test_AUPRO_is_a_python_float_of_the_pooled_curve():
     from anoddpm_amd import metrics
     mask, score, limit, conn = pc.make_case("pooled4")

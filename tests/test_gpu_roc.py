@@ -65,6 +65,18 @@ def test_curve_and_auc_match_sklearn_fixture(kat, name):
         assert all(rc.bits_equal(g, w) for g, w in zip(got, (fpr, tpr, thr)))
 
 
+def test_chunk_with_a_ragged_second_scatter_group():
+    from anoddpm_amd import metrics
+    mask, score = rc.make_ragged()
+    assert score.size == 5000 and 0 < mask.sum() < mask.size
+    want = rc.roc_numpy(mask, score)
+    p = metrics.roc_points(_dev(mask), _dev(score))[0]
+    assert (p["P"], p["N"], p["twoU"]) == (want["P"], want["N"], want["twoU"])
+    assert np.array_equal(p["fps"], want["fps"]) and np.array_equal(p["tps"], want["tps"])
+    assert rc.bits_equal(p["thresholds"], want["thresholds"])
+    assert rc.bits_equal(np.float64(p["auc"]), np.float64(want["auc"]))
+
+
 def _check_summary(kat, prefix, j, p, mask, score):
     fpr, tpr, thr = rc.sklearn_triple(p["fps"], p["tps"], p["thresholds"])
     assert (p["P"], p["N"], p["twoU"]) == (int(kat[f"{prefix}_P"][j]), int(kat[f"{prefix}_N"][j]), int(kat[f"{prefix}_twoU"][j]))

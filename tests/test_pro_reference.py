@@ -45,6 +45,24 @@ def test_fp64_restatement_and_published_form_against_exact(kat, name):
         assert np.max(np.abs(pro[1:] - exact["pro"])) <= tol
 
 
+def test_ragged_case_is_what_it_is_for():
+    mask, score, limit, conn = pc.make_case(pc.RAGGED)
+    assert score.shape == (1, 1, 50, 100)
+    exact = pc.pro_exact(mask, score[0], limit, conn)
+    assert (exact["K"], exact["P"]) == (5, 1 + 6 + 62 + 200 + 600) and exact["N"] > 0 and exact["fps"].size <= 8
+    pc.check_against_exact(pc.pro_fp64(mask, score[0], limit, conn), exact, "ragged fp64")
+    # at every border of the 320-element wave chunks in the rows 10 to 24, one key carries several areas on both sides
+    area = pc.regions(mask, conn)[0].reshape(-1)
+    bits = (score.reshape(-1) + np.float32(0)).view(np.uint32)
+
+    def mixed(lo):
+        a, b = area[lo:lo + 320], bits[lo:lo + 320]
+        return {k for k in np.unique(b[a != 0]) if np.unique(a[(b == k) & (a != 0)]).size > 1}
+
+    for border in (1280, 1600, 1920, 2240):
+        assert mixed(border - 320) & mixed(border), border
+
+
 def test_hand_cases(kat):
     aupro = {name: float(kat[f"{name}_aupro"][0]) for name in pc.SMALL}
     assert aupro["first_beyond"] == 0.35 and int(kat["first_beyond_N"][0]) == 56      # the first point (24 / 56, 1) lies beyond 0.3

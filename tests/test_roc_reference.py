@@ -80,6 +80,14 @@ def test_restatement_batch_of_55(kat):
     assert np.isnan(kat["batch_auc"][rc.BATCH_ALL_ZERO_MASK]) and np.isnan(kat["batch_auc"]).sum() == 1
 
 
+def test_ragged_case_is_what_it_is_for():
+    mask, score = rc.make_ragged()
+    assert score.size == rc.RAGGED_N == 5000 and 0 < mask.sum() < mask.size
+    bits = (score + np.float32(0)).view(np.uint32)
+    for border in range(320, 5000, 320):                                 # the 320-element wave chunks: a tie across every border
+        assert np.intersect1d(bits[border - 64:border], bits[border:border + 64]).size, border
+
+
 def test_roc_abi_validation_without_gpu():
     from anoddpm_amd import _lib
     L = _lib.lib()
