@@ -292,6 +292,17 @@ class ProArgs(Structure):
                 ("limit", c_double), ("S", c_int32), ("planes_per_segment", c_int32), ("H", c_int32), ("W", c_int32)]
 
 
+class DistanceArgs(Structure):
+    _fields_ = [("src", c_void_p), ("sq", c_void_p), ("dist", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64),
+                ("src_stride", c_int64), ("S", c_int32), ("H", c_int32), ("W", c_int32), ("level", c_float)]
+
+
+class SurfaceArgs(Structure):
+    _fields_ = [("pred", c_void_p), ("ref", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64),
+                ("counts", c_void_p), ("max2", c_void_p), ("mean", c_void_p), ("p95", c_void_p), ("status", c_void_p),
+                ("pred_stride", c_int64), ("ref_stride", c_int64), ("S", c_int32), ("H", c_int32), ("W", c_int32), ("level", c_float)]
+
+
 PHILOX_REVERSE, PHILOX_FORWARD, PHILOX_FILL = 0, 1, 2                                   # the `domain` word of the philox counter
 ANOMALY_NCOUNTS = 12
 ANOMALY_BLOCKS = 64
@@ -300,13 +311,14 @@ ROC_CURVE_DROP, ROC_CURVE_ALL = 0, 1                                            
 SSIM_UNIFORM, SSIM_GAUSSIAN = 0, 1                                                      # anoddpm_ssim_args.mode
 SSIM_MAX_WIN = 15
 MEDIAN_SIZES = (3, 5, 7)                                                                # anoddpm_median_args.k
+SURFACE_EMPTY_PRED, SURFACE_EMPTY_REF = 1, 2                                            # bits of anoddpm_surface_args.status
 ERODE_MAX = 8                                                                           # anoddpm_erode_args.n
 
 _STRUCTS = [SimplexArgs, PUpdateArgs, IgemmArgs, GnArgs, SoftmaxArgs, ResampleArgs, LinearArgs,
             PosembArgs, StemArgs, LayoutArgs, Op, AdamwArgs, ChanStatsArgs, GnFinalizeArgs, HeadArgs, AnomalyArgs, VlbArgs, WgradArgs, GnBwdArgs,
             Wgrad1Args, PackArgs, SoftmaxBwdArgs, TransposeArgs, LinearBwdArgs, StemBwdArgs, HeadBwdArgs, ColsumFoldArgs,
             MriSliceArgs, ResizeArgs, AttentionArgs, PackBatchArgs, LinearBwdBatchArgs, LossArgs, DropoutArgs, RocArgs, SsimArgs,
-            ComponentAreasArgs, ProArgs, MedianArgs, ErodeArgs, ComponentsArgs]
+            ComponentAreasArgs, ProArgs, DistanceArgs, SurfaceArgs, MedianArgs, ErodeArgs, ComponentsArgs]
 
 # every symbol include/anoddpm_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -325,6 +337,7 @@ SYMBOLS = [
     "anoddpm_ssim", "anoddpm_ssim_workspace_bytes",
     "anoddpm_median2d", "anoddpm_erode2d", "anoddpm_small_components", "anoddpm_small_components_workspace_bytes",
     "anoddpm_component_areas", "anoddpm_pro_auc", "anoddpm_pro_workspace_bytes",
+    "anoddpm_distance_transform", "anoddpm_surface_distance", "anoddpm_surface_workspace_bytes",
     "anoddpm_philox_fill", "anoddpm_philox_bits_host", "anoddpm_p_sample_update_gauss", "anoddpm_q_sample_gauss",
     "anoddpm_strided_update", "anoddpm_chain_advance_strided",
 ]
@@ -429,6 +442,10 @@ def lib():
     L.anoddpm_pro_auc.argtypes = [POINTER(ProArgs), c_void_p]
     L.anoddpm_pro_workspace_bytes.argtypes = [c_int32, c_int64]
     L.anoddpm_pro_workspace_bytes.restype = c_int64
+    L.anoddpm_distance_transform.argtypes = [POINTER(DistanceArgs), c_void_p]
+    L.anoddpm_surface_distance.argtypes = [POINTER(SurfaceArgs), c_void_p]
+    L.anoddpm_surface_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.anoddpm_surface_workspace_bytes.restype = c_int64
     L.anoddpm_vlb_terms.argtypes = [POINTER(VlbArgs), c_void_p]
     L.anoddpm_dropout.argtypes = [POINTER(DropoutArgs), c_void_p]
     L.anoddpm_loss_forward.argtypes = [POINTER(LossArgs), c_void_p]

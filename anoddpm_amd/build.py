@@ -34,6 +34,7 @@ SOURCES = {
     "metrics.hip": ["-ffp-contract=off"],
     "roc.hip": ["-ffp-contract=off"],
     "pro.hip": ["-ffp-contract=off"],
+    "surface.hip": ["-ffp-contract=off"],
     "ssim.hip": ["-ffp-contract=off"],
     "postproc.hip": [],
     "wgrad.hip": [],

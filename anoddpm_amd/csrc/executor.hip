@@ -234,9 +234,11 @@ extern "C" int anoddpm_struct_size(int32_t which)
         case 35: return (int)sizeof(anoddpm_ssim_args);
         case 36: return (int)sizeof(anoddpm_component_areas_args);
         case 37: return (int)sizeof(anoddpm_pro_args);
-        case 38: return (int)sizeof(anoddpm_median_args);
-        case 39: return (int)sizeof(anoddpm_erode_args);
-        case 40: return (int)sizeof(anoddpm_components_args);
+        case 38: return (int)sizeof(anoddpm_distance_args);
+        case 39: return (int)sizeof(anoddpm_surface_args);
+        case 40: return (int)sizeof(anoddpm_median_args);
+        case 41: return (int)sizeof(anoddpm_erode_args);
+        case 42: return (int)sizeof(anoddpm_components_args);
         default: return -1;
     }
 }

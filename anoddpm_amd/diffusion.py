@@ -633,6 +633,9 @@ class GaussianDiffusionModel:
     # opt-in per-region overlap score of the detection records: a false-positive-rate limit in (0, 1] (0.3 in the literature); see
     # _attach_pro.  A plain attribute like `postprocess`.
     pro_limit = None
+    # opt-in boundary distances of the detection records (Hausdorff, HD95, average symmetric surface distance of the thresholded
+    # map against the mask); see _attach_surface.  A plain attribute like `postprocess`.
+    surface_metrics = False
     # opt-in strided reverse sampler (StridedSampler; None: the reference's ancestral sampler, and none of the strided code runs).
     # Read by ReverseChain / reverse_chain / forward_backward and the detection loops unless they are handed `sampler=`; also set at
     # construction from ANODDPM_SAMPLER="<stride>[,<eta>]".  A plain attribute like `postprocess`.
@@ -1356,6 +1359,35 @@ class GaussianDiffusionModel:
             if pp:
                 rec["aupro_pp"] = val[len(records) + j]
 
+    def _attach_surface(self, records, mask):
+        """Opt-in (`self.surface_metrics`, with a mask): `hd`, `hd95`, `assd` of every setting's thresholded map (the record's
+        `threshold` image, > 0) against the mask -- metrics.surface_distance, ONE batched call for all settings, the mask shared
+        when it is one plane -- and with post-processing `hd_pp`, `hd95_pp`, `assd_pp` of the filtered map cut at 0.5 without its
+        components below `postprocess.min_size` pixels, from the same call.  fp64 device scalars: the mean over the record's
+        planes whose two borders exist, NaN when there is none.  Without `self.surface_metrics` or without a mask the records keep
+        exactly their keys.  Never synchronises."""
+        if not self.surface_metrics or mask is None or not records:
+            return
+        from . import metrics
+        R = len(records)
+        preds = [torch.stack([rec["threshold"] for rec in records])]                                        # [R, B, C, H, W], -1 / 1
+        suffixes = [""]
+        if "sqerr_pp" in records[0]:
+            pp = self.postprocess
+            cut, _ = metrics._small_components(torch.stack([rec["sqerr_pp"] for rec in records]), 0.5, pp.min_size, pp.connectivity)
+            preds.append(cut.reshape(preds[0].shape))
+            suffixes.append("_pp")
+        H, W = preds[0].shape[-2:]
+        pred = torch.stack(preds).reshape(len(suffixes) * R, -1, H, W)
+        ref = mask.reshape(-1, H, W)
+        ref = ref[0] if ref.shape[0] == 1 else ref.unsqueeze(0).expand(pred.shape)
+        o = metrics.surface_distance(pred, ref)
+        for k in ("hd", "hd95", "assd"):
+            val = metrics._valid_mean(o[k], o["status"])[0]
+            for i, sfx in enumerate(suffixes):
+                for j, rec in enumerate(records):
+                    rec[k + sfx] = val[i * R + j]
+
     def _score_settings(self, settings, outputs, total_avg, x_0, mask):
         """The end of detection_A / detection_B: settings[j] (the keys that name a setting) owns the `total_avg` chains
         outputs[j * total_avg:(j + 1) * total_avg]; one record per setting, in that order, scored -> `self.last_detection`.  A
@@ -1372,6 +1404,7 @@ class GaussianDiffusionModel:
         self._attach_ssim(self.last_detection, x_0)
         self._attach_postprocessed(self.last_detection, sqerrs, mask, x_0)
         self._attach_pro(self.last_detection, sqerrs, mask)
+        self._attach_surface(self.last_detection, mask)
 
     def detection_A(self, model, x_0, args, file, mask, total_avg=2):
         """GaussianDiffusion.py:480-529: simplex frequencies 2^7..2^1 x t_distance 50..0.6T step 50, `total_avg` chains each -- all

@@ -47,6 +47,15 @@ of its region, `aupro` sorts `(score, area)` pairs and walks the curve in ONE la
 workgroup per segment, fp64 sums in a fixed order -- same input, same bits), `pro_points` returns the curve, `AUPRO` a Python float.
 `anomaly_metrics_pro(..., pro_limit=0.3)` and `GaussianDiffusionModel.pro_limit` add it to their results; unset, nothing changes.
 
+Boundary distances (the reference has no counterpart): how far the predicted outline lies from the true one, which no overlap score
+says.  `distance_transform` is `scipy.ndimage.distance_transform_edt(plane > level)` of every plane of a batch (csrc/surface.hip: a
+sweep down and up every column, then per row the integer minimum over `(x - x')^2 + g^2`), bit for bit; `surface_distance` gives the
+Hausdorff distance, its 95th percentile (`hd95`, medpy's pooled form) and the average symmetric surface distance of every
+prediction against its reference or against one shared reference, in four launches whatever the batch: the order statistics are
+selected on the integer squared distances and the means are fp64 sums in a fixed order, so the same input gives the same bits.
+`HD95` returns a Python float; `anomaly_metrics_surface` and `GaussianDiffusionModel.surface_metrics` add the three to their
+results; unset, nothing changes.  Pixel units only (no `sampling=`), 2-D planes only, one threshold per call.
+
 `anomaly_metrics` is the native entry: everything the metric loop needs from one launch and one 96-byte D2H copy (plus the AUC launch).
 The individual functions accept the reference's arguments; they use the fused pass when handed device tensors of
 the shapes the reference passes and raise `AnoddpmError` otherwise (no CPU path)."""
@@ -55,10 +64,12 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import AnomalyArgs, ComponentAreasArgs, ComponentsArgs, ErodeArgs, MedianArgs, ProArgs, RocArgs, SsimArgs, check, current_stream, lib
+from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs, ErodeArgs, MedianArgs, ProArgs, RocArgs, SsimArgs, SurfaceArgs, check,
+                   current_stream, lib)
 
 __all__ = ["anomaly_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "median_filter", "erode_mask",
-           "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "aupro", "pro_points", "AUPRO", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
+           "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "aupro", "pro_points", "AUPRO", "distance_transform",
+           "surface_distance", "HD95", "anomaly_metrics_surface", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
 
 NC = _lib.ANOMALY_NCOUNTS
@@ -650,6 +661,86 @@ def pro_points(mask, score, limit=0.3, connectivity=2, batched=None):
                  P=int(counts[s, 2]), aupro=float(val[s])) for s, L in enumerate(lens.tolist())]
 
 
+# ---------------------------------------------------------------------------------- distance transform and boundary distances
+def _surface_workspace(S, H, W, what):
+    nbytes = lib().anoddpm_surface_workspace_bytes(S, H, W)
+    if nbytes < 0:
+        raise ValueError(f"{what}: {S} planes of {H} x {W} are too large: (H-1)^2 + (W-1)^2, H*W and 2 * planes * H*W must stay below 2^31")
+    return nbytes
+
+
+def distance_transform(x, level=0.0, squared=False, batched=None):
+    """`scipy.ndimage.distance_transform_edt(plane > level)` of every H x W plane of x ([..., H, W]: every dimension before the
+    last two a stack of independent planes, so `batched` changes nothing but is accepted as by the sibling functions; NaN is
+    background): an fp64 device tensor shaped like x, bit for bit scipy's wherever the plane has a background pixel, without a
+    host synchronisation.  `squared=True`: the exact int32 squared distance instead.  A plane without a background pixel has no
+    defined answer: +inf (squared: -1) everywhere in it."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("distance_transform: x must be a device tensor")
+    S, C, H, W = _planes(x, False, "distance_transform")
+    xt = _f32c(x, "distance_transform(x)")
+    dev = xt.device
+    nbytes = _surface_workspace(C, H, W, "distance_transform") // 4
+    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    sq = torch.empty(tuple(x.shape), dtype=torch.int32, device=dev)
+    dist = None if squared else torch.empty(tuple(x.shape), dtype=torch.float64, device=dev)
+    a = DistanceArgs()
+    a.src, a.sq, a.dist = xt.data_ptr(), sq.data_ptr(), (None if squared else dist.data_ptr())
+    a.workspace, a.workspace_bytes, a.src_stride = ws.data_ptr(), nbytes, H * W
+    a.S, a.H, a.W, a.level = C, H, W, float(level)
+    with torch.cuda.device(dev):
+        check(lib().anoddpm_distance_transform(ctypes.byref(a), current_stream()), "distance_transform")
+    return sq if squared else dist
+
+
+def surface_distance(pred, ref, level=0.0, return_status=False):
+    """Boundary distances of every H x W plane of pred ([..., H, W]) against the plane of ref at the same place, or against ONE
+    `[H, W]` reference shared by all (its border is computed once).  With `m = plane > level`, the border of m is `m &
+    ~scipy.ndimage.binary_erosion(m)` (4 neighbours, the image edge counts as background), `d_pr` the distances from the pixels of
+    pred's border to the nearest pixel of ref's border and `d_rp` the reverse, in pixels.  Returns a dict of device tensors shaped
+    like pred without its last two dimensions (plus the trailing axis named), no host synchronisation, the same bits every run:
+    `hd` (Hausdorff distance), `hd95` (the 95th percentile of `d_pr` and `d_rp` pooled: medpy's `hd95`), `assd` (the mean of the
+    two directions' means), all fp64; `p95` [..., 3] (of `d_pr`, of `d_rp`, pooled), `mean` [..., 2], `max2` [..., 2] (int32, the
+    largest squared distances), `counts` [..., 2] (int32 border sizes) and `status` (int32: bit 0 pred's border is empty, bit 1
+    ref's).  Where the status is non-zero every fp64 value is NaN and `max2` is -1.  `return_status=True` returns `(dict, status)`."""
+    if not isinstance(pred, torch.Tensor) or not isinstance(ref, torch.Tensor):
+        raise TypeError("surface_distance: pred and ref must be device tensors")
+    S, C, H, W = _planes(pred, False, "surface_distance")
+    if tuple(ref.shape) != tuple(pred.shape) and tuple(ref.shape) != (H, W):
+        raise ValueError(f"surface_distance: ref {tuple(ref.shape)} is neither the shape of pred {tuple(pred.shape)} nor one [H, W] plane")
+    pt = _f32c(pred, "surface_distance(pred)")
+    rt = _f32c(ref, "surface_distance(ref)")
+    if rt.device != pt.device:
+        raise ValueError("surface_distance: pred and ref are on different devices")
+    dev = pt.device
+    nbytes = _surface_workspace(C, H, W, "surface_distance")
+    lead = tuple(pred.shape[:-2])
+    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    out = {"counts": torch.empty(lead + (2,), dtype=torch.int32, device=dev), "max2": torch.empty(lead + (2,), dtype=torch.int32, device=dev),
+           "mean": torch.empty(lead + (2,), dtype=torch.float64, device=dev), "p95": torch.empty(lead + (3,), dtype=torch.float64, device=dev),
+           "status": torch.empty(lead, dtype=torch.int32, device=dev)}
+    a = SurfaceArgs()
+    a.pred, a.ref, a.workspace, a.workspace_bytes = pt.data_ptr(), rt.data_ptr(), ws.data_ptr(), nbytes
+    for k in ("counts", "max2", "mean", "p95", "status"):
+        setattr(a, k, out[k].data_ptr())
+    a.pred_stride, a.ref_stride = H * W, (H * W if rt.numel() == C * H * W and C > 1 else 0)
+    a.S, a.H, a.W, a.level = C, H, W, float(level)
+    with torch.cuda.device(dev):
+        check(lib().anoddpm_surface_distance(ctypes.byref(a), current_stream()), "surface_distance")
+    out["hd"] = torch.sqrt(out["max2"].max(dim=-1).values.double())              # max2 is -1 where the status is set: NaN
+    out["hd95"] = out["p95"][..., 2]
+    out["assd"] = (out["mean"][..., 0] + out["mean"][..., 1]) / 2
+    return (out, out["status"]) if return_status else out
+
+
+def _valid_mean(values, status):
+    """Mean of `values` over the entries of the last axis whose status is 0 (NaN when there is none), and their number."""
+    ok = status == 0
+    n = ok.sum(dim=-1)
+    total = torch.where(ok, values, torch.zeros_like(values)).sum(dim=-1)
+    return torch.where(n > 0, total / n.clamp(min=1), torch.full_like(total, float("nan"))), n
+
+
 def anomaly_metrics(real, recon, mask, threshold=0.5, postprocess=None, roi=None):
     """dice / IoU / precision / recall / FPR / mse / PSNR of detection.py:229-250 from one launch, the AUC of
     detection.py:230-231 (the whole batch flattened into one curve, evaluation.py:81) from a second one -- which also gives `AP`
@@ -692,6 +783,36 @@ def anomaly_metrics_pro(real, recon, mask, threshold=0.5, postprocess=None, roi=
     r = anomaly_metrics(real, recon, mask, threshold, postprocess, roi)
     if pro_limit is not None:
         _add_pro(r, mask, pro_limit)
+    return r
+
+
+def anomaly_metrics_surface(real, recon, mask, threshold=0.5, postprocess=None, roi=None):
+    """`anomaly_metrics` with the boundary distances beside its results -- a function of its own, as `anomaly_metrics_pro` is, so
+    that `anomaly_metrics` keeps its signature, its keys and its launches.  ADDS `HD`, `HD95`, `ASSD`: `surface_distance` of the
+    thresholded map `maps["pred"]` against the mask, plane by plane, each the mean over the planes whose status is 0 (both borders
+    exist; NaN when there is none), `HD95_valid`, the number of those planes, and `surface_status`, the OR of the planes' status
+    words; with `postprocess` also `HD_pp`, `HD95_pp`, `ASSD_pp` from `maps["pred_pp"]`, from the same launch.  Without a mask:
+    NaN, 0, 0.  The inputs must be `[..., H, W]` images."""
+    r = anomaly_metrics(real, recon, mask, threshold, postprocess, roi)
+    maps = r["maps"]
+    suffixes = [""] + (["_pp"] if "pred_pp" in maps else [])
+    for sfx in suffixes:
+        r["HD" + sfx] = r["HD95" + sfx] = r["ASSD" + sfx] = float("nan")
+    r["HD95_valid"], r["surface_status"] = 0, 0
+    if mask is None:
+        return r
+    pred = maps["pred"]
+    if mask.numel() != pred.numel():
+        raise ValueError(f"anomaly_metrics_surface: mask {tuple(mask.shape)} does not match the images {tuple(pred.shape)}")
+    preds = torch.stack([pred] + ([maps["pred_pp"].reshape(pred.shape)] if len(suffixes) == 2 else []))
+    o = surface_distance(preds.reshape(len(suffixes), -1, *pred.shape[-2:]), mask.reshape(1, -1, *pred.shape[-2:]).expand(len(suffixes), -1, -1, -1))
+    vals = torch.stack([_valid_mean(o[k], o["status"])[0] for k in ("hd", "hd95", "assd")]).cpu()      # [3, len(suffixes)]
+    status = o["status"].cpu()
+    r["HD95_valid"] = int((status[0] == 0).sum())
+    for st in status[0].tolist():
+        r["surface_status"] |= st
+    for j, sfx in enumerate(suffixes):
+        r["HD" + sfx], r["HD95" + sfx], r["ASSD" + sfx] = (float(vals[i, j]) for i in range(3))
     return r
 
 
@@ -861,6 +982,15 @@ def AUPRO(real_mask, square_error, limit=0.3):
     into one curve.  NaN without a region or without background; ValueError for inputs outside the precondition of `ROC_AUC`.
     Device tensors only: the reference has no host implementation to fall back to."""
     return pro_points(real_mask, square_error, limit=limit, batched=False)[0]["aupro"]
+
+
+def HD95(real_mask, pred_mask):
+    """The 95th-percentile Hausdorff distance (medpy's `hd95`: the 95th percentile of the border-to-border distances of both
+    directions pooled) between the 0 / 1 masks, in pixels, as a Python float: `surface_distance(pred_mask, real_mask)["hd95"]`,
+    and for inputs of several planes its mean over the planes where both borders exist.  NaN when there is no such plane.
+    Device tensors only: the reference has no host implementation to fall back to."""
+    o = surface_distance(pred_mask, real_mask)
+    return float(_valid_mean(o["hd95"].reshape(-1), o["status"].reshape(-1))[0])
 
 
 def AUC_score(fpr, tpr):

@@ -761,6 +761,76 @@ int anoddpm_component_areas(const anoddpm_component_areas_args *a, void *stream)
 int anoddpm_pro_auc(const anoddpm_pro_args *a, void *stream);
 int64_t anoddpm_pro_workspace_bytes(int32_t S, int64_t n);   /* HOST function; -1 for S < 1, n < 1 or n >= 2^31 */
 
+/* ------------------------------------------------------------------ distance transform and boundary distances of anomaly maps
+ * The Hausdorff distance, its 95th-percentile form (HD95) and the average symmetric surface distance (ASSD): how far the
+ * predicted outline lies from the true one, which no overlap score says.  The reference has no counterpart.  Pixel units, 2-D
+ * planes, one threshold per call.  Every quantity is an integer squared distance or the fp64 square root of one.
+ *
+ * anoddpm_distance_transform: S planes of H x W fp32 at src + p * src_stride.  Foreground is value > level (NaN is background).
+ *   sq[p][y][x]    int32: the squared Euclidean distance from (y, x) to the nearest background pixel of the same plane, exact;
+ *                  0 on the background
+ *   dist[p][y][x]  optional fp64: sqrt(sq), correctly rounded.  With at least one background pixel in the plane it equals
+ *                  scipy.ndimage.distance_transform_edt(plane > level) bit for bit
+ *   A plane without a background pixel has no defined answer (scipy measures to a virtual pixel at (-1, -1)): sq is -1 and
+ *   dist is +inf everywhere in it.
+ *   workspace      [dev] 4 * S * H * W bytes (a quarter of anoddpm_surface_workspace_bytes(S, H, W))
+ *   Two launches: a sweep down and up every column, then per row the minimum over x' of (x - x')^2 + g(y, x')^2 in integers.
+ *
+ * anoddpm_surface_distance: S pairs of planes, pred at pred + s * pred_stride and ref at ref + s * ref_stride; ref_stride 0 =
+ *   one reference plane shared by every prediction (its border and column distances are computed once).  With m = plane > level:
+ *     border(m)  the pixels of m with at least one of the 4 neighbours background or outside the image
+ *                = m & ~scipy.ndimage.binary_erosion(m, iterations=1, border_value=0)  (medpy's and DeepMind's surface)
+ *     d_pr       for every pixel of border(pred) the distance to the nearest pixel of border(ref); d_rp the reverse
+ *   counts[s]  {|border(pred)|, |border(ref)|}
+ *   max2[s]    the largest SQUARED distance of d_pr and of d_rp (Hausdorff distance = sqrt(max(max2)))
+ *   mean[s]    the mean of d_pr and of d_rp: the fp64 sum of the square roots divided by the count.  Order of the sum: thread t
+ *              of 1024 adds the plane's border pixels t, t + 1024, ... (row-major pixel index) in that order, a halving tree
+ *              folds the 64 partials of each wave (lane i + lane i+32, then +16, ... +1) and then the 16 wave sums the same way.
+ *              ASSD = (mean[0] + mean[1]) / 2
+ *   p95[s]     the 95th percentile of d_pr, of d_rp, and of the two pooled into one multiset (medpy's hd95).  For n sorted values
+ *              v:  k = 19 (n - 1), lo = k div 20, r = k mod 20, hi = min(lo + 1, n - 1);  value = a + (b - a) * (r / 20) with
+ *              a = sqrt(v[lo]), b = sqrt(v[hi]) in fp64, every operation rounded once (numpy.percentile(d, 95) within a few
+ *              ulp).  v[lo] and v[hi] are selected exactly on the integer squared distances; sqrt is monotone.
+ *   status[s]  ANODDPM_SURFACE_EMPTY_PRED: border(pred) is empty; ANODDPM_SURFACE_EMPTY_REF: border(ref) is empty.  When it is
+ *              non-zero every fp64 output of the pair is NaN and both max2 are -1 (counts are still counts); no other pair is
+ *              touched.
+ *   workspace  [dev] anoddpm_surface_workspace_bytes(S, H, W) bytes
+ *   Four launches whatever S; integer atomics only; no allocation, no host synchronisation; the same bits on every launch and
+ *   wherever a pair sits in a batch.
+ * Both need (H - 1)^2 + (W - 1)^2 < 2^31 (every squared distance fits int32), H * W < 2^31 and 2 * S * H * W < 2^31. */
+#define ANODDPM_SURFACE_EMPTY_PRED 1
+#define ANODDPM_SURFACE_EMPTY_REF 2
+
+typedef struct anoddpm_distance_args {
+    const float *src;               /* [dev] */
+    int32_t *sq;                    /* [dev] [S][H][W] */
+    double *dist;                   /* [dev] [S][H][W] or NULL */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    int64_t src_stride;
+    int32_t S, H, W;
+    float level;
+} anoddpm_distance_args;
+
+typedef struct anoddpm_surface_args {
+    const float *pred;              /* [dev] */
+    const float *ref;               /* [dev] */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    int32_t *counts;                /* [dev] [S][2] */
+    int32_t *max2;                  /* [dev] [S][2] */
+    double *mean;                   /* [dev] [S][2] */
+    double *p95;                    /* [dev] [S][3] */
+    int32_t *status;                /* [dev] [S] */
+    int64_t pred_stride, ref_stride;
+    int32_t S, H, W;
+    float level;
+} anoddpm_surface_args;
+
+int anoddpm_distance_transform(const anoddpm_distance_args *a, void *stream);
+int anoddpm_surface_distance(const anoddpm_surface_args *a, void *stream);
+int64_t anoddpm_surface_workspace_bytes(int32_t S, int32_t H, int32_t W);   /* HOST function; -1 when the extents break the conditions above */
+
 /* ------------------------------------------------------------------ post-processing of anomaly maps before they are scored
  * The three steps published brain-MRI anomaly-segmentation pipelines apply between the squared error and AP / Dice (the
  * reference has no counterpart: it scores the raw map).  All three select or count, so each output equals scipy's bit for bit.
