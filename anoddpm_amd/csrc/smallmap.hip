@@ -20,27 +20,20 @@
 // k of its row) per four MFMAs.  B: the packed weights [tap][K/4][N][4] stream from L2 straight into a register ring, one
 // 16-byte load per lane per four MFMAs, PD steps ahead; the N tile is the fast grid dimension, so the workgroups of one XCD
 // (block id mod 8) share weight columns in their L2.
+#include "buf_load.h"
 #include "common.h"
 
+using anoddpm::buf_load4;
+using anoddpm::buf_rsrc;
+using anoddpm::f32x4;
 using anoddpm::silu_f;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SM_NT = 512;                 // 8 waves: they split K'
 
 __host__ __device__ constexpr int sm_kch(int ks) { return ks == 3 ? 256 : 512; }     // channels per K chunk: 32 / 64 per wave
 __host__ __device__ constexpr int sm_hpix(int ks, int tm, int w) { return ks == 1 ? tm : (tm / w + 2) * (w + 2); }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t sm_rsrc(const float *base)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7ffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 sm_bld4(__amdgpu_buffer_rsrc_t r, unsigned lane_bytes, unsigned wave_bytes)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_bytes, (int)wave_bytes, 0));
-}
 
 template <int KS, int RT, int CT, int LOG2W>
 __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_args a)
@@ -81,7 +74,7 @@ __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_arg
     const float *A1 = a.a1 ? a.a1 + (int64_t)b * a.a1_bs : A0;
 
     // ---- B stream: buffer loads, per-lane byte offset + a scalar offset per (chunk, step): no vector address arithmetic ----
-    const __amdgpu_buffer_rsrc_t rW = sm_rsrc(a.bmat);
+    const __amdgpu_buffer_rsrc_t rW = buf_rsrc(a.bmat);
     const unsigned ulane = ((unsigned)q * (unsigned)N + (unsigned)(n0 + l16)) * 16u;
     const int total_steps = nchunks * SPC;
     auto b_off = [&](int chunk, int s) -> unsigned {            // s is a compile-time constant at every call site
@@ -96,7 +89,7 @@ __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_arg
     for (int s = 0; s < PD; ++s) {
         const unsigned o = b_off(0, s);
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) ring[s][ct] = sm_bld4(rW, ulane, o + ct * 256u);
+        for (int ct = 0; ct < CT; ++ct) ring[s][ct] = buf_load4(rW, ulane, o + ct * 256u);
     }
 
     // ---- A staging geometry: item j of this thread = halo pixel hp_j, channel quad kq ----
@@ -254,7 +247,7 @@ __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_arg
             // refill the slot with step s + PD (possibly of the next chunk)
             const unsigned o = (s + PD < SPC) ? b_off(chunk, s + PD) : b_off(chunk + 1, s + PD - SPC);
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) ring[slot][ct] = sm_bld4(rW, ulane, o + ct * 256u);
+            for (int ct = 0; ct < CT; ++ct) ring[slot][ct] = buf_load4(rW, ulane, o + ct * 256u);
             __builtin_amdgcn_sched_barrier(0);                   // keep the requests where they are: left alone, hipcc sinks them next to their use
         }
         if (more) {

@@ -22,23 +22,11 @@
 // VALU (transforms) and MFMA phases alternate -- on this hardware they share the issue port anyway -- four barriers per patch.
 // The per-workgroup gradient goes to a workspace [PG][9][K][N] with dg = G^T dU G applied in the epilogue (two exchanges through LDS);
 // one small kernel sums the PG slabs into dw.
-#include "common.h"
+#include "f43.h"
 
-using anoddpm::silu_f;
+using namespace anoddpm;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_g(const float *base)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7ffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 bld4g(__amdgpu_buffer_rsrc_t r, unsigned lane_bytes, unsigned wave_bytes)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_bytes, (int)wave_bytes, 0));
-}
 
 constexpr int G4_NT = 768;
 constexpr int G4_PW = 18;                          // input patch: 18 x 10 pixels (16 x 8 outputs + halo)
@@ -108,7 +96,7 @@ __global__ __launch_bounds__(G4_NT, 1) void wgrad43_kernel(const anoddpm_wgrad_a
         return g;
     };
     // 32-bit buffer addressing (tensors < 2 GB, checked by the launcher): per-lane byte offset + wave-uniform byte offset
-    const __amdgpu_buffer_rsrc_t rA0 = rsrc_g(a.a0), rA1 = rsrc_g(a.a1 ? a.a1 : a.a0), rDY = rsrc_g(a.dy);
+    const __amdgpu_buffer_rsrc_t rA0 = buf_rsrc(a.a0), rA1 = buf_rsrc(a.a1 ? a.a1 : a.a0), rDY = buf_rsrc(a.dy);
     auto load_in = [&](const Geo &g) {
         const int gy = g.y0 + spy - 1, gx = g.x0 + spx - 1;
         const bool ok = in_slot && gy >= 0 && gy < H && gx >= 0 && gx < W;
@@ -120,7 +108,7 @@ __global__ __launch_bounds__(G4_NT, 1) void wgrad43_kernel(const anoddpm_wgrad_a
             const bool first = kc < a.c0;                           // wave-uniform
             const unsigned ld = (unsigned)(first ? a.a0_ld : a.a1_ld);
             const unsigned wave_off = (unsigned)g.b * (unsigned)(first ? a.a0_bs : a.a1_bs) * 4u + (unsigned)(first ? kc : kc - a.c0) * 4u;
-            in_raw[c] = bld4g(first ? rA0 : rA1, (sp * ld + (unsigned)sq * 4u) * 4u, wave_off);
+            in_raw[c] = buf_load4(first ? rA0 : rA1, (sp * ld + (unsigned)sq * 4u) * 4u, wave_off);
         }
     };
     auto store_in = [&](const Geo &g) {
@@ -147,7 +135,7 @@ __global__ __launch_bounds__(G4_NT, 1) void wgrad43_kernel(const anoddpm_wgrad_a
         const unsigned wave_off = ((unsigned)g.b * (unsigned)a.dy_bs + (unsigned)(g.y0 * W + g.x0) * (unsigned)a.dy_ld +
                                    (unsigned)(n0 + round * 32)) * 4u;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) dy_raw[j] = bld4g(rDY, dy_lane[j], wave_off);
+        for (int j = 0; j < 2; ++j) dy_raw[j] = buf_load4(rDY, dy_lane[j], wave_off);
     };
     auto store_dy = [&]() {
 #pragma unroll
@@ -157,7 +145,7 @@ __global__ __launch_bounds__(G4_NT, 1) void wgrad43_kernel(const anoddpm_wgrad_a
         }
     };
 
-    const __amdgpu_buffer_rsrc_t rCS = rsrc_g(a.colsum ? a.colsum : a.dy);
+    const __amdgpu_buffer_rsrc_t rCS = buf_rsrc(a.colsum ? a.colsum : a.dy);
     // Column sums of dY (bias / embedding gradients): the waves of row pair 1 of the first input-channel block sum their tile row
     // over the workgroup's patches of an image and store ONE row per image: colsum[b][pg * 2 + tile row][n] (2 PG rows per image
     // instead of one per tile row of every patch: 64 instead of 1 024 at 256^2); images the workgroup has no patch in get zeros.
@@ -177,49 +165,13 @@ __global__ __launch_bounds__(G4_NT, 1) void wgrad43_kernel(const anoddpm_wgrad_a
     const int s_vin = ((4 * s_trow) * G4_PW + 4 * s_tx) * SP + s_ch;
     const int s_zin = ((4 * s_trow) * 16 + 4 * s_tx) * SP + s_ch;
     const int s_out = (s_trow * 4 + s_tx) * 16 + s_ch;                               // [pos][tile][channel]: + pos * 128
-    const int s_ua = s_up == 0 ? 0 : (s_up == 1 ? 1 : 3), s_ub = s_up == 0 ? 5 : (s_up == 1 ? 2 : 4);
-    auto col_pass_v1 = [&](const float (&t)[6], float *V) {
-        const float p = t[4] - 4.f * t[2], q = t[3] - 4.f * t[1], r = t[4] - t[2], w = t[3] - t[1];
-        V[0 * 128] = 4.f * t[0] - 5.f * t[2] + t[4];
-        V[1 * 128] = p + q;
-        V[2 * 128] = p - q;
-        V[3 * 128] = r + 2.f * w;
-        V[4 * 128] = r - 2.f * w;
-        V[5 * 128] = 4.f * t[1] - 5.f * t[3] + t[5];
-    };
+    const int s_ua = bt_pair_first(s_up), s_ub = bt_pair_second(s_up);
     auto transform_v_s = [&]() {
-        const float *D = reinterpret_cast<const float *>(ldsPin + s_slot * G4_PIN) + s_vin;
         float ta[6], tb[6];
-        if (s_up == 0) {
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const float d0 = D[j * SP], d1 = D[SVROW + j * SP], d2 = D[2 * SVROW + j * SP], d3 = D[3 * SVROW + j * SP], d4 = D[4 * SVROW + j * SP], d5 = D[5 * SVROW + j * SP];
-                ta[j] = 4.f * d0 - 5.f * d2 + d4;
-                tb[j] = 4.f * d1 - 5.f * d3 + d5;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else if (s_up == 1) {
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const float d1 = D[SVROW + j * SP], d2 = D[2 * SVROW + j * SP], d3 = D[3 * SVROW + j * SP], d4 = D[4 * SVROW + j * SP];
-                const float p = d4 - 4.f * d2, q = d3 - 4.f * d1;
-                ta[j] = p + q;
-                tb[j] = p - q;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const float d1 = D[SVROW + j * SP], d2 = D[2 * SVROW + j * SP], d3 = D[3 * SVROW + j * SP], d4 = D[4 * SVROW + j * SP];
-                const float r = d4 - d2, w = d3 - d1;
-                ta[j] = r + 2.f * w;
-                tb[j] = r - 2.f * w;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        bt_row_pair<SVROW, SP, true>(s_up, reinterpret_cast<const float *>(ldsPin + s_slot * G4_PIN) + s_vin, ta, tb);
         float *V = reinterpret_cast<float *>(ldsV + s_slot * G4_V) + s_out;
-        col_pass_v1(ta, V + s_ua * 6 * 128);
-        col_pass_v1(tb, V + s_ub * 6 * 128);
+        bt_cols<128>(ta, V + s_ua * 6 * 128);
+        bt_cols<128>(tb, V + s_ub * 6 * 128);
     };
     auto col_pass_z1 = [&](const float (&t)[4], float *Z) {
         const float e02 = t[0] + t[2], o13 = t[1] + t[3], e024 = t[0] + 4.f * t[2], o138 = 2.f * t[1] + 8.f * t[3];

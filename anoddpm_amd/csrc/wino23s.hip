@@ -17,13 +17,15 @@
 // Per 32-channel K chunk (one barrier):  transform patch(c+1) -> V(c+1)   |   32 or 64 MFMAs per wave on V(c)   |   activate and
 // store the raw patch (c+2) (GroupNorm-apply + SiLU, nearest-x2 / concat resolved, zero padding after the transform)   |   request
 // patch(c+3).  The B operand streams from L2 through a register ring (buffer loads, scalar offsets), two steps ahead.
+#include "buf_load.h"
 #include "common.h"
 
+using anoddpm::buf_load4;
+using anoddpm::buf_rsrc;
+using anoddpm::f32x4;
 using anoddpm::silu_f;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WS_NT = 512;
 constexpr int WS_KCH = 32;                 // channels per K chunk
@@ -31,15 +33,6 @@ constexpr int WS_PITCH = WS_KCH + 4;       // floats between pixels (patch) / ti
 constexpr int WS_PPX = 100;                // 10 x 10 input pixels: the 8 x 8 outputs of a workgroup + halo
 constexpr int WS_VBUF = 16 * 16 * WS_PITCH;    // floats per V buffer [pos][tile][PITCH]
 constexpr int WS_PBUF = 104 * WS_PITCH;        // floats per patch buffer (100 pixels + slack for the unconditional last slot)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ws_rsrc(const float *base)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7ffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 ws_bld4(__amdgpu_buffer_rsrc_t r, unsigned lane_bytes, unsigned wave_bytes)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_bytes, (int)wave_bytes, 0));
-}
 
 template <int CT>                           // 16-channel column tiles per workgroup: 2 (32 channels) or 4 (64)
 __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args a)
@@ -69,7 +62,7 @@ __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args
     const float *A1 = a.a1 ? a.a1 + (int64_t)b * a.a1_bs : A0;
 
     // ---- B stream: positions 2 wave, 2 wave + 1; step (chunk, i): 16 k; per-lane byte offset + scalar offset ----
-    const __amdgpu_buffer_rsrc_t rU = ws_rsrc(a.bmat);
+    const __amdgpu_buffer_rsrc_t rU = buf_rsrc(a.bmat);
     const unsigned ulane = ((unsigned)q * (unsigned)N + (unsigned)(n0 + l16)) * 16u;
     const unsigned pos_bytes = (unsigned)K4 * (unsigned)N * 16u;
     auto b_off = [&](int chunk, int i, int pp) -> unsigned {     // i, pp compile-time
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args
         for (int pp = 0; pp < 2; ++pp) {
             const unsigned o = b_off(0, i, pp);
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) ring[i][pp][ct] = ws_bld4(rU, ulane, o + ct * 256u);
+            for (int ct = 0; ct < CT; ++ct) ring[i][pp][ct] = buf_load4(rU, ulane, o + ct * 256u);
         }
 
     // ---- patch staging: item j of this thread = (halo pixel hp, channel quad kq); 100 x 8 items over 512 threads ----
@@ -249,7 +242,7 @@ __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args
             for (int pp = 0; pp < 2; ++pp) {
                 const unsigned o = b_off(chunk + 1, i, pp);
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) ring[i][pp][ct] = ws_bld4(rU, ulane, o + ct * 256u);
+                for (int ct = 0; ct < CT; ++ct) ring[i][pp][ct] = buf_load4(rU, ulane, o + ct * 256u);
             }
             __builtin_amdgcn_sched_barrier(0);
         }

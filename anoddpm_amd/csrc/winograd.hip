@@ -23,29 +23,19 @@
 //   * 64 MFMAs per wave per iteration in four bursts of 16, operand reads for the next burst issued before each.
 // The fp32 MFMA does not hide VALU issue on this chip (tools/mfma_ubench.hip), so the design minimises VALU
 // instructions per MFMA: no 64-bit address arithmetic, no predicated loads, no repeated transforms.
+#include "buf_load.h"
 #include "common.h"
 
+using anoddpm::buf_load4;
+using anoddpm::buf_rsrc;
+using anoddpm::f32x4;
 using anoddpm::silu_f;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WKC = 16;            // channels per K iteration
-
-// Buffer loads: descriptor (SGPRs) + per-lane 32-bit byte offset (VGPR) + wave-uniform 32-bit byte offset (SGPR).
-// All address arithmetic that changes inside the K loop is then scalar -- VALU instructions are NOT hidden by the
-// fp32 MFMA on gfx950, 64-bit VALU pointer adds would come straight out of the matrix issue time.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wrsrc(const float *base)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7ffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 wbld4(__amdgpu_buffer_rsrc_t r, unsigned lane_bytes, unsigned wave_bytes)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_bytes, (int)wave_bytes, 0));
-}
 
 constexpr int DPITCH = 5;          // float4 per patch pixel in LDS: 4 quads + 1 pad (spreads the stride-2-pixel reads over banks)
 
@@ -133,8 +123,8 @@ __global__ __launch_bounds__(128 * WMW * WNW, 2) void wino_kernel(const anoddpm_
     }
     f32x4 praw[PJ];
     f32x4 asc = {1.f, 1.f, 1.f, 1.f}, ash = {0.f, 0.f, 0.f, 0.f};
-    const __amdgpu_buffer_rsrc_t rA0 = wrsrc(A0), rA1 = wrsrc(A1 ? A1 : A0);
-    const __amdgpu_buffer_rsrc_t rSc = wrsrc(gsc ? gsc : A0), rSh = wrsrc(gsh ? gsh : A0);
+    const __amdgpu_buffer_rsrc_t rA0 = buf_rsrc(A0), rA1 = buf_rsrc(A1 ? A1 : A0);
+    const __amdgpu_buffer_rsrc_t rSc = buf_rsrc(gsc ? gsc : A0), rSh = buf_rsrc(gsh ? gsh : A0);
     auto load_patch = [&](int chunk) {                              // unconditional loads, clamped addresses
         const int kbase = chunk * WKC;
         const bool first = kbase < a.c0;                            // wave-uniform source choice
@@ -142,13 +132,13 @@ __global__ __launch_bounds__(128 * WMW * WNW, 2) void wino_kernel(const anoddpm_
         const unsigned ld = (unsigned)(first ? a.a0_ld : a.a1_ld);
         const unsigned koff = (unsigned)(first ? kbase : kbase - a.c0) * 4u;
         if (FAST || affine) {
-            asc = wbld4(rSc, (unsigned)(pq * 16), (unsigned)kbase * 4u);
-            ash = wbld4(rSh, (unsigned)(pq * 16), (unsigned)kbase * 4u);
+            asc = buf_load4(rSc, (unsigned)(pq * 16), (unsigned)kbase * 4u);
+            ash = buf_load4(rSh, (unsigned)(pq * 16), (unsigned)kbase * 4u);
         }
 #pragma unroll
         for (int j = 0; j < PJ; ++j) {
             const unsigned sp = spix[j] >= 0 ? (unsigned)spix[j] : 0u;
-            praw[j] = wbld4(r, (sp * ld + (unsigned)(pq * 4)) * 4u, koff);
+            praw[j] = buf_load4(r, (sp * ld + (unsigned)(pq * 4)) * 4u, koff);
         }
     };
     auto store_patch = [&](int buf) {                               // transform, zero padding AFTER it
@@ -192,7 +182,7 @@ __global__ __launch_bounds__(128 * WMW * WNW, 2) void wino_kernel(const anoddpm_
 
     // A group = 16 MFMAs: (chunk, kg, uu) -> 4 positions v x K = 4 (quad q = 2*kg + h of the 16-channel chunk).
     // B operands of a group: U[xi = 8xh + 4uu + v][k4 = 4*chunk + 2kg + h][n], v = 0..3
-    const __amdgpu_buffer_rsrc_t rU = wrsrc(a.bmat);
+    const __amdgpu_buffer_rsrc_t rU = buf_rsrc(a.bmat);
     const unsigned xi_bytes = (unsigned)xi_stride * 4u;             // launcher guarantees 16 * xi_bytes < 2^31
     const unsigned ubase = (unsigned)(xh * 8) * xi_bytes;           // wave-uniform
     const unsigned ulane = (unsigned)(nbc * 4 + h * N * 4) * 4u;    // per-lane byte offset
@@ -200,7 +190,7 @@ __global__ __launch_bounds__(128 * WMW * WNW, 2) void wino_kernel(const anoddpm_
     auto load_b = [&](int chunk, int kg, int uu, int set) {
         const unsigned w = ubase + (unsigned)(chunk * 4 + 2 * kg) * (unsigned)N * 16u + (unsigned)(uu * 4) * xi_bytes;
 #pragma unroll
-        for (int v = 0; v < 4; ++v) bvr[set][v] = wbld4(rU, ulane, w + (unsigned)v * xi_bytes);
+        for (int v = 0; v < 4; ++v) bvr[set][v] = buf_load4(rU, ulane, w + (unsigned)v * xi_bytes);
     };
     f32x4 rawX[4], rawY[4], av[4];
     auto issue_reads = [&](int buf, int kg, int uu, int which) {    // 4 ds_read_b128: one patch row of the tile

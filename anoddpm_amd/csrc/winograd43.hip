@@ -20,14 +20,12 @@
 // Epilogue: the 36 x 16 x 128 products go through LDS in three rounds of 48 / 48 / 32 channels (120 KB, aliasing the loop
 // buffers); one thread per (tile, channel) forms A^T M A, adds bias / temb / residual, stores 16 pixels through buffer stores with
 // scalar pixel offsets and folds the GroupNorm sums.
-#include "common.h"
+#include "f43.h"
 #include "gn_fold.h"
 
-using anoddpm::silu_f;
+using namespace anoddpm;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int F4_NT = 768;                 // threads
 constexpr int F4_KC = 16;                  // channels per K iteration
@@ -45,22 +43,9 @@ constexpr int F4_LDS_FLOATS = F4_EX_FLOATS > F4_LOOP_FLOATS ? F4_EX_FLOATS : F4_
 constexpr int F4_KMAX = 1024;                         // input channels whose GroupNorm affine fits the LDS table
 constexpr int F4_AFF_FLOATS = 2 * F4_KMAX;            // [K] scales, then [K] shifts of this workgroup's image, behind both uses of `lds`
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc43(const float *base)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7ffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 bld4(__amdgpu_buffer_rsrc_t r, unsigned lane_bytes, unsigned wave_bytes)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_bytes, (int)wave_bytes, 0));
-}
-
 // DBG (timing ablations only, wrong results; ANODDPM_DEBUG2): 1 no epilogue, 2 no input transform, 3 no patch staging, 4 no B requests
 // NTL = 16-channel tiles per workgroup: 8 (128 output channels) or 4 (64 channels: twice the workgroups when the map is too
 // small to fill the 256 CUs with 128-channel ones, at the price of repeating the staging / input transform per 64 channels)
-#ifndef F43_PAIR_TRANSFORM
-#define F43_PAIR_TRANSFORM 0
-#endif
 template <bool FAST, int DBG = 0, int NTL = 8>
 __global__ __launch_bounds__(F4_NT, 1) void wino43_kernel(const anoddpm_igemm_args a)
 {
@@ -104,8 +89,8 @@ __global__ __launch_bounds__(F4_NT, 1) void wino43_kernel(const anoddpm_igemm_ar
     }
     f32x4 praw[F4_PJ];
     f32x4 asc = {1.f, 1.f, 1.f, 1.f}, ash = {0.f, 0.f, 0.f, 0.f};
-    const __amdgpu_buffer_rsrc_t rA0 = rsrc43(A0), rA1 = rsrc43(A1 ? A1 : A0);
-    const __amdgpu_buffer_rsrc_t rSc = rsrc43(gsc ? gsc : A0), rSh = rsrc43(gsh ? gsh : A0);
+    const __amdgpu_buffer_rsrc_t rA0 = buf_rsrc(A0), rA1 = buf_rsrc(A1 ? A1 : A0);
+    const __amdgpu_buffer_rsrc_t rSc = buf_rsrc(gsc ? gsc : A0), rSh = buf_rsrc(gsh ? gsh : A0);
     auto load_patch = [&](int chunk) {                              // unconditional loads, clamped addresses
         const int kbase = chunk * F4_KC;
         const bool first = kbase < a.c0;
@@ -115,7 +100,7 @@ __global__ __launch_bounds__(F4_NT, 1) void wino43_kernel(const anoddpm_igemm_ar
 #pragma unroll
         for (int j = 0; j < F4_PJ; ++j) {
             const unsigned sp = spix[j] >= 0 ? (unsigned)spix[j] : 0u;
-            praw[j] = bld4(r, (sp * ld + (unsigned)(pq * 4)) * 4u, koff);
+            praw[j] = buf_load4(r, (sp * ld + (unsigned)(pq * 4)) * 4u, koff);
         }
     };
     auto store_patch = [&](int buf, int chunk) {                    // transform, zero padding AFTER it
@@ -132,13 +117,7 @@ __global__ __launch_bounds__(F4_NT, 1) void wino43_kernel(const anoddpm_igemm_ar
         for (int j = 0; j < F4_PJ; ++j) {
             const int idx = tid + j * F4_NT;
             f32x4 v = praw[j];
-            if (FAST) {
-                v = v * asc + ash;
-                v[0] = silu_f(v[0]); v[1] = silu_f(v[1]); v[2] = silu_f(v[2]); v[3] = silu_f(v[3]);
-            } else {
-                if (affine) v = v * asc + ash;
-                if (act) { v[0] = silu_f(v[0]); v[1] = silu_f(v[1]); v[2] = silu_f(v[2]); v[3] = silu_f(v[3]); }
-            }
+            v = f43_activate<FAST>(v, asc, ash, affine, act);
             ldsD[buf * F4_DT + (idx >> 2) * F4_PITCH + (idx & 3)] = spix[j] >= 0 ? v : zero;
         }
     };
@@ -147,19 +126,11 @@ __global__ __launch_bounds__(F4_NT, 1) void wino43_kernel(const anoddpm_igemm_ar
     // wave -> (row u = wave % 6, tile-row pair = wave / 6); lane -> (channel pair = lane & 7, tile slot = lane >> 3): the 32 lanes
     // of a ds_read_b64 group then cover one tile row x 8 pairs = 32 distinct 8-byte bank slots, and the 16 lanes of a ds_write_b64
     // group two neighbouring tiles x 8 pairs.  float2 items keep the transform at ~30 live registers.
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     const int tu = wave % 6;
     const int tpair = lane & 7;
     const int ttile = ((wave / 6) * 2 + (lane >> 5)) * 4 + ((lane >> 3) & 3);
     const int tbase2 = (((4 * (ttile >> 2)) * F4_PW + 4 * (ttile & 3)) * F4_PITCH) * 2 + tpair;      // float2 index of the tile's patch corner
-    // B^T row u as (patch row, coefficient) pairs -- every row of B^T touches at most four patch rows:
-    //   u0: 4 d0 - 5 d2 + d4        u1: -4 d1 - 4 d2 + d3 + d4     u2: 4 d1 - 4 d2 - d3 + d4
-    //   u3: -2 d1 - d2 + 2 d3 + d4  u4: 2 d1 - d2 - 2 d3 + d4      u5: 4 d1 - 5 d3 + d5
-    const int tr0 = (tu == 0) ? 0 : 1, tr1 = (tu == 5) ? 3 : 2, tr2 = (tu == 0) ? 4 : ((tu == 5) ? 5 : 3), tr3 = 4;
-    const float tc0 = (tu == 0) ? 4.f : (tu == 1 ? -4.f : (tu == 2 ? 4.f : (tu == 3 ? -2.f : (tu == 4 ? 2.f : 4.f))));
-    const float tc1 = (tu == 0 || tu == 5) ? -5.f : ((tu == 1 || tu == 2) ? -4.f : -1.f);
-    const float tc2 = (tu == 0 || tu == 5) ? 1.f : (tu == 1 ? 1.f : (tu == 2 ? -1.f : (tu == 3 ? 2.f : -2.f)));
-    const float tc3 = (tu == 0 || tu == 5) ? 0.f : 1.f;
+    F43_BT_ROW(tu);
     const int to0 = tr0 * F4_PW * F4_PITCH * 2, to1 = tr1 * F4_PW * F4_PITCH * 2, to2 = tr2 * F4_PW * F4_PITCH * 2, to3 = tr3 * F4_PW * F4_PITCH * 2;
     auto transform = [&](int pbuf, int vbuf) {
         const f32x2 *D = reinterpret_cast<const f32x2 *>(ldsD + pbuf * F4_DT) + tbase2;
@@ -173,69 +144,24 @@ __global__ __launch_bounds__(F4_NT, 1) void wino43_kernel(const anoddpm_igemm_ar
             __builtin_amdgcn_sched_barrier(0);
         }
         // stage 2: V[u][v] = sum_j t[j] B^T[v][j];  V layout [pos][tile][quad] float4 = [pos][tile][pair] float2
-        const f32x2 p = t[4] - 4.f * t[2], q = t[3] - 4.f * t[1], r = t[4] - t[2], s = t[3] - t[1];
-        f32x2 *V = reinterpret_cast<f32x2 *>(ldsV + vbuf * F4_V) + ((tu * 6) * 16 + ttile) * 8 + tpair;
-        V[0 * 128] = 4.f * t[0] - 5.f * t[2] + t[4];
-        V[1 * 128] = p + q;
-        V[2 * 128] = p - q;
-        V[3 * 128] = r + 2.f * s;
-        V[4 * 128] = r - 2.f * s;
-        V[5 * 128] = 4.f * t[1] - 5.f * t[3] + t[5];
+        bt_cols<128>(t, reinterpret_cast<f32x2 *>(ldsV + vbuf * F4_V) + ((tu * 6) * 16 + ttile) * 8 + tpair);
     };
 
     // Round 6, F43_PAIR_TRANSFORM=1 (measurement builds; measured equal to the single-row items, profiles/r6_f43_pair_transform_ab.txt,
-    // so NOT the default): row-PAIR items on single channels (the form wgrad43.hip runs; profiles/r6_wgrad43_ab.txt): rows (1,2)
-    // and (3,4) of B^T share their partial sums, (0,5) read disjoint patch rows -- 4 operations per column and row pair instead of
-    // 4 per row, literal coefficients.  768 items = 16 tiles x 16 channels x 3 row pairs: wave w = (row pair w % 3, tile row w / 3),
-    // lane = (tile column lane >> 4, channel lane & 15).
+    // so NOT the default): row-PAIR items on single channels (bt_row_pair; the form wgrad43.hip runs, profiles/r6_wgrad43_ab.txt).
+    // 768 items = 16 tiles x 16 channels x 3 row pairs: wave w = (row pair w % 3, tile row w / 3), lane = (tile column lane >> 4,
+    // channel lane & 15).
     const int p_up = wave % 3;
     const int p_tx = lane >> 4, p_ch = lane & 15;
     constexpr int PP = F4_PITCH * 4, PROW = F4_PW * PP;             // floats per staged pixel / patch row
     const int p_in = ((4 * (wave / 3)) * F4_PW + 4 * p_tx) * PP + p_ch;
     const int p_out = ((wave / 3) * 4 + p_tx) * 16 + p_ch;          // V[pos][tile][channel]: + pos * 256
-    const int p_ua = p_up == 0 ? 0 : (p_up == 1 ? 1 : 3), p_ub = p_up == 0 ? 5 : (p_up == 1 ? 2 : 4);
-    auto col_pass = [&](const float (&t)[6], float *V) {
-        const float p = t[4] - 4.f * t[2], q = t[3] - 4.f * t[1], r = t[4] - t[2], w = t[3] - t[1];
-        V[0 * 256] = 4.f * t[0] - 5.f * t[2] + t[4];
-        V[1 * 256] = p + q;
-        V[2 * 256] = p - q;
-        V[3 * 256] = r + 2.f * w;
-        V[4 * 256] = r - 2.f * w;
-        V[5 * 256] = 4.f * t[1] - 5.f * t[3] + t[5];
-    };
     auto transform_p = [&](int pbuf, int vbuf) {
-        const float *D = reinterpret_cast<const float *>(ldsD + pbuf * F4_DT) + p_in;
         float ta[6], tb[6];
-        if (p_up == 0) {
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const float d0 = D[j * PP], d1 = D[PROW + j * PP], d2 = D[2 * PROW + j * PP], d3 = D[3 * PROW + j * PP], d4 = D[4 * PROW + j * PP], d5 = D[5 * PROW + j * PP];
-                ta[j] = 4.f * d0 - 5.f * d2 + d4;
-                tb[j] = 4.f * d1 - 5.f * d3 + d5;
-                __builtin_amdgcn_sched_barrier(0);                  // one column of reads in flight (see transform())
-            }
-        } else if (p_up == 1) {
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const float d1 = D[PROW + j * PP], d2 = D[2 * PROW + j * PP], d3 = D[3 * PROW + j * PP], d4 = D[4 * PROW + j * PP];
-                const float p = d4 - 4.f * d2, q = d3 - 4.f * d1;
-                ta[j] = p + q;
-                tb[j] = p - q;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const float d1 = D[PROW + j * PP], d2 = D[2 * PROW + j * PP], d3 = D[3 * PROW + j * PP], d4 = D[4 * PROW + j * PP];
-                const float r = d4 - d2, w = d3 - d1;
-                ta[j] = r + 2.f * w;
-                tb[j] = r - 2.f * w;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        bt_row_pair<PROW, PP, true>(p_up, reinterpret_cast<const float *>(ldsD + pbuf * F4_DT) + p_in, ta, tb);   // one column of reads in flight (see transform())
         float *V = reinterpret_cast<float *>(ldsV + vbuf * F4_V) + p_out;
-        col_pass(ta, V + p_ua * 6 * 256);
-        col_pass(tb, V + p_ub * 6 * 256);
+        bt_cols<256>(ta, V + bt_pair_first(p_up) * 6 * 256);
+        bt_cols<256>(tb, V + bt_pair_second(p_up) * 6 * 256);
     };
     auto transform_sel = [&](int pbuf, int vbuf) {
         if (F43_PAIR_TRANSFORM) transform_p(pbuf, vbuf);
@@ -250,7 +176,7 @@ __global__ __launch_bounds__(F4_NT, 1) void wino43_kernel(const anoddpm_igemm_ar
         for (int nt = 0; nt < NTL; ++nt) acc[p][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int l15 = lane & 15, kq = lane >> 4;
-    const __amdgpu_buffer_rsrc_t rU = rsrc43(a.bmat);
+    const __amdgpu_buffer_rsrc_t rU = buf_rsrc(a.bmat);
     const unsigned xi_bytes = (unsigned)K4 * (unsigned)N * 16u;                       // bytes per position of U
     const unsigned ulane = ((unsigned)kq * (unsigned)N + (unsigned)(n0 + l15)) * 16u;  // + nt*256 + chunk*4*N*16 + pos*xi_bytes
     const int vread = (wave * 3) * 64 + l15 * 4 + kq;                                 // + p*64 float4
@@ -261,7 +187,7 @@ __global__ __launch_bounds__(F4_NT, 1) void wino43_kernel(const anoddpm_igemm_ar
     constexpr int NG = 3 * NTL;                                     // (position, channel tile) groups per iteration
     auto load_group = [&](int chunk, int g, int slot) {             // g = p * NTL + nt (compile-time), slot = g % 4
         const unsigned w = (unsigned)(wave * 3 + g / NTL) * xi_bytes + (unsigned)(chunk * 4) * (unsigned)N * 16u;
-        ring[slot] = bld4(rU, ulane + (unsigned)(g % NTL) * 256u, w);
+        ring[slot] = buf_load4(rU, ulane + (unsigned)(g % NTL) * 256u, w);
     };
 
     // prologue: patch(0) -> LDS -> V(0); patch(1) -> LDS; patch(2) requested
@@ -272,8 +198,8 @@ __global__ __launch_bounds__(F4_NT, 1) void wino43_kernel(const anoddpm_igemm_ar
     const bool aff_slot = (FAST || affine) && tid < K4 && !fold;
     anoddpm::FoldLoads fl;
     if (aff_slot) {
-        aff_sc = bld4(rSc, (unsigned)(tid * 16), 0u);
-        aff_sh = bld4(rSh, (unsigned)(tid * 16), 0u);
+        aff_sc = buf_load4(rSc, (unsigned)(tid * 16), 0u);
+        aff_sh = buf_load4(rSh, (unsigned)(tid * 16), 0u);
     } else if (fold) {
         fl = anoddpm::fold_affine_request(a, b, tid);                 // oldest requests of the workgroup, like the table loads above
     }
@@ -357,8 +283,8 @@ __global__ __launch_bounds__(F4_NT, 1) void wino43_kernel(const anoddpm_igemm_ar
     // scalar offset per pixel of the 4x4 tile, so the 16 stores / residual loads of an item carry no vector address arithmetic.
     float *M = lds;
     const float *TE = a.temb ? a.temb + (int64_t)b * a.temb_ld : nullptr;
-    const __amdgpu_buffer_rsrc_t rO = rsrc43(a.out + (int64_t)b * a.o_bs);
-    const __amdgpu_buffer_rsrc_t rR = rsrc43(a.res ? a.res + (int64_t)b * a.r_bs : a.out);
+    const __amdgpu_buffer_rsrc_t rO = buf_rsrc(a.out + (int64_t)b * a.o_bs);
+    const __amdgpu_buffer_rsrc_t rR = buf_rsrc(a.res ? a.res + (int64_t)b * a.r_bs : a.out);
     const bool has_res = a.res != nullptr;
     const unsigned uW = (unsigned)W, o_ld = (unsigned)a.out_ld, r_ld = (unsigned)a.res_ld;
     constexpr int ROUNDS = NTL == 8 ? 3 : 2;                        // 8 tiles: 3 + 3 + 2; 4 tiles: 2 + 2

@@ -19,16 +19,13 @@
 // three-piece V live in LDS single-buffered (46 + 108 KB), so an iteration is  stage | barrier | transform + split | barrier |
 // 36 x 6 MFMAs per wave | barrier; the raw patch of the next iteration is requested before the MFMA phase.  Weights: three bf16
 // planes [piece][pos][K/8][N][8] (pack kind 6), one 16-byte load per piece and position per lane through a register ring.
-#include "common.h"
+#include "f43.h"
 
-using anoddpm::silu_f;
+using namespace anoddpm;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int B4_NT = 512;                 // 8 waves: wave w = all 36 positions x channels 16 w .. 16 w + 15 x 16 tiles
 constexpr int B4_KC = 32;                  // channels per K iteration
@@ -39,15 +36,6 @@ constexpr int B4_PJ = 6;                   // staging slots per thread: 6 * 512 
 constexpr int B4_DT = B4_PPIX * B4_PITCH;              // float4 of the patch buffer (exactly the patch: LDS is full)
 constexpr int B4_VPIECE = 36 * 16 * 64;                // bytes of one piece of V: [pos][tile][32 bf16]
 constexpr int B4_LDS_BYTES = B4_DT * 16 + 3 * B4_VPIECE;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t b4_rsrc(const void *base)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0x7ffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 b4_bld4(__amdgpu_buffer_rsrc_t r, unsigned lane_bytes, unsigned wave_bytes)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_bytes, (int)wave_bytes, 0));
-}
 
 // x -> {hi, mid, lo} bf16 pieces (round to nearest even each), two values at a time: returns the packed pairs
 __device__ __forceinline__ void split3(f32x2 x, unsigned &hi, unsigned &mid, unsigned &lo)
@@ -61,15 +49,6 @@ __device__ __forceinline__ void split3(f32x2 x, unsigned &hi, unsigned &mid, uns
     hi = __builtin_bit_cast(unsigned, h);
     mid = __builtin_bit_cast(unsigned, m);
     lo = __builtin_bit_cast(unsigned, l);
-}
-
-__device__ __forceinline__ void b4_at6(const float (&m)[6], float (&o)[4])
-{
-    const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-    o[0] = m[0] + s12 + s34;
-    o[1] = d12 + 2.f * d34;
-    o[2] = s12 + 4.f * s34;
-    o[3] = d12 + 8.f * d34 + m[5];
 }
 
 __global__ __launch_bounds__(B4_NT, 1) void wino43b_kernel(const anoddpm_igemm_args a)
@@ -108,8 +87,8 @@ __global__ __launch_bounds__(B4_NT, 1) void wino43b_kernel(const anoddpm_igemm_a
         spix[j] = sp;
     }
     f32x4 praw[B4_PJ];
-    const __amdgpu_buffer_rsrc_t rA0 = b4_rsrc(A0), rA1 = b4_rsrc(A1 ? A1 : A0);
-    const __amdgpu_buffer_rsrc_t rSc = b4_rsrc(gsc ? gsc : A0), rSh = b4_rsrc(gsh ? gsh : A0);
+    const __amdgpu_buffer_rsrc_t rA0 = buf_rsrc(A0), rA1 = buf_rsrc(A1 ? A1 : A0);
+    const __amdgpu_buffer_rsrc_t rSc = buf_rsrc(gsc ? gsc : A0), rSh = buf_rsrc(gsh ? gsh : A0);
     auto load_patch = [&](int chunk) {                              // unconditional loads, clamped addresses
         if (chunk >= nchunks) chunk = nchunks - 1;
         const int kbase = chunk * B4_KC;
@@ -120,22 +99,21 @@ __global__ __launch_bounds__(B4_NT, 1) void wino43b_kernel(const anoddpm_igemm_a
 #pragma unroll
         for (int j = 0; j < B4_PJ; ++j) {
             const unsigned sp = spix[j] >= 0 ? (unsigned)spix[j] : 0u;
-            praw[j] = b4_bld4(r, (sp * ld + (unsigned)(pq * 4)) * 4u, koff);
+            praw[j] = buf_load4(r, (sp * ld + (unsigned)(pq * 4)) * 4u, koff);
         }
     };
     auto store_patch = [&](int chunk) {                             // GroupNorm-apply + SiLU, zero padding AFTER it
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         f32x4 asc = {1.f, 1.f, 1.f, 1.f}, ash = {0.f, 0.f, 0.f, 0.f};
         if (affine) {
-            asc = b4_bld4(rSc, (unsigned)(pq * 16), (unsigned)(chunk * B4_KC) * 4u);
-            ash = b4_bld4(rSh, (unsigned)(pq * 16), (unsigned)(chunk * B4_KC) * 4u);
+            asc = buf_load4(rSc, (unsigned)(pq * 16), (unsigned)(chunk * B4_KC) * 4u);
+            ash = buf_load4(rSh, (unsigned)(pq * 16), (unsigned)(chunk * B4_KC) * 4u);
         }
 #pragma unroll
         for (int j = 0; j < B4_PJ; ++j) {
             const int idx = tid + j * B4_NT;
             f32x4 v = praw[j];
-            if (affine) v = v * asc + ash;
-            if (act) { v[0] = silu_f(v[0]); v[1] = silu_f(v[1]); v[2] = silu_f(v[2]); v[3] = silu_f(v[3]); }
+            v = f43_activate<false>(v, asc, ash, affine, act);
             if ((idx >> 3) < B4_PPIX) ldsD[(idx >> 3) * B4_PITCH + (idx & 7)] = spix[j] >= 0 ? v : zero;
         }
     };
@@ -148,14 +126,7 @@ __global__ __launch_bounds__(B4_NT, 1) void wino43b_kernel(const anoddpm_igemm_a
         const int tu = w12 % 6;
         const int tpair = (lane & 7) + 8 * half;                    // channel pair 0..15 of the chunk
         const int ttile = (w12 / 6) * 8 + (lane >> 3);
-        // B^T row u as (patch row, coefficient) pairs:
-        //   u0: 4 d0 - 5 d2 + d4        u1: -4 d1 - 4 d2 + d3 + d4     u2: 4 d1 - 4 d2 - d3 + d4
-        //   u3: -2 d1 - d2 + 2 d3 + d4  u4: 2 d1 - d2 - 2 d3 + d4      u5: 4 d1 - 5 d3 + d5
-        const int tr0 = (tu == 0) ? 0 : 1, tr1 = (tu == 5) ? 3 : 2, tr2 = (tu == 0) ? 4 : ((tu == 5) ? 5 : 3), tr3 = 4;
-        const float tc0 = (tu == 0) ? 4.f : (tu == 1 ? -4.f : (tu == 2 ? 4.f : (tu == 3 ? -2.f : (tu == 4 ? 2.f : 4.f))));
-        const float tc1 = (tu == 0 || tu == 5) ? -5.f : ((tu == 1 || tu == 2) ? -4.f : -1.f);
-        const float tc2 = (tu == 0 || tu == 5) ? 1.f : (tu == 1 ? 1.f : (tu == 2 ? -1.f : (tu == 3 ? 2.f : -2.f)));
-        const float tc3 = (tu == 0 || tu == 5) ? 0.f : 1.f;
+        F43_BT_ROW(tu);
         const int rp = B4_PW * B4_PITCH * 2;                         // float2 per patch row
         const f32x2 *D = reinterpret_cast<const f32x2 *>(ldsD) + ((4 * (ttile >> 2)) * B4_PW + 4 * (ttile & 3)) * B4_PITCH * 2 + tpair;
         f32x2 t[6];
@@ -163,14 +134,8 @@ __global__ __launch_bounds__(B4_NT, 1) void wino43b_kernel(const anoddpm_igemm_a
         for (int j = 0; j < 6; ++j)
             t[j] = tc0 * D[tr0 * rp + j * B4_PITCH * 2] + tc1 * D[tr1 * rp + j * B4_PITCH * 2] + tc2 * D[tr2 * rp + j * B4_PITCH * 2] +
                    tc3 * D[tr3 * rp + j * B4_PITCH * 2];
-        const f32x2 p = t[4] - 4.f * t[2], q = t[3] - 4.f * t[1], r = t[4] - t[2], s = t[3] - t[1];
         f32x2 v[6];
-        v[0] = 4.f * t[0] - 5.f * t[2] + t[4];
-        v[1] = p + q;
-        v[2] = p - q;
-        v[3] = r + 2.f * s;
-        v[4] = r - 2.f * s;
-        v[5] = 4.f * t[1] - 5.f * t[3] + t[5];
+        bt_cols<1>(t, v);
         // V[piece][pos = 6 u + v][tile][32 bf16]: this item's two channels are one 4-byte slot
         unsigned char *dst = ldsV + ((tu * 6) * 16 + ttile) * 64 + tpair * 4;
 #pragma unroll
@@ -189,7 +154,7 @@ __global__ __launch_bounds__(B4_NT, 1) void wino43b_kernel(const anoddpm_igemm_a
     for (int p = 0; p < 36; ++p) acc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int l15 = lane & 15, kq = lane >> 4;
     const int nw = n0 + wave * 16 + l15;                            // this lane's output channel
-    const __amdgpu_buffer_rsrc_t rU = b4_rsrc(a.bmat);
+    const __amdgpu_buffer_rsrc_t rU = buf_rsrc(a.bmat);
     const unsigned piece_bytes = 36u * (unsigned)K8 * (unsigned)N * 16u;
     const unsigned pos_bytes = (unsigned)K8 * (unsigned)N * 16u;
     const unsigned ulane = ((unsigned)kq * (unsigned)N + (unsigned)nw) * 16u;        // + (chunk * 4) * N * 16 + pos * pos_bytes + piece * piece_bytes
@@ -199,7 +164,7 @@ __global__ __launch_bounds__(B4_NT, 1) void wino43b_kernel(const anoddpm_igemm_a
         if (chunk >= nchunks) chunk = nchunks - 1;
         const unsigned o = (unsigned)pos * pos_bytes + (unsigned)(chunk * 4) * (unsigned)N * 16u;
 #pragma unroll
-        for (int pc = 0; pc < 3; ++pc) ring[slot][pc] = b4_bld4(rU, ulane, o + (unsigned)pc * piece_bytes);
+        for (int pc = 0; pc < 3; ++pc) ring[slot][pc] = buf_load4(rU, ulane, o + (unsigned)pc * piece_bytes);
     };
     const unsigned char *vA = ldsV + l15 * 64 + kq * 16;            // + pos * 1024 + piece * B4_VPIECE
 
@@ -241,8 +206,8 @@ __global__ __launch_bounds__(B4_NT, 1) void wino43b_kernel(const anoddpm_igemm_a
 
     // ---- epilogue, in registers (as winograd43r.hip): lane = (channel nw, tiles kq*4 .. kq*4+3); tile r sits in component r
     const float *TE = a.temb ? a.temb + (int64_t)b * a.temb_ld : nullptr;
-    const __amdgpu_buffer_rsrc_t rO = b4_rsrc(a.out + (int64_t)b * a.o_bs);
-    const __amdgpu_buffer_rsrc_t rR = b4_rsrc(a.res ? a.res + (int64_t)b * a.r_bs : a.out);
+    const __amdgpu_buffer_rsrc_t rO = buf_rsrc(a.out + (int64_t)b * a.o_bs);
+    const __amdgpu_buffer_rsrc_t rR = buf_rsrc(a.res ? a.res + (int64_t)b * a.r_bs : a.out);
     const bool has_res = a.res != nullptr;
     const unsigned uW = (unsigned)W, o_ld = (unsigned)a.out_ld, r_ld = (unsigned)a.res_ld;
     float add = 0.f;
@@ -270,14 +235,14 @@ __global__ __launch_bounds__(B4_NT, 1) void wino43b_kernel(const anoddpm_igemm_a
             float mu[6], o[4];
 #pragma unroll
             for (int u = 0; u < 6; ++u) mu[u] = acc[u * 6 + v][r];
-            b4_at6(mu, o);
+            at6(mu, o);
 #pragma unroll
             for (int i = 0; i < 4; ++i) y[i][v] = o[i];
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float o4[4];
-            b4_at6(y[i], o4);
+            at6(y[i], o4);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const unsigned so = ((unsigned)(r * 4) + (unsigned)i * uW + (unsigned)j) * 4u;

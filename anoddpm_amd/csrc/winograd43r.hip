@@ -18,16 +18,12 @@
 // 36 A-fragment reads (LDS) and 36 B-fragment loads (U[pos][k/4][n][4] from L2, six-deep register ring).
 #include <type_traits>
 
-#include "common.h"
+#include "f43.h"
 #include "gn_fold.h"
 
-using anoddpm::silu_f;
+using namespace anoddpm;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int R4_NT = 512;                 // threads: 8 waves
 constexpr int R4_KC = 16;                  // channels per K iteration
@@ -41,30 +37,6 @@ constexpr int R4_V = 36 * 16 * 4;                     // float4 per V buffer: [p
 constexpr int R4_KMAX = 1024;                         // input channels whose GroupNorm affine fits the LDS table (launcher: larger K is refused)
 constexpr int R4_AFF = 2 * R4_KMAX / 4;               // float4: [K/4] scales, then [K/4] shifts of this workgroup's image (K / 4 <= 256 <= threads)
 constexpr int R4_LDS_FLOATS = (2 * R4_DT + 2 * R4_V + R4_AFF) * 4;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const float *base)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7ffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 bld4(__amdgpu_buffer_rsrc_t r, unsigned lane_bytes, unsigned wave_bytes)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_bytes, (int)wave_bytes, 0));
-}
-template <int AUX>
-__device__ __forceinline__ f32x4 bld4x(__amdgpu_buffer_rsrc_t r, unsigned lane_bytes, unsigned wave_bytes)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_bytes, (int)wave_bytes, AUX));
-}
-
-// A^T of F(4x4,3x3) applied to six values: rows (1 1 1 1 1 0), (0 1 -1 2 -2 0), (0 1 1 4 4 0), (0 1 -1 8 -8 1)
-__device__ __forceinline__ void at6(const float (&m)[6], float (&o)[4])
-{
-    const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-    o[0] = m[0] + s12 + s34;
-    o[1] = d12 + 2.f * d34;
-    o[2] = s12 + 4.f * s34;
-    o[3] = d12 + 8.f * d34 + m[5];
-}
 
 // DBG (timing ablations only, wrong results; ANODDPM_DEBUG6): 1 no epilogue, 2 no input transform, 3 no patch staging, 4 no B requests
 // DBG 7: every patch request reads the tile's first pixel (same instruction stream, no HBM latency in the in-order vmcnt queue)
@@ -81,9 +53,6 @@ __device__ __forceinline__ void at6(const float (&m)[6], float (&o)[4])
 // 4..7 run T at position 18 instead of before position 0, so that a SIMD's MFMA-free transform block of one wave sits beside the
 // other wave's MFMAs); bit 1 = input transform in scalar f32 (v_fma_f32 with SGPR coefficients) instead of packed f32
 // F43_PAIR_TRANSFORM=1 (measurement builds, ANODDPM_EXTRA_FLAGS): the product launches use the row-pair input transform (VAR bit 5)
-#ifndef F43_PAIR_TRANSFORM
-#define F43_PAIR_TRANSFORM 0
-#endif
 constexpr int R4_VAR = F43_PAIR_TRANSFORM ? 32 : 0;
 // GNB (round 6, training): the launch is a data gradient and its epilogue also performs the reduction pass of the GroupNorm + SiLU
 // backward (anoddpm_igemm_args.gnb_*): the GroupNorm's input x rides in the residual slot of the epilogue (same requests, same
@@ -155,8 +124,8 @@ __global__ __launch_bounds__(R4_NT, 1) void wino43r_kernel(const anoddpm_igemm_a
     }
     f32x4 praw[R4_PJ];
     f32x4 asc = {1.f, 1.f, 1.f, 1.f}, ash = {0.f, 0.f, 0.f, 0.f};
-    const __amdgpu_buffer_rsrc_t rA0 = rsrc(A0), rA1 = rsrc(A1 ? A1 : A0);
-    const __amdgpu_buffer_rsrc_t rSc = rsrc(gsc ? gsc : A0), rSh = rsrc(gsh ? gsh : A0);
+    const __amdgpu_buffer_rsrc_t rA0 = buf_rsrc(A0), rA1 = buf_rsrc(A1 ? A1 : A0);
+    const __amdgpu_buffer_rsrc_t rSc = buf_rsrc(gsc ? gsc : A0), rSh = buf_rsrc(gsh ? gsh : A0);
     auto load_patch = [&](int chunk) {                              // unconditional loads, clamped addresses
         const int kbase = (cb + chunk) * R4_KC;
         const bool first = kbase < a.c0;
@@ -166,7 +135,7 @@ __global__ __launch_bounds__(R4_NT, 1) void wino43r_kernel(const anoddpm_igemm_a
 #pragma unroll
         for (int j = 0; j < R4_PJ; ++j) {
             const unsigned sp = (DBG == 7) ? (unsigned)(y0 * W + x0) : (spix[j] >= 0 ? (unsigned)spix[j] : 0u);
-            praw[j] = bld4x<PATCH_AUX>(r, (sp * ld + (unsigned)(pq * 4)) * 4u, koff);
+            praw[j] = buf_load4<PATCH_AUX>(r, (sp * ld + (unsigned)(pq * 4)) * 4u, koff);
         }
     };
     auto store_patch = [&](int buf, int chunk) {                    // GroupNorm-apply + SiLU, zero padding AFTER it
@@ -185,13 +154,7 @@ __global__ __launch_bounds__(R4_NT, 1) void wino43r_kernel(const anoddpm_igemm_a
                 const f32x4 same = {0.25f, -0.5f, 0.75f, 1.0f};
                 v = (praw[j][0] == 12345.678f) ? praw[j] : same;
             }
-            if (FAST) {
-                v = v * asc + ash;
-                v[0] = silu_f(v[0]); v[1] = silu_f(v[1]); v[2] = silu_f(v[2]); v[3] = silu_f(v[3]);
-            } else {
-                if (affine) v = v * asc + ash;
-                if (act) { v[0] = silu_f(v[0]); v[1] = silu_f(v[1]); v[2] = silu_f(v[2]); v[3] = silu_f(v[3]); }
-            }
+            v = f43_activate<FAST>(v, asc, ash, affine, act);
             ldsD[buf * R4_DT + (idx >> 2) * R4_PITCH + (idx & 3)] = spix[j] >= 0 ? v : zero;
         }
     };
@@ -208,14 +171,7 @@ __global__ __launch_bounds__(R4_NT, 1) void wino43r_kernel(const anoddpm_igemm_a
     const bool two_pass = wave >= 2 && wave <= 5;                   // wave-uniform
     constexpr int PASS_D = 8 * R4_PW * R4_PITCH * 2;                // tile row + 2 = patch row + 8 (float2 units)
     constexpr int PASS_V = 8 * 8;                                   // tile + 8 in V[pos][tile][pair]
-    // B^T row u as (patch row, coefficient) pairs -- every row of B^T touches at most four patch rows:
-    //   u0: 4 d0 - 5 d2 + d4        u1: -4 d1 - 4 d2 + d3 + d4     u2: 4 d1 - 4 d2 - d3 + d4
-    //   u3: -2 d1 - d2 + 2 d3 + d4  u4: 2 d1 - d2 - 2 d3 + d4      u5: 4 d1 - 5 d3 + d5
-    const int tr0 = (tu == 0) ? 0 : 1, tr1 = (tu == 5) ? 3 : 2, tr2 = (tu == 0) ? 4 : ((tu == 5) ? 5 : 3), tr3 = 4;
-    const float tc0 = (tu == 0) ? 4.f : (tu == 1 ? -4.f : (tu == 2 ? 4.f : (tu == 3 ? -2.f : (tu == 4 ? 2.f : 4.f))));
-    const float tc1 = (tu == 0 || tu == 5) ? -5.f : ((tu == 1 || tu == 2) ? -4.f : -1.f);
-    const float tc2 = (tu == 0 || tu == 5) ? 1.f : (tu == 1 ? 1.f : (tu == 2 ? -1.f : (tu == 3 ? 2.f : -2.f)));
-    const float tc3 = (tu == 0 || tu == 5) ? 0.f : 1.f;
+    F43_BT_ROW(tu);
     const int to0 = tr0 * R4_PW * R4_PITCH * 2, to1 = tr1 * R4_PW * R4_PITCH * 2, to2 = tr2 * R4_PW * R4_PITCH * 2, to3 = tr3 * R4_PW * R4_PITCH * 2;
     auto transform = [&](int pbuf, int vbuf, int dofs, int vofs) {
         const f32x2 *D = reinterpret_cast<const f32x2 *>(ldsD + pbuf * R4_DT) + tbase2 + dofs;
@@ -327,14 +283,14 @@ __global__ __launch_bounds__(R4_NT, 1) void wino43r_kernel(const anoddpm_igemm_a
 
     const int l15 = lane & 15, kq = lane >> 4;
     const int nw = n0 + wave * 16 + l15;                            // this lane's output channel
-    const __amdgpu_buffer_rsrc_t rU = rsrc(a.bmat);
+    const __amdgpu_buffer_rsrc_t rU = buf_rsrc(a.bmat);
     const unsigned xi_bytes = (unsigned)K4 * (unsigned)N * 16u;      // bytes per position of U
     const unsigned ulane = ((unsigned)kq * (unsigned)N + (unsigned)nw) * 16u;   // + chunk*4*N*16 + pos*xi_bytes
     const int vread = l15 * 4 + kq;                                  // + pos*64 float4
 
     f32x4 ring[R4_RING];
     auto load_b = [&](int chunk, int pos, int slot) {
-        ring[slot] = bld4(rU, ulane, (unsigned)pos * xi_bytes + (unsigned)((cb + chunk) * 4) * (unsigned)N * 16u);
+        ring[slot] = buf_load4(rU, ulane, (unsigned)pos * xi_bytes + (unsigned)((cb + chunk) * 4) * (unsigned)N * 16u);
     };
 
     // prologue: patch(0) -> LDS -> V(0); patch(1) -> LDS; patch(2) requested
@@ -345,8 +301,8 @@ __global__ __launch_bounds__(R4_NT, 1) void wino43r_kernel(const anoddpm_igemm_a
     const bool aff_slot = (FAST || affine) && tid < K4 && !fold;
     anoddpm::FoldLoads fl;
     if (aff_slot) {
-        aff_sc = bld4(rSc, (unsigned)(tid * 16), 0u);
-        aff_sh = bld4(rSh, (unsigned)(tid * 16), 0u);
+        aff_sc = buf_load4(rSc, (unsigned)(tid * 16), 0u);
+        aff_sh = buf_load4(rSh, (unsigned)(tid * 16), 0u);
     } else if (fold) {
         fl = anoddpm::fold_affine_request(a, b, tid);                 // oldest requests of the workgroup, like the table loads above
     }
@@ -459,12 +415,12 @@ __global__ __launch_bounds__(R4_NT, 1) void wino43r_kernel(const anoddpm_igemm_a
     // 256x256 128->128 layer; the stores of a round are HBM-burst-bound, not issue-bound.)
     const bool part = ksplit > 1;
     const float *TE = (a.temb && !part) ? a.temb + (int64_t)b * a.temb_ld : nullptr;
-    const __amdgpu_buffer_rsrc_t rO = part ? rsrc(a.ws + ((int64_t)ksi * a.B + b) * ((int64_t)H * W * N))
-                                           : rsrc(a.out + (int64_t)b * a.o_bs);
+    const __amdgpu_buffer_rsrc_t rO = part ? buf_rsrc(a.ws + ((int64_t)ksi * a.B + b) * ((int64_t)H * W * N))
+                                           : buf_rsrc(a.out + (int64_t)b * a.o_bs);
     // GNB: this wave's 16 channels of x come from the first or the second concatenated source (gnb_c0 % 16 == 0: wave-uniform)
     const bool gx_first = !GNB || n0 + wave * 16 < a.gnb_c0;
     const float *gx = !GNB ? nullptr : (gx_first ? a.gnb_x0 + (int64_t)b * a.gnb_x0_bs : a.gnb_x1 + (int64_t)b * a.gnb_x1_bs);
-    const __amdgpu_buffer_rsrc_t rR = GNB ? rsrc(gx) : rsrc(a.res ? a.res + (int64_t)b * a.r_bs : a.out);
+    const __amdgpu_buffer_rsrc_t rR = GNB ? buf_rsrc(gx) : buf_rsrc(a.res ? a.res + (int64_t)b * a.r_bs : a.out);
     const bool has_res = GNB || (a.res != nullptr && !part);
     const unsigned uW = (unsigned)W, o_ld = part ? (unsigned)N : (unsigned)a.out_ld;
     const unsigned r_ld = GNB ? (unsigned)(gx_first ? a.gnb_x0_ld : a.gnb_x1_ld) : (unsigned)a.res_ld;

@@ -19,15 +19,12 @@
 // tests); no plan selects it.
 #include <type_traits>
 
-#include "common.h"
+#include "f43.h"
 #include "gn_fold.h"
 
-using anoddpm::silu_f;
+using namespace anoddpm;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int W4_NT = 256;                 // threads: 4 waves, one per SIMD
 constexpr int W4_KC = 16;                  // channels per K iteration
@@ -41,25 +38,6 @@ constexpr int W4_V = 36 * 16 * 4;                     // float4 per V buffer: [p
 constexpr int W4_KMAX = 1024;
 constexpr int W4_AFF = 2 * W4_KMAX / 4;
 constexpr int W4_LDS_FLOATS = (2 * W4_DT + 2 * W4_V + W4_AFF) * 4;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrcw(const float *base)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7ffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 bldw(__amdgpu_buffer_rsrc_t r, unsigned lane_bytes, unsigned wave_bytes)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_bytes, (int)wave_bytes, 0));
-}
-
-// A^T of F(4x4,3x3) applied to six values: rows (1 1 1 1 1 0), (0 1 -1 2 -2 0), (0 1 1 4 4 0), (0 1 -1 8 -8 1)
-__device__ __forceinline__ void at6w(const float (&m)[6], float (&o)[4])
-{
-    const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-    o[0] = m[0] + s12 + s34;
-    o[1] = d12 + 2.f * d34;
-    o[2] = s12 + 4.f * s34;
-    o[3] = d12 + 8.f * d34 + m[5];
-}
 
 // W4_RING = positions of B fragments in flight (x 2 fragments each).  288 accumulator registers exceed the 256 AGPRs: hipcc keeps
 // every MFMA destination in an AGPR and moves the overflow through VGPRs (68-116 v_accvgpr moves per chunk); with 9 positions in
@@ -105,8 +83,8 @@ __global__ __launch_bounds__(W4_NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
     f32x4 praw[W4_PJ];
     f32x4 asc = {1.f, 1.f, 1.f, 1.f}, ash = {0.f, 0.f, 0.f, 0.f};
-    const __amdgpu_buffer_rsrc_t rA0 = rsrcw(A0), rA1 = rsrcw(A1 ? A1 : A0);
-    const __amdgpu_buffer_rsrc_t rSc = rsrcw(gsc ? gsc : A0), rSh = rsrcw(gsh ? gsh : A0);
+    const __amdgpu_buffer_rsrc_t rA0 = buf_rsrc(A0), rA1 = buf_rsrc(A1 ? A1 : A0);
+    const __amdgpu_buffer_rsrc_t rSc = buf_rsrc(gsc ? gsc : A0), rSh = buf_rsrc(gsh ? gsh : A0);
     auto load_patch = [&](int chunk) {                              // unconditional loads, clamped addresses
         const int kbase = chunk * W4_KC;
         const bool first = kbase < a.c0;
@@ -116,7 +94,7 @@ __global__ __launch_bounds__(W4_NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
         for (int j = 0; j < W4_PJ; ++j) {
             const unsigned sp = spix[j] >= 0 ? (unsigned)spix[j] : 0u;
-            praw[j] = bldw(r, (sp * ld + (unsigned)(pq * 4)) * 4u, koff);
+            praw[j] = buf_load4(r, (sp * ld + (unsigned)(pq * 4)) * 4u, koff);
         }
     };
     // GroupNorm-apply + SiLU of slots j0 .. j0 + 2, zero padding AFTER it (two halves: three slots each)
@@ -130,13 +108,7 @@ __global__ __launch_bounds__(W4_NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))
         for (int j = j0; j < j0 + 3; ++j) {
             const int idx = tid + j * W4_NT;
             f32x4 v = praw[j];
-            if (FAST) {
-                v = v * asc + ash;
-                v[0] = silu_f(v[0]); v[1] = silu_f(v[1]); v[2] = silu_f(v[2]); v[3] = silu_f(v[3]);
-            } else {
-                if (affine) v = v * asc + ash;
-                if (act) { v[0] = silu_f(v[0]); v[1] = silu_f(v[1]); v[2] = silu_f(v[2]); v[3] = silu_f(v[3]); }
-            }
+            v = f43_activate<FAST>(v, asc, ash, affine, act);
             ldsD[buf * W4_DT + (idx >> 2) * W4_PITCH + (idx & 3)] = spix[j] >= 0 ? v : zero;
         }
     };
@@ -154,11 +126,8 @@ __global__ __launch_bounds__(W4_NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))
     for (int ps = 0; ps < 3; ++ps) {
         const int v = wave + 4 * ps;
         const int tu = v % 6, pr = v / 6;
-        const int tr0 = (tu == 0) ? 0 : 1, tr1 = (tu == 5) ? 3 : 2, tr2 = (tu == 0) ? 4 : ((tu == 5) ? 5 : 3), tr3 = 4;
-        pg[ps].tc0 = (tu == 0) ? 4.f : (tu == 1 ? -4.f : (tu == 2 ? 4.f : (tu == 3 ? -2.f : (tu == 4 ? 2.f : 4.f))));
-        pg[ps].tc1 = (tu == 0 || tu == 5) ? -5.f : ((tu == 1 || tu == 2) ? -4.f : -1.f);
-        pg[ps].tc2 = (tu == 0 || tu == 5) ? 1.f : (tu == 1 ? 1.f : (tu == 2 ? -1.f : (tu == 3 ? 2.f : -2.f)));
-        pg[ps].tc3 = (tu == 0 || tu == 5) ? 0.f : 1.f;
+        F43_BT_ROW(tu);
+        pg[ps].tc0 = tc0; pg[ps].tc1 = tc1; pg[ps].tc2 = tc2; pg[ps].tc3 = tc3;
         pg[ps].to0 = tr0 * W4_PW * W4_PITCH * 2; pg[ps].to1 = tr1 * W4_PW * W4_PITCH * 2;
         pg[ps].to2 = tr2 * W4_PW * W4_PITCH * 2; pg[ps].to3 = tr3 * W4_PW * W4_PITCH * 2;
         pg[ps].dofs = pr * PASS_D;
@@ -201,7 +170,7 @@ __global__ __launch_bounds__(W4_NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))
 
     const int l15 = lane & 15, kq = lane >> 4;
     const int nw = n0 + wave * 32 + l15;                            // this lane's first output channel; the second is nw + 16
-    const __amdgpu_buffer_rsrc_t rU = rsrcw(a.bmat);
+    const __amdgpu_buffer_rsrc_t rU = buf_rsrc(a.bmat);
     const unsigned xi_bytes = (unsigned)K4 * (unsigned)N * 16u;      // bytes per position of U
     const unsigned ulane = ((unsigned)kq * (unsigned)N + (unsigned)nw) * 16u;
     const int vread = l15 * 4 + kq;
@@ -209,8 +178,8 @@ __global__ __launch_bounds__(W4_NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))
     f32x4 ring0[W4_RING], ring1[W4_RING];
     auto load_b = [&](int chunk, int pos, int slot) {
         const unsigned w = (unsigned)pos * xi_bytes + (unsigned)(chunk * 4) * (unsigned)N * 16u;
-        ring0[slot] = bldw(rU, ulane, w);
-        ring1[slot] = bldw(rU, ulane + 256u, w);
+        ring0[slot] = buf_load4(rU, ulane, w);
+        ring1[slot] = buf_load4(rU, ulane + 256u, w);
     };
 
     // prologue: patch(0) -> LDS -> V(0); patch(1) -> LDS; patch(2) requested
@@ -220,8 +189,8 @@ __global__ __launch_bounds__(W4_NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))
     const bool aff_slot = (FAST || affine) && tid < K4 && !fold;
     anoddpm::FoldLoads fl;
     if (aff_slot) {
-        aff_sc = bldw(rSc, (unsigned)(tid * 16), 0u);
-        aff_sh = bldw(rSh, (unsigned)(tid * 16), 0u);
+        aff_sc = buf_load4(rSc, (unsigned)(tid * 16), 0u);
+        aff_sh = buf_load4(rSh, (unsigned)(tid * 16), 0u);
     } else if (fold) {
         fl = anoddpm::fold_affine_request(a, b, tid);
     }
@@ -300,8 +269,8 @@ __global__ __launch_bounds__(W4_NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))
 
     // ---- epilogue, in registers: lane = (channels nw and nw + 16, tiles kq*4 .. kq*4+3); tile r of the lane sits in component r
     const float *TE = a.temb ? a.temb + (int64_t)b * a.temb_ld : nullptr;
-    const __amdgpu_buffer_rsrc_t rO = rsrcw(a.out + (int64_t)b * a.o_bs);
-    const __amdgpu_buffer_rsrc_t rR = rsrcw(a.res ? a.res + (int64_t)b * a.r_bs : a.out);
+    const __amdgpu_buffer_rsrc_t rO = buf_rsrc(a.out + (int64_t)b * a.o_bs);
+    const __amdgpu_buffer_rsrc_t rR = buf_rsrc(a.res ? a.res + (int64_t)b * a.r_bs : a.out);
     const bool has_res = a.res != nullptr;
     const unsigned uW = (unsigned)W, o_ld = (unsigned)a.out_ld, r_ld = (unsigned)a.res_ld;
     const float alpha = a.alpha;
@@ -357,14 +326,14 @@ __global__ __launch_bounds__(W4_NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))
                 float mu[6], o[4];
 #pragma unroll
                 for (int u = 0; u < 6; ++u) mu[u] = g == 0 ? acc0[u * 6 + v][r] : acc1[u * 6 + v][r];
-                at6w(mu, o);
+                at6(mu, o);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) y[i][v] = o[i];
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float o4[4];
-                at6w(y[i], o4);
+                at6(y[i], o4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const unsigned so = ((unsigned)(r * 4) + (unsigned)i * uW + (unsigned)j) * 4u;
