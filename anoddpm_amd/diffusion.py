@@ -627,14 +627,14 @@ class _FusedLoss(torch.autograd.Function):
 
 class GaussianDiffusionModel:
     # opt-in post-processing of the detection records (metrics.PostProcess, and an optional 0 / 1 region-of-interest tensor shaped
-    # like one image or like x_0): see _attach_postprocessed.  Plain attributes: pickled and deep-copied with the instance.
+    # like one image or like x_0): see _score_settings.  Plain attributes: pickled and deep-copied with the instance.
     postprocess = None
     postprocess_roi = None
     # opt-in per-region overlap score of the detection records: a false-positive-rate limit in (0, 1] (0.3 in the literature); see
-    # _attach_pro.  A plain attribute like `postprocess`.
+    # _score_settings.  A plain attribute like `postprocess`.
     pro_limit = None
     # opt-in boundary distances of the detection records (Hausdorff, HD95, average symmetric surface distance of the thresholded
-    # map against the mask); see _attach_surface.  A plain attribute like `postprocess`.
+    # map against the mask); see _score_settings.  A plain attribute like `postprocess`.
     surface_metrics = False
     # opt-in strided reverse sampler (StridedSampler; None: the reference's ancestral sampler, and none of the strided code runs).
     # Read by ReverseChain / reverse_chain / forward_backward and the detection loops unless they are handed `sampler=`; also set at
@@ -1285,126 +1285,39 @@ class GaussianDiffusionModel:
             chain.finish()
         return out
 
-    @staticmethod
-    def _scatter_scores(records, mask, scores, suffix):
-        """ONE batched ROC launch (metrics.curve_scores) on `scores` [R, ...], one segment per record -> the [R] status words, and in
-        the records `auc`, `ap`, `best_dice` (fp64 device scalars; NaN when the class they need is empty or the status is non-zero)
-        and `best_threshold` (fp32: the highest threshold that reaches the best Dice), each + suffix.  Never raises or synchronises."""
-        from . import metrics
-        o = metrics.curve_scores(mask, scores, batched=True)
-        for j, rec in enumerate(records):
-            for k in ("auc", "ap", "best_dice", "best_threshold"):
-                rec[k + suffix] = o[k][j]
-        return o["status"]
-
-    def _attach_auc(self, records, sqerrs, mask):
-        """detection.py:230-231 for every setting of a sweep, with `ap` / `best_dice` from the same launch (`_scatter_scores`) and `auc_status`."""
-        if mask is not None and records:
-            status = self._scatter_scores(records, mask, torch.stack([s.reshape(-1) for s in sqerrs]), "")
-            for j, rec in enumerate(records):
-                rec["auc_status"] = status[j]
-
-    @staticmethod
-    def _attach_ssim(records, x_0):
-        """detection.py:241-246 for every setting of a sweep in ONE launch: `ssim`, an fp64 device tensor `[B]`, the SSIM of every
-        image of `x_0` against the record's `mean` image (7 x 7 uniform window, data_range 2.0).  `x_0` is read in place by every
-        setting when B == 1 (segment stride 0).  Stays None for images smaller than the window.  Never synchronises."""
-        if not records or x_0.dim() != 4 or min(x_0.shape[-2:]) < 7:
-            return
-        from . import metrics
-        B = x_0.shape[0]
-        means = torch.stack([rec["mean"] for rec in records])       # [R, B, C, H, W]
-        real = x_0[0] if B == 1 else x_0.unsqueeze(0).expand_as(means)
-        val = metrics.ssim(real, means).reshape(len(records), B)
-        for j, rec in enumerate(records):
-            rec["ssim"] = val[j]
-
-    def _attach_postprocessed(self, records, sqerrs, mask, x_0):
-        """Opt-in (`self.postprocess`, a metrics.PostProcess): the squared-error maps of every setting of a sweep after the median
-        filter inside the eroded region of interest (`self.postprocess_roi`, else `x_0 > postprocess.roi_level`, else the whole
-        image) -- ONE erosion launch, ONE median launch over all settings' maps -- as `sqerr_pp`, and with a mask ONE ROC launch on
-        them: `auc_pp`, `ap_pp`, `best_dice_pp` (fp64 device scalars, NaN as `auc` / `ap` / `best_dice`) and `best_threshold_pp`
-        (None without a mask).  Without `self.postprocess` the records keep exactly their keys.  Never synchronises."""
-        pp = self.postprocess
-        if pp is None or not records:
-            return
-        from . import metrics
-        filtered = metrics.postprocess_maps(torch.stack(sqerrs), pp, real=x_0, roi=self.postprocess_roi)     # [R, B, C, H, W]
-        for j, rec in enumerate(records):
-            rec["sqerr_pp"] = filtered[j]
-            rec["auc_pp"] = rec["ap_pp"] = rec["best_dice_pp"] = rec["best_threshold_pp"] = None
-        if mask is not None:
-            self._scatter_scores(records, mask, filtered.reshape(len(records), -1), "_pp")
-
-    def _attach_pro(self, records, sqerrs, mask):
-        """Opt-in (`self.pro_limit`): `aupro`, the area under the per-region overlap curve up to that false-positive rate
-        (metrics.aupro: all planes of a setting's squared-error map one segment, regions with 8 neighbours), and `aupro_pp` on
-        `sqerr_pp` when post-processing is on -- ONE component launch on the mask every setting shares and ONE PRO launch over
-        all maps.  fp64 device scalars, NaN as `auc`; None without a mask.  Without `self.pro_limit` the records keep exactly
-        their keys.  Never synchronises."""
-        if self.pro_limit is None or not records:
-            return
-        from . import metrics
-        pp = "sqerr_pp" in records[0]
-        for rec in records:
-            rec["aupro"] = None
-            if pp:
-                rec["aupro_pp"] = None
-        if mask is None:
-            return
-        maps = list(sqerrs) + ([rec["sqerr_pp"] for rec in records] if pp else [])
-        val = metrics.aupro(mask, torch.stack(maps), limit=self.pro_limit, batched=True)
-        for j, rec in enumerate(records):
-            rec["aupro"] = val[j]
-            if pp:
-                rec["aupro_pp"] = val[len(records) + j]
-
-    def _attach_surface(self, records, mask):
-        """Opt-in (`self.surface_metrics`, with a mask): `hd`, `hd95`, `assd` of every setting's thresholded map (the record's
-        `threshold` image, > 0) against the mask -- metrics.surface_distance, ONE batched call for all settings, the mask shared
-        when it is one plane -- and with post-processing `hd_pp`, `hd95_pp`, `assd_pp` of the filtered map cut at 0.5 without its
-        components below `postprocess.min_size` pixels, from the same call.  fp64 device scalars: the mean over the record's
-        planes whose two borders exist, NaN when there is none.  Without `self.surface_metrics` or without a mask the records keep
-        exactly their keys.  Never synchronises."""
-        if not self.surface_metrics or mask is None or not records:
-            return
-        from . import metrics
-        R = len(records)
-        preds = [torch.stack([rec["threshold"] for rec in records])]                                        # [R, B, C, H, W], -1 / 1
-        suffixes = [""]
-        if "sqerr_pp" in records[0]:
-            pp = self.postprocess
-            cut, _ = metrics._small_components(torch.stack([rec["sqerr_pp"] for rec in records]), 0.5, pp.min_size, pp.connectivity)
-            preds.append(cut.reshape(preds[0].shape))
-            suffixes.append("_pp")
-        H, W = preds[0].shape[-2:]
-        pred = torch.stack(preds).reshape(len(suffixes) * R, -1, H, W)
-        ref = mask.reshape(-1, H, W)
-        ref = ref[0] if ref.shape[0] == 1 else ref.unsqueeze(0).expand(pred.shape)
-        o = metrics.surface_distance(pred, ref)
-        for k in ("hd", "hd95", "assd"):
-            val = metrics._valid_mean(o[k], o["status"])[0]
-            for i, sfx in enumerate(suffixes):
-                for j, rec in enumerate(records):
-                    rec[k + sfx] = val[i * R + j]
+    # A record's scores, under the names `metrics.score_maps` gives them: (key, the options that put the key into every record --
+    # None where nothing fills it; None: only when it is filled).  Row j of the result belongs to record j.
+    _RECORD_SCORES = tuple((k, ()) for k in ("auc", "auc_status", "ap", "best_dice", "best_threshold", "ssim")) \
+        + tuple((k, ("postprocess",)) for k in ("sqerr_pp", "auc_pp", "ap_pp", "best_dice_pp", "best_threshold_pp")) \
+        + (("aupro", ("pro_limit",)), ("aupro_pp", ("pro_limit", "postprocess"))) \
+        + tuple((k, None) for k in ("hd", "hd95", "assd", "hd_pp", "hd95_pp", "assd_pp"))
 
     def _score_settings(self, settings, outputs, total_avg, x_0, mask):
         """The end of detection_A / detection_B: settings[j] (the keys that name a setting) owns the `total_avg` chains
-        outputs[j * total_avg:(j + 1) * total_avg]; one record per setting, in that order, scored -> `self.last_detection`.  A
-        score stays None where nothing fills it (`_attach_auc` needs a mask, `_attach_ssim` images of the window's size)."""
+        outputs[j * total_avg:(j + 1) * total_avg]; one record per setting, in that order -> `self.last_detection`.  The mean / mse /
+        threshold images and the counts come from one fused pass per setting, every score of `_RECORD_SCORES` from ONE
+        `metrics.score_maps` over all settings (one launch per step for the whole sweep; fp64 device scalars, `ssim` [B] per record;
+        never synchronises).  `auc` ... `ssim` stay None where nothing fills them (no mask, images below the SSIM window); the opt-in
+        `self.postprocess` (with `self.postprocess_roi`) and `self.pro_limit` add their keys, None without a mask;
+        `self.surface_metrics` adds `hd`, `hd95`, `assd` (and `_pp`) only with a mask.  All unset: exactly the first six."""
         from . import metrics
-        self.last_detection, sqerrs = [], []
+        self.last_detection, stacks = [], {"mean": [], "sqerr": [], "thr_img": []}
         for j, extra in enumerate(settings):
             output = outputs[j * total_avg:(j + 1) * total_avg].clone()
             maps, counts = metrics.anomaly_maps(x_0, output, mask, threshold=0.5)
-            self.last_detection.append(dict(extra, output=output, mean=maps["mean"], mse=maps["mse_img"], threshold=maps["thr_img"], counts=counts,
-                                            auc=None, auc_status=None, ap=None, best_dice=None, best_threshold=None, ssim=None))
-            sqerrs.append(maps["sqerr"])
-        self._attach_auc(self.last_detection, sqerrs, mask)
-        self._attach_ssim(self.last_detection, x_0)
-        self._attach_postprocessed(self.last_detection, sqerrs, mask, x_0)
-        self._attach_pro(self.last_detection, sqerrs, mask)
-        self._attach_surface(self.last_detection, mask)
+            self.last_detection.append(dict(extra, output=output, mean=maps["mean"], mse=maps["mse_img"], threshold=maps["thr_img"], counts=counts))
+            for k, stack in stacks.items():
+                stack.append(maps[k])
+        if not settings:
+            return
+        scores = metrics.score_maps(x_0, *(torch.stack(stacks[k]) for k in ("mean", "sqerr", "thr_img")), mask, postprocess=self.postprocess,
+                                    roi=self.postprocess_roi, pro_limit=self.pro_limit, surface=bool(self.surface_metrics))
+        for j, rec in enumerate(self.last_detection):
+            for key, options in self._RECORD_SCORES:
+                if key in scores:
+                    rec[key] = scores[key][j]
+                elif options is not None and all(getattr(self, o) is not None for o in options):
+                    rec[key] = None
 
     def detection_A(self, model, x_0, args, file, mask, total_avg=2):
         """GaussianDiffusion.py:480-529: simplex frequencies 2^7..2^1 x t_distance 50..0.6T step 50, `total_avg` chains each -- all

@@ -37,15 +37,13 @@ median-filter the residual, restrict it to an eroded brain mask and drop tiny co
 report AP and Dice.  `median_filter` (scipy.ndimage.median_filter, windows 3 / 5 / 7, reflect border), `erode_mask`
 (scipy.ndimage.binary_erosion, cross, 1 ... 8 iterations) and `remove_small_components` (scipy.ndimage.label + bincount) do that
 on the device (csrc/postproc.hip), batched over all maps of a sweep, bit for bit what scipy returns and without a host
-synchronisation.  `PostProcess` holds the settings; `anomaly_metrics(..., postprocess=pp)` and the detection records add `_pp`
-results beside the raw ones.  Everything is opt-in: without it nothing changes.
+synchronisation.  `PostProcess` holds the settings; the `_pp` results stand beside the raw ones.  Everything is opt-in: without it nothing changes.
 
 Per-region overlap (Bergmann et al., "The MVTec Anomaly Detection Dataset", IJCV 2021; the reference has no counterpart).  Every
 score above is pixel-wise, so one large lesion decides it; the PRO curve gives every connected ground-truth region the same weight
 and AUPRO integrates it up to a false-positive rate of 0.3.  `component_areas` (csrc/postproc.hip) gives every mask pixel the size
 of its region, `aupro` sorts `(score, area)` pairs and walks the curve in ONE launch per batch (`anoddpm_pro_auc`, csrc/pro.hip: one
 workgroup per segment, fp64 sums in a fixed order -- same input, same bits), `pro_points` returns the curve, `AUPRO` a Python float.
-`anomaly_metrics_pro(..., pro_limit=0.3)` and `GaussianDiffusionModel.pro_limit` add it to their results; unset, nothing changes.
 
 Boundary distances (the reference has no counterpart): how far the predicted outline lies from the true one, which no overlap score
 says.  `distance_transform` is `scipy.ndimage.distance_transform_edt(plane > level)` of every plane of a batch (csrc/surface.hip: a
@@ -53,10 +51,15 @@ sweep down and up every column, then per row the integer minimum over `(x - x')^
 Hausdorff distance, its 95th percentile (`hd95`, medpy's pooled form) and the average symmetric surface distance of every
 prediction against its reference or against one shared reference, in four launches whatever the batch: the order statistics are
 selected on the integer squared distances and the means are fp64 sums in a fixed order, so the same input gives the same bits.
-`HD95` returns a Python float; `anomaly_metrics_surface` and `GaussianDiffusionModel.surface_metrics` add the three to their
-results; unset, nothing changes.  Pixel units only (no `sampling=`), 2-D planes only, one threshold per call.
+`HD95` returns a Python float.  Pixel units only (no `sampling=`), 2-D planes only, one threshold per call.
 
-`anomaly_metrics` is the native entry: everything the metric loop needs from one launch and one 96-byte D2H copy (plus the AUC launch).
+`score_maps` states the scoring pipeline once: R stacks of maps in, one launch per step whatever R is -- curve scores, SSIM, and
+opt-in the post-processing with its own curve scores, AUPRO and the boundary distances -- a dict of device tensors with a leading
+R axis out, without a host synchronisation; a score that cannot be computed has no key.  Its callers only say how a result
+leaves: `anomaly_metrics` (with `postprocess`), `anomaly_metrics_pro` (`pro_limit`) and `anomaly_metrics_surface` run it with
+R = 1 behind one fused `anomaly_maps` pass, copy every number to the host at once and return Python floats (NaN where there is no
+score); `GaussianDiffusionModel._score_settings` (with `postprocess`, `pro_limit`, `surface_metrics`) runs it once over all
+settings of a sweep and puts row j into record j as device tensors (None where there is no score).
 The individual functions accept the reference's arguments; they use the fused pass when handed device tensors of
 the shapes the reference passes and raise `AnoddpmError` otherwise (no CPU path)."""
 import ctypes
@@ -67,7 +70,7 @@ from . import _lib
 from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs, ErodeArgs, MedianArgs, ProArgs, RocArgs, SsimArgs, SurfaceArgs, check,
                    current_stream, lib)
 
-__all__ = ["anomaly_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "median_filter", "erode_mask",
+__all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "median_filter", "erode_mask",
            "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "aupro", "pro_points", "AUPRO", "distance_transform",
            "surface_distance", "HD95", "anomaly_metrics_surface", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
@@ -80,6 +83,35 @@ def _f32c(x, name):
     if x.dtype != torch.float32:
         x = x.float()
     return x.contiguous()
+
+
+def _launch(name, a, dev, workspace=None):
+    """The tail of every wrapper: `anoddpm_<name>(a)` on dev's current stream.  `workspace`: `(nbytes, dtype, text)` -- what the
+    entry point's `*_workspace_bytes` answered (negative: ValueError(text)), allocated as `dtype` elements into `a.workspace` /
+    `a.workspace_bytes`."""
+    if workspace is not None:
+        nbytes, dtype, text = workspace
+        if nbytes < 0:
+            raise ValueError(text)
+        ws = torch.empty((nbytes // dtype.itemsize,), dtype=dtype, device=dev)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    with torch.cuda.device(dev):
+        check(getattr(lib(), "anoddpm_" + name)(ctypes.byref(a), current_stream()), name)
+
+
+def _nan_where_status(o, key):
+    """`o[key]` of a launch's results with NaN where its status word is non-zero."""
+    return torch.where(o["status"] != 0, torch.full_like(o[key], float("nan")), o[key])
+
+
+def _curve_buffers(out, second, dtype, S, cap, dev):
+    """The curve arrays of a ROC / PRO launch into `out` -- `fps`, `second` (`tps` / `pro`, of `dtype`), `thresholds` [S, cap] and
+    `len` [S] -- and their pointers with `cap`, in the order of the `curve_*` fields of the argument structs."""
+    out["fps"] = torch.empty((S, cap), dtype=torch.int32, device=dev)
+    out[second] = torch.empty((S, cap), dtype=dtype, device=dev)
+    out["thresholds"] = torch.empty((S, cap), dtype=torch.float32, device=dev)
+    out["len"] = torch.empty((S,), dtype=torch.int32, device=dev)
+    return out["fps"].data_ptr(), out[second].data_ptr(), out["thresholds"].data_ptr(), out["len"].data_ptr(), cap
 
 
 def anomaly_maps(real, recon, mask=None, threshold=0.5, want=("mean", "sqerr", "mse_img", "thr_img", "pred")):
@@ -188,25 +220,15 @@ def _roc_launch(mask, score, batched, curve, pr=False):
     if mk.device != sc.device:
         raise ValueError("roc: mask and score are on different devices")
     dev = sc.device
-    nbytes = lib().anoddpm_roc_workspace_bytes(S, n)
-    if nbytes < 0:
-        raise ValueError(f"roc: segment length {n} is outside [1, 2^31)")
-    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
     out = {"auc": torch.empty((S,), dtype=torch.float64, device=dev),
            "counts": torch.empty((S, 4), dtype=torch.int64, device=dev),
            "status": torch.empty((S,), dtype=torch.int32, device=dev), "n": n}
     a = RocArgs()
-    a.score, a.mask, a.workspace, a.workspace_bytes = sc.data_ptr(), mk.data_ptr(), ws.data_ptr(), nbytes
+    a.score, a.mask = sc.data_ptr(), mk.data_ptr()
     a.auc, a.counts, a.status = out["auc"].data_ptr(), out["counts"].data_ptr(), out["status"].data_ptr()
     a.n, a.score_stride, a.mask_stride, a.S = n, s_stride, m_stride, S
-    if curve:
-        cap = max(n, 2)                                              # a segment has at most n distinct scores
-        out["fps"] = torch.empty((S, cap), dtype=torch.int32, device=dev)
-        out["tps"] = torch.empty((S, cap), dtype=torch.int32, device=dev)
-        out["thresholds"] = torch.empty((S, cap), dtype=torch.float32, device=dev)
-        out["len"] = torch.empty((S,), dtype=torch.int32, device=dev)
-        a.curve_fps, a.curve_tps, a.curve_thr = out["fps"].data_ptr(), out["tps"].data_ptr(), out["thresholds"].data_ptr()
-        a.curve_len, a.curve_cap = out["len"].data_ptr(), cap
+    if curve:                                                        # a segment has at most n distinct scores
+        a.curve_fps, a.curve_tps, a.curve_thr, a.curve_len, a.curve_cap = _curve_buffers(out, "tps", torch.int32, S, max(n, 2), dev)
         a.curve_mode = _lib.ROC_CURVE_ALL if pr else _lib.ROC_CURVE_DROP
     if pr:
         out["ap"] = torch.empty((S,), dtype=torch.float64, device=dev)
@@ -215,8 +237,7 @@ def _roc_launch(mask, score, batched, curve, pr=False):
         out["best_counts"] = torch.empty((S, 2), dtype=torch.int64, device=dev)
         a.ap, a.best_dice = out["ap"].data_ptr(), out["best_dice"].data_ptr()
         a.best_thr, a.best_counts = out["best_threshold"].data_ptr(), out["best_counts"].data_ptr()
-    with torch.cuda.device(dev):
-        check(lib().anoddpm_roc_auc(ctypes.byref(a), current_stream()), "roc_auc")
+    _launch("roc_auc", a, dev, (lib().anoddpm_roc_workspace_bytes(S, n), torch.int32, f"roc: segment length {n} is outside [1, 2^31)"))
     return out
 
 
@@ -231,7 +252,7 @@ def roc_auc(mask, score, batched=None, return_status=False):
     synchronisation: NaN where a class is empty, and NaN where the inputs break the precondition (`return_status=True` also
     returns the [S] int32 status words)."""
     o = _roc_launch(mask, score, _is_batched(score, batched), curve=False)
-    auc = torch.where(o["status"] != 0, torch.full_like(o["auc"], float("nan")), o["auc"])
+    auc = _nan_where_status(o, "auc")
     return (auc, o["status"]) if return_status else auc
 
 
@@ -251,7 +272,7 @@ def curve_scores(mask, score, batched):
     synchronisation -- `auc`, `ap`, `best_dice` (fp64; NaN where `status`, the kernel's int32 word, is non-zero or the class they
     need is empty), `best_threshold` (fp32) and `best_counts` (int64 [S, 2]: tp and fp at that threshold)."""
     o = _roc_launch(mask, score, batched, curve=False, pr=True)
-    out = {k: torch.where(o["status"] != 0, torch.full_like(o[k], float("nan")), o[k]) for k in ("auc", "ap", "best_dice")}
+    out = {k: _nan_where_status(o, k) for k in ("auc", "ap", "best_dice")}
     out.update(best_threshold=o["best_threshold"], best_counts=o["best_counts"], status=o["status"])
     return out
 
@@ -349,20 +370,15 @@ def ssim(real, recon, batched=None, data_range=2.0, win_size=7, gaussian_weights
     else:
         raise ValueError(f"ssim: real {tuple(real.shape)} does not match recon {tuple(recon.shape)}")
     dev = rc.device
-    nbytes = lib().anoddpm_ssim_workspace_bytes(S, C, H, W)
-    if nbytes < 0:
-        raise ValueError(f"ssim: {S} x {C} x {H} x {W} is too large for one launch")
-    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
     out = torch.empty((S,), dtype=torch.float64, device=dev)
     smap = torch.empty(tuple(recon.shape), dtype=torch.float32, device=dev) if full else None
     a = SsimArgs()
-    a.real, a.recon, a.workspace, a.workspace_bytes = rl.data_ptr(), rc.data_ptr(), ws.data_ptr(), nbytes
+    a.real, a.recon = rl.data_ptr(), rc.data_ptr()
     a.mssim, a.map = out.data_ptr(), (smap.data_ptr() if full else None)
     a.real_stride, a.recon_stride = real_stride, n
     a.cn, a.data_range, a.K1, a.K2 = cn, float(data_range), SSIM_K1, SSIM_K2
     a.S, a.C, a.H, a.W, a.win, a.mode = S, C, H, W, win, mode
-    with torch.cuda.device(dev):
-        check(lib().anoddpm_ssim(ctypes.byref(a), current_stream()), "ssim")
+    _launch("ssim", a, dev, (lib().anoddpm_ssim_workspace_bytes(S, C, H, W), torch.float64, f"ssim: {S} x {C} x {H} x {W} is too large for one launch"))
     return (out, smap) if full else out
 
 # ---------------------------------------------------------------------------------- post-processing on the device
@@ -427,8 +443,7 @@ def median_filter(score, size=5, roi=None, batched=None, return_status=False):
     status = torch.empty(tuple(score.shape[:-2]), dtype=torch.int32, device=dev)
     a.src, a.dst, a.status, a.src_stride = sc.data_ptr(), out.data_ptr(), status.data_ptr(), s_stride
     a.S, a.H, a.W, a.k = S * C, H, W, int(size)
-    with torch.cuda.device(dev):
-        check(lib().anoddpm_median2d(ctypes.byref(a), current_stream()), "median2d")
+    _launch("median2d", a, dev)
     return (out, status) if return_status else out
 
 
@@ -446,8 +461,7 @@ def erode_mask(x, iterations=3, level=0.0):
     a = ErodeArgs()
     a.src, a.dst, a.src_stride = xt.data_ptr(), out.data_ptr(), H * W
     a.S, a.H, a.W, a.n, a.level = C, H, W, int(iterations), float(level)
-    with torch.cuda.device(xt.device):
-        check(lib().anoddpm_erode2d(ctypes.byref(a), current_stream()), "erode2d")
+    _launch("erode2d", a, xt.device)
     return out
 
 
@@ -466,18 +480,14 @@ def _small_components(x, level, min_size, connectivity):
     S, C, H, W = _planes(x, False, "remove_small_components")
     xt = _f32c(x, "remove_small_components(pred)")
     dev = xt.device
-    nbytes = lib().anoddpm_small_components_workspace_bytes(C, H, W)
-    if nbytes < 0:
-        raise ValueError(f"remove_small_components: {tuple(x.shape)} has 2^31 pixels or more")
-    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
     out = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)
     counts = torch.empty(tuple(x.shape[:-2]) + (2,), dtype=torch.int64, device=dev)
     a = ComponentsArgs()
-    a.src, a.dst, a.counts, a.workspace, a.workspace_bytes = xt.data_ptr(), out.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes
+    a.src, a.dst, a.counts = xt.data_ptr(), out.data_ptr(), counts.data_ptr()
     a.src_stride, a.S, a.H, a.W = H * W, C, H, W
     a.min_size, a.connectivity, a.level = int(min_size), int(connectivity), float(level)
-    with torch.cuda.device(dev):
-        check(lib().anoddpm_small_components(ctypes.byref(a), current_stream()), "small_components")
+    _launch("small_components", a, dev, (lib().anoddpm_small_components_workspace_bytes(C, H, W), torch.int32,
+                                         f"remove_small_components: {tuple(x.shape)} has 2^31 pixels or more"))
     return out, counts
 
 
@@ -574,18 +584,14 @@ def component_areas(mask, connectivity=2, level=0.0, batched=None):
     S, C, H, W = _planes(mask, _is_batched(mask, batched), "component_areas")
     xt = _f32c(mask, "component_areas(mask)")
     dev = xt.device
-    nbytes = lib().anoddpm_small_components_workspace_bytes(S * C, H, W)
-    if nbytes < 0:
-        raise ValueError(f"component_areas: {tuple(mask.shape)} has 2^31 pixels or more")
-    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
     areas = torch.empty(tuple(mask.shape), dtype=torch.int32, device=dev)
     counts = torch.empty(tuple(mask.shape[:-2]), dtype=torch.int64, device=dev)
     a = ComponentAreasArgs()
-    a.src, a.area, a.counts, a.workspace, a.workspace_bytes = xt.data_ptr(), areas.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes
+    a.src, a.area, a.counts = xt.data_ptr(), areas.data_ptr(), counts.data_ptr()
     a.src_stride, a.S, a.H, a.W = H * W, S * C, H, W
     a.connectivity, a.level = int(connectivity), float(level)
-    with torch.cuda.device(dev):
-        check(lib().anoddpm_component_areas(ctypes.byref(a), current_stream()), "component_areas")
+    _launch("component_areas", a, dev, (lib().anoddpm_small_components_workspace_bytes(S * C, H, W), torch.int32,
+                                        f"component_areas: {tuple(mask.shape)} has 2^31 pixels or more"))
     return areas, counts
 
 
@@ -608,30 +614,18 @@ def _pro_launch(mask, score, limit, connectivity, batched, curve):
     if mk.device != sc.device:
         raise ValueError("pro: mask and score are on different devices")
     dev = sc.device
-    nbytes = lib().anoddpm_pro_workspace_bytes(S, n)
-    if nbytes < 0:
-        raise ValueError(f"pro: segment length {n} is outside [1, 2^31)")
     areas, regions = component_areas(mk.reshape(-1, H, W), connectivity, batched=True)
-    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
     out = {"aupro": torch.empty((S,), dtype=torch.float64, device=dev),
            "counts": torch.empty((S, 4), dtype=torch.int64, device=dev),
            "status": torch.empty((S,), dtype=torch.int32, device=dev), "n": n}
     a = ProArgs()
     a.score, a.area, a.region_counts, a.mask = sc.data_ptr(), areas.data_ptr(), regions.data_ptr(), mk.data_ptr()
-    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
     a.aupro, a.counts, a.status = out["aupro"].data_ptr(), out["counts"].data_ptr(), out["status"].data_ptr()
     a.score_stride, a.area_stride, a.mask_stride = s_stride, (0 if shared else n), (0 if shared else n)
     a.limit, a.S, a.planes_per_segment, a.H, a.W = float(limit), S, C, H, W
-    if curve:
-        cap = n                                                      # a segment has at most n distinct scores
-        out["fps"] = torch.empty((S, cap), dtype=torch.int32, device=dev)
-        out["pro"] = torch.empty((S, cap), dtype=torch.float64, device=dev)
-        out["thresholds"] = torch.empty((S, cap), dtype=torch.float32, device=dev)
-        out["len"] = torch.empty((S,), dtype=torch.int32, device=dev)
-        a.curve_fps, a.curve_pro, a.curve_thr = out["fps"].data_ptr(), out["pro"].data_ptr(), out["thresholds"].data_ptr()
-        a.curve_len, a.curve_cap = out["len"].data_ptr(), cap
-    with torch.cuda.device(dev):
-        check(lib().anoddpm_pro_auc(ctypes.byref(a), current_stream()), "pro_auc")
+    if curve:                                                        # a segment has at most n distinct scores
+        a.curve_fps, a.curve_pro, a.curve_thr, a.curve_len, a.curve_cap = _curve_buffers(out, "pro", torch.float64, S, n, dev)
+    _launch("pro_auc", a, dev, (lib().anoddpm_pro_workspace_bytes(S, n), torch.float64, f"pro: segment length {n} is outside [1, 2^31)"))
     return out
 
 
@@ -645,7 +639,7 @@ def aupro(mask, score, limit=0.3, connectivity=2, batched=None, return_status=Fa
     run.  NaN where the mask has no region or no background, and where the inputs break the precondition of `roc_auc`
     (`return_status=True` also returns the [S] int32 status words)."""
     o = _pro_launch(mask, score, limit, connectivity, _is_batched(score, batched), curve=False)
-    val = torch.where(o["status"] != 0, torch.full_like(o["aupro"], float("nan")), o["aupro"])
+    val = _nan_where_status(o, "aupro")
     return (val, o["status"]) if return_status else val
 
 
@@ -662,11 +656,10 @@ def pro_points(mask, score, limit=0.3, connectivity=2, batched=None):
 
 
 # ---------------------------------------------------------------------------------- distance transform and boundary distances
-def _surface_workspace(S, H, W, what):
-    nbytes = lib().anoddpm_surface_workspace_bytes(S, H, W)
-    if nbytes < 0:
-        raise ValueError(f"{what}: {S} planes of {H} x {W} are too large: (H-1)^2 + (W-1)^2, H*W and 2 * planes * H*W must stay below 2^31")
-    return nbytes
+def _surface_workspace(S, H, W, what, share=1):
+    """`_launch`'s workspace of the two entry points of csrc/surface.hip: `1 / share` of what `anoddpm_surface_workspace_bytes` answers."""
+    return (lib().anoddpm_surface_workspace_bytes(S, H, W) // share, torch.int32,
+            f"{what}: {S} planes of {H} x {W} are too large: (H-1)^2 + (W-1)^2, H*W and 2 * planes * H*W must stay below 2^31")
 
 
 def distance_transform(x, level=0.0, squared=False, batched=None):
@@ -680,16 +673,12 @@ def distance_transform(x, level=0.0, squared=False, batched=None):
     S, C, H, W = _planes(x, False, "distance_transform")
     xt = _f32c(x, "distance_transform(x)")
     dev = xt.device
-    nbytes = _surface_workspace(C, H, W, "distance_transform") // 4
-    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
     sq = torch.empty(tuple(x.shape), dtype=torch.int32, device=dev)
     dist = None if squared else torch.empty(tuple(x.shape), dtype=torch.float64, device=dev)
     a = DistanceArgs()
     a.src, a.sq, a.dist = xt.data_ptr(), sq.data_ptr(), (None if squared else dist.data_ptr())
-    a.workspace, a.workspace_bytes, a.src_stride = ws.data_ptr(), nbytes, H * W
-    a.S, a.H, a.W, a.level = C, H, W, float(level)
-    with torch.cuda.device(dev):
-        check(lib().anoddpm_distance_transform(ctypes.byref(a), current_stream()), "distance_transform")
+    a.src_stride, a.S, a.H, a.W, a.level = H * W, C, H, W, float(level)
+    _launch("distance_transform", a, dev, _surface_workspace(C, H, W, "distance_transform", share=4))    # 4 * S * H * W bytes: a quarter
     return sq if squared else dist
 
 
@@ -713,20 +702,17 @@ def surface_distance(pred, ref, level=0.0, return_status=False):
     if rt.device != pt.device:
         raise ValueError("surface_distance: pred and ref are on different devices")
     dev = pt.device
-    nbytes = _surface_workspace(C, H, W, "surface_distance")
     lead = tuple(pred.shape[:-2])
-    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
     out = {"counts": torch.empty(lead + (2,), dtype=torch.int32, device=dev), "max2": torch.empty(lead + (2,), dtype=torch.int32, device=dev),
            "mean": torch.empty(lead + (2,), dtype=torch.float64, device=dev), "p95": torch.empty(lead + (3,), dtype=torch.float64, device=dev),
            "status": torch.empty(lead, dtype=torch.int32, device=dev)}
     a = SurfaceArgs()
-    a.pred, a.ref, a.workspace, a.workspace_bytes = pt.data_ptr(), rt.data_ptr(), ws.data_ptr(), nbytes
+    a.pred, a.ref = pt.data_ptr(), rt.data_ptr()
     for k in ("counts", "max2", "mean", "p95", "status"):
         setattr(a, k, out[k].data_ptr())
     a.pred_stride, a.ref_stride = H * W, (H * W if rt.numel() == C * H * W and C > 1 else 0)
     a.S, a.H, a.W, a.level = C, H, W, float(level)
-    with torch.cuda.device(dev):
-        check(lib().anoddpm_surface_distance(ctypes.byref(a), current_stream()), "surface_distance")
+    _launch("surface_distance", a, dev, _surface_workspace(C, H, W, "surface_distance"))
     out["hd"] = torch.sqrt(out["max2"].max(dim=-1).values.double())              # max2 is -1 where the status is set: NaN
     out["hd95"] = out["p95"][..., 2]
     out["assd"] = (out["mean"][..., 0] + out["mean"][..., 1]) / 2
@@ -739,6 +725,123 @@ def _valid_mean(values, status):
     n = ok.sum(dim=-1)
     total = torch.where(ok, values, torch.zeros_like(values)).sum(dim=-1)
     return torch.where(n > 0, total / n.clamp(min=1), torch.full_like(total, float("nan"))), n
+
+
+def score_maps(real, mean, sqerr, pred, mask, postprocess=None, roi=None, pro_limit=None, surface=False, threshold=0.5, pred_pp=False):
+    """Every score of R stacks of anomaly maps, one launch per step whatever R is.  real: [B, C, H, W]; mean (the averaged
+    reconstructions), sqerr and pred: [R, B, C, H, W], `pred > 0` being the thresholded map (the 0 / 1 `pred` and the -1 / 1
+    `thr_img` of `anomaly_maps` both do); mask: like real, or None.  Setting r pools its B images into one curve, as
+    detection.py:230-231 does.  Returns a dict of device tensors with a leading R axis; never synchronises, never copies to the
+    host, and the same bits in row r whatever the other rows hold.  A score that cannot be computed has no key:
+
+    `ssim` [R, B] (7 x 7 uniform window, data_range 2.0; `real[0]` is read in place by every setting when B == 1) -- for
+    non-empty `[B, C, H, W]` images of at least the window's size.
+    With a mask: `auc`, `ap`, `best_dice`, `best_threshold`, `auc_status` [R] (`curve_scores` of sqerr).
+    With `postprocess` (a `PostProcess`; `roi`: see `postprocess_maps`): `sqerr_pp` like sqerr -- one erosion and one median
+    launch -- with a mask `auc_pp`, `ap_pp`, `best_dice_pp`, `best_threshold_pp`, `auc_pp_status` [R] of it, and, when `pred_pp`
+    or `surface` asks for it, `pred_pp`: `sqerr_pp > threshold` without its components below `postprocess.min_size` pixels.
+    With `pro_limit` and a mask: `aupro` (and `aupro_pp`) [R] as `aupro(..., connectivity=2)`, `aupro_regions` (int64) and
+    `aupro_status` [R] of the raw maps -- one component run on the mask and one PRO launch.
+    With `surface` and a mask: `hd`, `hd95`, `assd` (and their `_pp` forms) [R]: `surface_distance` of every plane of pred (and
+    pred_pp) against its mask plane in one call (a mask of one plane is shared), each the mean over the setting's planes whose
+    status is 0, NaN when there is none; `surface_status` [R, B * C], the planes' status words for pred."""
+    R, have_mask = sqerr.shape[0], mask is not None
+    out, stacks = {}, [("", sqerr)]
+
+    def curves(sfx, sq):
+        o = curve_scores(mask, sq.reshape(R, -1), batched=True)
+        out.update({k + sfx: o[k] for k in ("auc", "ap", "best_dice", "best_threshold")})
+        out["auc" + sfx + "_status"] = o["status"]
+
+    if have_mask:
+        curves("", sqerr)
+    if real.dim() == 4 and min(real.shape[-2:]) >= 7 and real.numel() > 0:
+        B = real.shape[0]
+        out["ssim"] = ssim(real[0] if B == 1 else real.unsqueeze(0).expand_as(mean), mean).reshape(R, B)
+    if postprocess is not None:
+        out["sqerr_pp"] = postprocess_maps(sqerr, postprocess, real=real, roi=roi)
+        stacks.append(("_pp", out["sqerr_pp"]))
+        if have_mask:
+            curves("_pp", out["sqerr_pp"])
+    if have_mask and pro_limit is not None:
+        o = _pro_launch(mask, torch.cat([sq for _, sq in stacks]), pro_limit, 2, batched=True, curve=False)
+        out["aupro_regions"], out["aupro_status"] = o["counts"][:R, 0], o["status"][:R]
+        for (sfx, _), val in zip(stacks, _nan_where_status(o, "aupro").reshape(-1, R)):
+            out["aupro" + sfx] = val
+    preds = [pred]
+    if postprocess is not None and (pred_pp or (surface and have_mask)):
+        out["pred_pp"] = _small_components(out["sqerr_pp"], float(threshold), postprocess.min_size, postprocess.connectivity)[0]
+        preds.append(out["pred_pp"])
+    if have_mask and surface:
+        H, W = pred.shape[-2:]
+        planes = torch.cat(preds).reshape(len(preds) * R, -1, H, W)
+        ref = mask.reshape(-1, H, W)
+        o = surface_distance(planes, ref[0] if ref.shape[0] == 1 else ref.unsqueeze(0).expand(planes.shape))
+        out["surface_status"] = o["status"][:R]
+        for k in ("hd", "hd95", "assd"):
+            for (sfx, _), val in zip(stacks, _valid_mean(o[k], o["status"])[0].reshape(-1, R)):
+                out[k + sfx] = val
+    return out
+
+
+NAN = float("nan")
+# anomaly_metrics*: (key, key of score_maps, value when score_maps has none, options that bring the key)
+_METRIC_KEYS = (("AUC", "auc", NAN, ()), ("AP", "ap", NAN, ()), ("best_dice", "best_dice", NAN, ()), ("best_threshold", "best_threshold", NAN, ()),
+                ("AUC_status", "auc_status", 0, ()), ("SSIM", "ssim", NAN, ()),
+                ("AUC_pp", "auc_pp", NAN, ("pp",)), ("AP_pp", "ap_pp", NAN, ("pp",)), ("best_dice_pp", "best_dice_pp", NAN, ("pp",)),
+                ("best_threshold_pp", "best_threshold_pp", NAN, ("pp",)), ("AUC_pp_status", "auc_pp_status", 0, ("pp",)),
+                ("AUPRO", "aupro", NAN, ("pro",)), ("AUPRO_regions", "aupro_regions", 0, ("pro",)), ("AUPRO_status", "aupro_status", 0, ("pro",)),
+                ("AUPRO_pp", "aupro_pp", NAN, ("pro", "pp")),
+                ("HD", "hd", NAN, ("surface",)), ("HD95", "hd95", NAN, ("surface",)), ("ASSD", "assd", NAN, ("surface",)),
+                ("HD_pp", "hd_pp", NAN, ("surface", "pp")), ("HD95_pp", "hd95_pp", NAN, ("surface", "pp")), ("ASSD_pp", "assd_pp", NAN, ("surface", "pp")))
+
+
+def _to_host(tensors):
+    """The device tensors of a dict on the host from ONE copy, as fp64 (counts, status words and fp32 values are exact in it)."""
+    flat = torch.cat([t.reshape(-1).double() for t in tensors.values()]).cpu()
+    parts = flat.split([t.numel() for t in tensors.values()])
+    return {k: p.reshape(t.shape) for (k, t), p in zip(tensors.items(), parts)}
+
+
+def _metrics(real, recon, mask, threshold, postprocess, roi, pro_limit=None, surface=False):
+    """`anomaly_metrics`, `anomaly_metrics_pro` and `anomaly_metrics_surface`: `anomaly_maps`, `score_maps` of the one stack, one
+    copy of every number to the host, `_METRIC_KEYS`."""
+    maps, counts = anomaly_maps(real, recon, mask, threshold)
+    o = score_maps(real, maps["mean"][None], maps["sqerr"][None], maps["pred"][None], mask, postprocess=postprocess, roi=roi,
+                   pro_limit=pro_limit, surface=surface, threshold=threshold, pred_pp=True)
+    dev = {src: o[src][0] for _, src, _, _ in _METRIC_KEYS if src in o}
+    dev["counts"] = counts
+    if "ssim" in o:
+        dev["ssim"] = o["ssim"].mean()
+    if "surface_status" in o:
+        dev["surface_status"] = o["surface_status"][0]
+    if postprocess is not None:
+        maps["sqerr_pp"], maps["pred_pp"] = o["sqerr_pp"][0], o["pred_pp"][0]
+        dev["counts_pp"] = anomaly_maps(torch.zeros_like(maps["pred_pp"]), maps["pred_pp"], mask, threshold=0.5, want=())[1]    # (pred - 0)^2 > 0.5 is pred itself
+    h = _to_host(dev)
+    c = h["counts"]
+    r = {k: float(v) for k, v in _ratios(c).items() if k != "dice_per_image"}
+    mse = float(c[:, 9].sum()) / real.numel()
+    r["mse"] = mse
+    r["PSNR"] = float(20.0 * torch.log10(torch.tensor(float(c[:, 10].max())) / torch.sqrt(torch.tensor(mse)))) if mse > 0 else float("inf")
+    on = {"pp": postprocess is not None, "pro": pro_limit is not None, "surface": surface}
+    for key, src, absent, options in _METRIC_KEYS:
+        if all(on[k] for k in options):
+            r[key] = type(absent)(h[src]) if src in h else absent
+    for sfx in ("", "_pp") if on["pp"] else ("",):
+        if r["best_dice" + sfx] != r["best_dice" + sfx]:
+            r["best_threshold" + sfx] = NAN                          # no positive: no threshold is better than another
+    if surface:
+        status = [int(st) for st in h["surface_status"].tolist()] if "surface_status" in h else []
+        r["HD95_valid"], r["surface_status"] = sum(st == 0 for st in status), 0
+        for st in status:
+            r["surface_status"] |= st
+    if on["pp"]:
+        ratios = _ratios(h["counts_pp"])
+        for key in ("dice", "precision", "recall"):
+            r[key + "_pp"] = float(ratios[key])
+    r["maps"] = maps
+    return r
 
 
 def anomaly_metrics(real, recon, mask, threshold=0.5, postprocess=None, roi=None):
@@ -756,21 +859,7 @@ def anomaly_metrics(real, recon, mask, threshold=0.5, postprocess=None, roi=None
     `maps["sqerr_pp"]` -- and `dice_pp`, `precision_pp`, `recall_pp`: the filtered map cut at `threshold`, without its
     components below `postprocess.min_size` pixels (`maps["pred_pp"]`), counted by the same pass as `dice` / `precision` /
     `recall`.  The inputs must be `[..., H, W]` images then."""
-    maps, counts = anomaly_maps(real, recon, mask, threshold)
-    roc = curve_scores(mask, maps["sqerr"], batched=False) if mask is not None else None
-    ss = ssim(real, maps["mean"]) if real.dim() == 4 and min(real.shape[-2:]) >= 7 and real.numel() > 0 else None
-    c = counts.cpu()
-    r = {k: float(v) for k, v in _ratios(c).items() if k != "dice_per_image"}
-    n_total = real.numel()
-    mse = float(c[:, 9].sum()) / n_total
-    r["mse"] = mse
-    r["PSNR"] = float(20.0 * torch.log10(torch.tensor(float(c[:, 10].max())) / torch.sqrt(torch.tensor(mse)))) if mse > 0 else float("inf")
-    _curve_floats(r, roc, "")
-    r["SSIM"] = float(ss.mean().cpu()) if ss is not None else float("nan")
-    r["maps"] = maps
-    if postprocess is not None:
-        _add_postprocessed(r, real, mask, threshold, postprocess, roi)
-    return r
+    return _metrics(real, recon, mask, threshold, postprocess, roi)
 
 
 def anomaly_metrics_pro(real, recon, mask, threshold=0.5, postprocess=None, roi=None, pro_limit=0.3):
@@ -780,10 +869,7 @@ def anomaly_metrics_pro(real, recon, mask, threshold=0.5, postprocess=None, roi=
     neighbours) and `AUPRO_status`, and with `postprocess` also `AUPRO_pp` on the filtered map, all from one component run on
     the mask and one PRO launch; NaN as `AUC`.  The inputs must be `[..., H, W]` images.  `pro_limit=None`: exactly
     `anomaly_metrics(...)`, no key and no launch more."""
-    r = anomaly_metrics(real, recon, mask, threshold, postprocess, roi)
-    if pro_limit is not None:
-        _add_pro(r, mask, pro_limit)
-    return r
+    return _metrics(real, recon, mask, threshold, postprocess, roi, pro_limit=pro_limit)
 
 
 def anomaly_metrics_surface(real, recon, mask, threshold=0.5, postprocess=None, roi=None):
@@ -793,70 +879,7 @@ def anomaly_metrics_surface(real, recon, mask, threshold=0.5, postprocess=None, 
     exist; NaN when there is none), `HD95_valid`, the number of those planes, and `surface_status`, the OR of the planes' status
     words; with `postprocess` also `HD_pp`, `HD95_pp`, `ASSD_pp` from `maps["pred_pp"]`, from the same launch.  Without a mask:
     NaN, 0, 0.  The inputs must be `[..., H, W]` images."""
-    r = anomaly_metrics(real, recon, mask, threshold, postprocess, roi)
-    maps = r["maps"]
-    suffixes = [""] + (["_pp"] if "pred_pp" in maps else [])
-    for sfx in suffixes:
-        r["HD" + sfx] = r["HD95" + sfx] = r["ASSD" + sfx] = float("nan")
-    r["HD95_valid"], r["surface_status"] = 0, 0
-    if mask is None:
-        return r
-    pred = maps["pred"]
-    if mask.numel() != pred.numel():
-        raise ValueError(f"anomaly_metrics_surface: mask {tuple(mask.shape)} does not match the images {tuple(pred.shape)}")
-    preds = torch.stack([pred] + ([maps["pred_pp"].reshape(pred.shape)] if len(suffixes) == 2 else []))
-    o = surface_distance(preds.reshape(len(suffixes), -1, *pred.shape[-2:]), mask.reshape(1, -1, *pred.shape[-2:]).expand(len(suffixes), -1, -1, -1))
-    vals = torch.stack([_valid_mean(o[k], o["status"])[0] for k in ("hd", "hd95", "assd")]).cpu()      # [3, len(suffixes)]
-    status = o["status"].cpu()
-    r["HD95_valid"] = int((status[0] == 0).sum())
-    for st in status[0].tolist():
-        r["surface_status"] |= st
-    for j, sfx in enumerate(suffixes):
-        r["HD" + sfx], r["HD95" + sfx], r["ASSD" + sfx] = (float(vals[i, j]) for i in range(3))
-    return r
-
-
-def _add_pro(r, mask, limit):
-    """The `AUPRO` keys of `anomaly_metrics_pro`: one launch over the raw and, when it exists, the filtered map (one shared mask)."""
-    maps = r["maps"]
-    names = ["AUPRO"] + (["AUPRO_pp"] if "sqerr_pp" in maps else [])
-    r["AUPRO_regions"], r["AUPRO_status"] = 0, 0
-    for k in names:
-        r[k] = float("nan")
-    if mask is None:
-        return
-    sq = maps["sqerr"]
-    scores = torch.stack([sq, maps["sqerr_pp"].reshape(sq.shape)]) if len(names) == 2 else sq.unsqueeze(0)
-    o = _pro_launch(mask, scores, limit, 2, batched=True, curve=False)
-    status, counts, val = o["status"].cpu(), o["counts"].cpu(), o["aupro"].cpu()
-    r["AUPRO_regions"], r["AUPRO_status"] = int(counts[0, 0]), int(status[0])
-    for j, k in enumerate(names):
-        if int(status[j]) == 0:
-            r[k] = float(val[j])
-
-
-def _curve_floats(r, roc, suffix):
-    """`AUC`, `AP`, `best_dice`, `best_threshold` (+ suffix) and `AUC<suffix>_status` of `r` as Python numbers from `roc`, the
-    `curve_scores` of one segment (None without a mask: NaN, status 0)."""
-    st = r["AUC" + suffix + "_status"] = int(roc["status"].cpu()[0]) if roc is not None else 0
-    for key, src in (("AUC", "auc"), ("AP", "ap"), ("best_dice", "best_dice"), ("best_threshold", "best_threshold")):
-        r[key + suffix] = float(roc[src].cpu()[0]) if roc is not None and st == 0 else float("nan")
-    if r["best_dice" + suffix] != r["best_dice" + suffix]:
-        r["best_threshold" + suffix] = float("nan")                  # no positive: no threshold is better than another
-
-
-def _add_postprocessed(r, real, mask, threshold, pp, roi):
-    """The `_pp` keys of `anomaly_metrics`."""
-    maps = r["maps"]
-    sq = postprocess_maps(maps["sqerr"], pp, real=real, roi=roi)
-    pred, _ = _small_components(sq, float(threshold), pp.min_size, pp.connectivity)
-    roc = curve_scores(mask, sq, batched=False) if mask is not None else None
-    _, counts = anomaly_maps(torch.zeros_like(pred), pred, mask, threshold=0.5, want=())    # (pred - 0)^2 > 0.5 is pred itself
-    ratios = _ratios(counts.cpu())
-    for key in ("dice", "precision", "recall"):
-        r[key + "_pp"] = float(ratios[key])
-    _curve_floats(r, roc, "_pp")
-    maps["sqerr_pp"], maps["pred_pp"] = sq, pred
+    return _metrics(real, recon, mask, threshold, postprocess, roi, surface=True)
 
 
 # ---------------------------------------------------------------------------------- evaluation.py surface

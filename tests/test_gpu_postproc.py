@@ -11,6 +11,7 @@ import torch
 
 import postproc_cases as pc
 from conftest import GOLDEN
+from score_cases import PARENT_RECORD_KEYS, PP_RECORD_KEYS, bits as _bits, host as _host, tiny as _tiny
 
 pytestmark = pytest.mark.gpu
 
@@ -18,9 +19,6 @@ DEV = "cuda:0"
 MEDIAN_CASES = [(name, k) for name in sorted(pc.MEDIAN) for k in pc.WINDOWS]
 ERODE_CASES = [(name, n) for name in sorted(pc.ERODE) for n in pc.ERODE_N]
 COMPONENT_CASES = [(name, c) for name in sorted(pc.COMPONENTS) for c in (1, 2)]
-PARENT_RECORD_KEYS = {"t_distance", "output", "mean", "mse", "threshold", "counts", "auc", "auc_status", "ap", "best_dice",
-                      "best_threshold", "ssim"}
-PP_RECORD_KEYS = {"sqerr_pp", "auc_pp", "ap_pp", "best_dice_pp", "best_threshold_pp"}
 
 
 @pytest.fixture(scope="module")
@@ -30,15 +28,6 @@ def kat():
 
 def _dev(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
-def _bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _host(t):
-    return t.cpu().numpy()
 
 
 def _is_f32_on_device(t, like):
@@ -363,17 +352,6 @@ def test_postprocess_maps_launches_once_per_step(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------- detection records
-def _tiny(size):
-    import GaussianDiffusion as GD
-    from UNet import UNetModel
-    from oracle import unet_oracle as uo
-    m = UNetModel(img_size=size, base_channels=32, n_heads=2, attention_resolutions="16,8")
-    m.load_state_dict(uo.fill_deterministic({k: tuple(v.shape) for k, v in m.state_dict().items()}))
-    m.to(DEV).eval()
-    d = GD.GaussianDiffusionModel([size, size], GD.get_beta_schedule(200, "linear"), noise="gauss")
-    return GD, m, d
-
-
 def test_detection_records_carry_the_postprocessed_scores(tmp_path, monkeypatch):
     from anoddpm_amd import metrics
     GD, m, d = _tiny(32)

@@ -12,6 +12,7 @@ import torch
 import pr_cases as pc
 import roc_cases as rc
 from conftest import GOLDEN
+from score_cases import tiny as _tiny
 
 pytestmark = pytest.mark.gpu
 
@@ -276,17 +277,6 @@ def test_anomaly_metrics_ap_and_best_dice_come_with_the_auc(kat):
     assert all(np.isnan(no_mask[k]) for k in ("AUC", "AP", "best_dice", "best_threshold")) and no_mask["AUC_status"] == 0
     no_pos = metrics.anomaly_metrics(real, recon, torch.zeros_like(mask))
     assert all(np.isnan(no_pos[k]) for k in ("AUC", "AP", "best_dice", "best_threshold")) and no_pos["AUC_status"] == 0
-
-
-def _tiny():
-    import GaussianDiffusion as GD
-    from UNet import UNetModel
-    from oracle import unet_oracle as uo
-    m = UNetModel(img_size=32, base_channels=32, n_heads=2, attention_resolutions="16,8")
-    m.load_state_dict(uo.fill_deterministic({k: tuple(v.shape) for k, v in m.state_dict().items()}))
-    m.to(DEV).eval()
-    d = GD.GaussianDiffusionModel([32, 32], GD.get_beta_schedule(200, "linear"), noise="gauss")
-    return GD, m, d
 
 
 def test_detection_records_carry_ap_and_best_dice(tmp_path, monkeypatch):

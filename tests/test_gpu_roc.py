@@ -9,6 +9,7 @@ import torch
 
 import roc_cases as rc
 from conftest import GOLDEN
+from score_cases import tiny as _tiny
 
 pytestmark = pytest.mark.gpu
 
@@ -214,17 +215,6 @@ def test_anomaly_metrics_auc_is_the_flattened_batch(kat):
     assert r["mse"] == float(c[:, 9].sum()) / real.numel() and r["dice"] == float(metrics._ratios(c)["dice"])
     no_mask = metrics.anomaly_metrics(real, recon, None)
     assert np.isnan(no_mask["AUC"]) and no_mask["AUC_status"] == 0
-
-
-def _tiny():
-    import GaussianDiffusion as GD
-    from UNet import UNetModel
-    from oracle import unet_oracle as uo
-    m = UNetModel(img_size=32, base_channels=32, n_heads=2, attention_resolutions="16,8")
-    m.load_state_dict(uo.fill_deterministic({k: tuple(v.shape) for k, v in m.state_dict().items()}))
-    m.to(DEV).eval()
-    d = GD.GaussianDiffusionModel([32, 32], GD.get_beta_schedule(200, "linear"), noise="gauss")
-    return GD, m, d
 
 
 def test_detection_records_carry_the_auc(tmp_path, monkeypatch):

@@ -11,6 +11,7 @@ import torch
 
 import ssim_cases as sc
 from conftest import GOLDEN
+from score_cases import bits as _bits, tiny as _tiny
 
 pytestmark = pytest.mark.gpu
 
@@ -37,11 +38,6 @@ def _check(got, want, what):
         assert np.isnan(got), what
     else:
         assert abs(got - want) <= sc.MSSIM_TOL, what
-
-
-def _bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 @pytest.mark.parametrize("name,window", CASES)
@@ -198,17 +194,6 @@ def test_too_small_images_raise():
         evaluation.SSIM(torch.zeros(5, 5, device=DEV), torch.zeros(5, 5, device=DEV))
 
 
-def _tiny(size):
-    import GaussianDiffusion as GD
-    from UNet import UNetModel
-    from oracle import unet_oracle as uo
-    m = UNetModel(img_size=size, base_channels=32, n_heads=2, attention_resolutions="16,8")
-    m.load_state_dict(uo.fill_deterministic({k: tuple(v.shape) for k, v in m.state_dict().items()}))
-    m.to(DEV).eval()
-    d = GD.GaussianDiffusionModel([size, size], GD.get_beta_schedule(200, "linear"), noise="gauss")
-    return GD, m, d
-
-
 def test_detection_records_carry_the_ssim(tmp_path, monkeypatch):
     from anoddpm_amd import metrics
     GD, m, d = _tiny(32)
@@ -229,16 +214,13 @@ def test_detection_records_carry_the_ssim(tmp_path, monkeypatch):
     # without a mask the SSIM is still there (it needs none)
     d.detection_B(m, x_0, args, ("vol", "slice"), None, denoise_fn="gauss", total_avg=2)
     assert all(r["ssim"] is not None and r["auc"] is None for r in d.last_detection)
-    # an image smaller than the 7 x 7 window: None
-    recs = [{"mean": torch.zeros(1, 1, 6, 6, device=DEV)}, {"mean": torch.zeros(1, 1, 6, 6, device=DEV)}]
-    for r in recs:
-        r["ssim"] = None
-    d._attach_ssim(recs, torch.zeros(1, 1, 6, 6, device=DEV))
-    assert all(r["ssim"] is None for r in recs)
-    # a batch of images: [B] per record, the real images repeated per setting
+    # an image smaller than the 7 x 7 window: no SSIM
+    small = torch.zeros(2, 1, 1, 6, 6, device=DEV)
+    assert "ssim" not in metrics.score_maps(torch.zeros(1, 1, 6, 6, device=DEV), small, small, small, None)
+    # a batch of images: [B] per setting, the real images repeated per setting
     xb = torch.rand(2, 1, 32, 32, device=DEV) * 2 - 1
-    recs = [{"mean": (xb + 0.1 * (j + 1) * torch.rand_like(xb)).clamp(-1, 1), "ssim": None} for j in range(3)]
-    d._attach_ssim(recs, xb)
-    for r in recs:
-        assert r["ssim"].shape == (2,) and _bits(r["ssim"].cpu().numpy(), metrics.ssim(xb, r["mean"]).cpu().numpy())
+    means = torch.stack([(xb + 0.1 * (j + 1) * torch.rand_like(xb)).clamp(-1, 1) for j in range(3)])
+    val = metrics.score_maps(xb, means, torch.zeros_like(means), torch.zeros_like(means), None)["ssim"]
+    for j in range(3):
+        assert val[j].shape == (2,) and _bits(val[j].cpu().numpy(), metrics.ssim(xb, means[j]).cpu().numpy())
     assert not os.listdir(tmp_path)

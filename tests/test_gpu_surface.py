@@ -12,17 +12,12 @@ import torch
 
 import surface_cases as sc
 from conftest import GOLDEN
+from score_cases import PARENT_METRIC_KEYS, PARENT_RECORD_KEYS, PP_METRIC_KEYS, PP_RECORD_KEYS, bits_any_nan as _bits, host as _host, tiny as _tiny
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-PARENT_METRIC_KEYS = {"dice", "precision", "recall", "FPR", "IoU", "mse", "PSNR", "AUC", "AUC_status", "AP", "best_dice", "best_threshold",
-                      "SSIM", "maps"}
-PP_METRIC_KEYS = {"dice_pp", "precision_pp", "recall_pp", "AUC_pp", "AUC_pp_status", "AP_pp", "best_dice_pp", "best_threshold_pp"}
 SURFACE_METRIC_KEYS = {"HD", "HD95", "ASSD", "HD95_valid", "surface_status"}
-PARENT_RECORD_KEYS = {"t_distance", "output", "mean", "mse", "threshold", "counts", "auc", "auc_status", "ap", "best_dice",
-                      "best_threshold", "ssim"}
-PP_RECORD_KEYS = {"sqerr_pp", "auc_pp", "ap_pp", "best_dice_pp", "best_threshold_pp"}
 
 
 @pytest.fixture(scope="module")
@@ -42,18 +37,6 @@ def surface_cases():
 
 def _dev(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
-def _host(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(a, b):
-    """The same dtype, shape and bits; every NaN counts as the same NaN."""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.dtype == np.float64 and b.dtype == np.float64:
-        a, b = np.where(np.isnan(a), np.nan, a), np.where(np.isnan(b), np.nan, b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 # ---------------------------------------------------------------------------------- distance transform
@@ -254,17 +237,6 @@ def test_anomaly_metrics_surface_adds_keys_and_nothing_else():
 
 
 # ---------------------------------------------------------------------------------- detection records
-def _tiny(size):
-    import GaussianDiffusion as GD
-    from UNet import UNetModel
-    from oracle import unet_oracle as uo
-    m = UNetModel(img_size=size, base_channels=32, n_heads=2, attention_resolutions="16,8")
-    m.load_state_dict(uo.fill_deterministic({k: tuple(v.shape) for k, v in m.state_dict().items()}))
-    m.to(DEV).eval()
-    d = GD.GaussianDiffusionModel([size, size], GD.get_beta_schedule(200, "linear"), noise="gauss")
-    return GD, m, d
-
-
 def test_detection_records_carry_boundary_distances_when_asked(tmp_path, monkeypatch):
     from anoddpm_amd import _lib, metrics
     GD, m, d = _tiny(32)

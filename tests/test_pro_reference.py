@@ -206,7 +206,7 @@ def test_python_argument_validation_without_gpu():
         metrics.aupro(np.zeros((4, 4)), s)
 
 
-def test_new_names_are_exported_and_defaults_add_nothing():
+def test_new_names_are_exported_and_defaults_add_nothing(monkeypatch):
     import evaluation
     from anoddpm_amd import metrics
     from anoddpm_amd.diffusion import GaussianDiffusionModel
@@ -220,11 +220,16 @@ def test_new_names_are_exported_and_defaults_add_nothing():
     assert inspect.signature(metrics.aupro).parameters["limit"].default == 0.3
     assert inspect.signature(metrics.aupro).parameters["connectivity"].default == 2
     assert inspect.signature(metrics.AUPRO).parameters["limit"].default == 0.3
-    # the record template: unset, the hook returns before it touches a record
+    # the record template: unset, `_score_settings` asks for no PRO launch and a record has no new key
     assert GaussianDiffusionModel.pro_limit is None
-    model = object.__new__(GaussianDiffusionModel)
-    records = [{"auc": None, "ssim": None}]
-    model._attach_pro(records, [None], None)
-    assert records == [{"auc": None, "ssim": None}]
-    template = inspect.getsource(GaussianDiffusionModel._score_settings)
-    assert "aupro" not in template.split("self._attach_auc")[0]         # the dict every record starts from has no new key
+    import torch
+    from score_cases import PARENT_RECORD_KEYS
+    model, asked = object.__new__(GaussianDiffusionModel), []
+    image = torch.zeros(1, 1, 8, 8)
+    monkeypatch.setattr(metrics, "anomaly_maps", lambda *a, **kw: ({k: image for k in ("mean", "sqerr", "mse_img", "thr_img", "pred")}, torch.zeros(1, 12)))
+    monkeypatch.setattr(metrics, "score_maps", lambda *a, **kw: (asked.append(kw["pro_limit"]), {})[1])
+    model._score_settings([{"t_distance": 50}], torch.zeros(2, 1, 8, 8), 2, image, None)
+    assert asked == [None] and set(model.last_detection[0]) == PARENT_RECORD_KEYS
+    model.pro_limit = 0.3
+    model._score_settings([{"t_distance": 50}], torch.zeros(2, 1, 8, 8), 2, image, None)
+    assert asked == [None, 0.3] and model.last_detection[0]["aupro"] is None

@@ -13,6 +13,7 @@ import pytest
 
 import surface_cases as sc
 from conftest import GOLDEN
+from score_cases import bits as _bits
 
 
 @pytest.fixture(scope="module")
@@ -24,11 +25,6 @@ def kat():
 def surface_results():
     """name -> the `surface_ref` of every pair of the case; computed once, read by every test."""
     return {name: [sc.surface_ref(p, r) for p, r in sc.pairs_of(pred, ref)] for name, (pred, ref) in sc.surface_cases().items()}
-
-
-def _bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 # ---------------------------------------------------------------------------------- distance transform
