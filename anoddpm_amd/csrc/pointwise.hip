@@ -14,6 +14,8 @@
 //     its B operand is one ds_read_b128 per four MFMAs;
 //   * v_mfma_f32_32x32x2_f32 with the k index permuted identically on both operands (channel 4q+e of half h is k-step (q, e)).
 // Work split: 256 workgroups (one per CU, 8 waves) x output-channel blocks; wave w of workgroup g takes tiles g*8+w, +stride, ...
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -31,6 +33,7 @@ __global__ __launch_bounds__(PW_NT) void pointwise_stream_kernel(const anoddpm_i
     constexpr int NBP = NB + 2;                                     // row pitch in float4
     constexpr int NTN = NB / 32;
     __shared__ __attribute__((aligned(16))) f32x4 wl[(KMAX / 4) * NBP];
+    __shared__ __attribute__((aligned(16))) f32x4 bl[NB / 4];       // bias of this channel block (zeros without one)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int p = lane & 31, h = lane >> 5;
     const int K = a.c0 + a.c1, N = a.N;
@@ -40,10 +43,33 @@ __global__ __launch_bounds__(PW_NT) void pointwise_stream_kernel(const anoddpm_i
     {   // weights of this channel block: [K/4][N] float4 in global -> [K/4][NBP] in LDS
         const f32x4 *__restrict__ wg = reinterpret_cast<const f32x4 *>(a.bmat);
         const int total = (K >> 2) * NB;
-        for (int idx = tid; idx < total; idx += PW_NT) {
-            const int q = idx / NB, n = idx - q * NB;
-            wl[q * NBP + n] = wg[(int64_t)q * N + n0 + n];
-        }
+        // The bias rides with the first weight requests and waits in LDS: the epilogues then read it with ds_read (lgkmcnt)
+        // instead of a global load per channel quad and tile, each followed by a vmcnt(0) that also drained the A ring.
+        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+        if (a.bias && tid < NB / 4) bv = *reinterpret_cast<const f32x4 *>(a.bias + n0 + 4 * tid);
+        // A thread's requests first, then its LDS writes: one round trip per batch instead of one per float4 (written as a
+        // plain loop, hipcc emits load / vmcnt(0) / ds_write per element).  total is a multiple of 4 * PW_NT for every shape
+        // the launcher admits (K % 128 == 0, NB % 64 == 0); the last loop is the general tail.
+        auto batch = [&](int idx0, auto u_) {
+            constexpr int U = decltype(u_)::value;
+            f32x4 v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int idx = idx0 + u * PW_NT, q = idx / NB, n = idx - q * NB;
+                v[u] = wg[(int64_t)q * N + n0 + n];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int idx = idx0 + u * PW_NT, q = idx / NB, n = idx - q * NB;
+                wl[q * NBP + n] = v[u];
+            }
+        };
+        int idx = tid;
+        for (; idx + 15 * PW_NT < total; idx += 16 * PW_NT) batch(idx, std::integral_constant<int, 16>{});
+        for (; idx + 7 * PW_NT < total; idx += 8 * PW_NT) batch(idx, std::integral_constant<int, 8>{});
+        for (; idx + 3 * PW_NT < total; idx += 4 * PW_NT) batch(idx, std::integral_constant<int, 4>{});
+        for (; idx < total; idx += PW_NT) batch(idx, std::integral_constant<int, 1>{});
+        if (tid < NB / 4) bl[tid] = bv;
     }
     __syncthreads();
 
@@ -86,6 +112,7 @@ __global__ __launch_bounds__(PW_NT) void pointwise_stream_kernel(const anoddpm_i
     f32x4 bq[2][NTN];
 #pragma unroll
     for (int nt = 0; nt < NTN; ++nt) bq[0][nt] = wrow[nt * 32];
+    const bool has_res = a.res != nullptr, has_temb = a.temb != nullptr;     // block-uniform: one epilogue body per combination
     for (int t = 0; t < my_tiles; ++t) {
         f32x16 acc[NTN];
 #pragma unroll
@@ -120,26 +147,39 @@ __global__ __launch_bounds__(PW_NT) void pointwise_stream_kernel(const anoddpm_i
         const int tile = gw + t * stride;
         const int b = tile / tiles_per_image, pl = (tile - b * tiles_per_image) * 32 + p;
         float *__restrict__ O = a.out + (int64_t)b * a.o_bs + (int64_t)pl * a.out_ld + n0 + 4 * h;
-        const float *R = a.res ? a.res + (int64_t)b * a.r_bs + (int64_t)pl * a.res_ld + n0 + 4 * h : nullptr;
-        const float *TE = a.temb ? a.temb + (int64_t)b * a.temb_ld + n0 + 4 * h : nullptr;
-        const float *BI = a.bias ? a.bias + n0 + 4 * h : nullptr;
+        // R / TE are formed without a null test here: has_res / has_temb choose a body that never reads an absent one, and a
+        // sub-tile's residual and embedding requests sit in front of ONE wait.
+        const float *R = a.res + (int64_t)b * a.r_bs + (int64_t)pl * a.res_ld + n0 + 4 * h;
+        const float *TE = a.temb + (int64_t)b * a.temb_ld + n0 + 4 * h;
+        auto epilogue = [&](auto hr_, auto ht_) {
+            constexpr bool HR = decltype(hr_)::value, HT = decltype(ht_)::value;
 #pragma unroll
-        for (int nt = 0; nt < NTN; ++nt) {
-            f32x4 rv[4], add[4];
+            for (int nt = 0; nt < NTN; ++nt) {
+                f32x4 rv[4], te[4];
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {                           // all residual loads of the sub-tile before its stores
-                const int c = nt * 32 + g * 8;
-                rv[g] = R ? *reinterpret_cast<const f32x4 *>(R + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-                add[g] = BI ? *reinterpret_cast<const f32x4 *>(BI + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-                if (TE) add[g] += *reinterpret_cast<const f32x4 *>(TE + c);
+                for (int g = 0; g < 4; ++g) {                       // all requests of the sub-tile before its stores
+                    const int c = nt * 32 + g * 8;
+                    rv[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if constexpr (HR) rv[g] = *reinterpret_cast<const f32x4 *>(R + c);
+                    if constexpr (HT) te[g] = *reinterpret_cast<const f32x4 *>(TE + c);
+                }
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    f32x4 add = bl[nt * 8 + g * 2 + h];             // channels n0 + nt * 32 + g * 8 + 4 h ..
+                    if constexpr (HT) add += te[g];
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = a.alpha * acc[nt][g * 4 + e] + add[e] + rv[g][e];
+                    if (!(DBG & 1) || v[0] == 12345.678f) *reinterpret_cast<f32x4 *>(O + nt * 32 + g * 8) = v;
+                }
             }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = a.alpha * acc[nt][g * 4 + e] + add[g][e] + rv[g][e];
-                if (!(DBG & 1) || v[0] == 12345.678f) *reinterpret_cast<f32x4 *>(O + nt * 32 + g * 8) = v;
-            }
+        };
+        if (has_res) {
+            if (has_temb) epilogue(std::true_type{}, std::true_type{});
+            else epilogue(std::true_type{}, std::false_type{});
+        } else {
+            if (has_temb) epilogue(std::false_type{}, std::true_type{});
+            else epilogue(std::false_type{}, std::false_type{});
         }
     }
 }

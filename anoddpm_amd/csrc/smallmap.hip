@@ -35,6 +35,18 @@ constexpr int SM_NT = 512;                 // 8 waves: they split K'
 __host__ __device__ constexpr int sm_kch(int ks) { return ks == 3 ? 256 : 512; }     // channels per K chunk: 32 / 64 per wave
 __host__ __device__ constexpr int sm_hpix(int ks, int tm, int w) { return ks == 1 ? tm : (tm / w + 2) * (w + 2); }
 
+// A kernel argument as a scalar VALUE.  `lane_cond ? a.x : a.y` on two fields of the argument struct is otherwise compiled as a select
+// of the fields' ADDRESSES and a global_load from the kernarg segment, followed by s_waitcnt vmcnt(0): vmcnt retires in order, so that
+// wait drains every operand request in flight (profiles/r7_small_kernel_waits.txt).
+__device__ __forceinline__ int sm_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+template <typename T>
+__device__ __forceinline__ const T *sm_uniform(const T *p)
+{
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return reinterpret_cast<const T *>(((uint64_t)hi << 32) | lo);
+}
+
 template <int KS, int RT, int CT, int LOG2W>
 __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_args a)
 {
@@ -111,12 +123,13 @@ __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_arg
     }
     f32x4 araw[NI];
     unsigned avalid = 0;
+    const int ld0 = sm_uniform(a.a0_ld), ld1 = sm_uniform(a.a1_ld);     // the values, not the fields: `first` depends on the lane
     auto load_A = [&](int chunk) {
         const int k = chunk * KCH + 4 * kq;
         const bool kv = k < K;
         const bool first = k < a.c0;
         const float *src = first ? A0 + (kv ? k : 0) : A1 + (kv ? k - a.c0 : 0);
-        const int ld = first ? a.a0_ld : a.a1_ld;
+        const int ld = first ? ld0 : ld1;
         avalid = 0;
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
@@ -150,11 +163,24 @@ __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_arg
         double *csum = reinterpret_cast<double *>(Abuf);
         double *gst = csum + 2 * Kpad;
         const int groups = a.fold_groups, cpg = K / groups;
+        const int fc0 = sm_uniform(a.c0), fc1 = sm_uniform(a.c1);
+        const int fmt0 = sm_uniform(a.fold_fmt0), fmt1 = sm_uniform(a.fold_fmt1);
+        const int rows0 = sm_uniform(a.fold_rows0), rows1 = sm_uniform(a.fold_rows1);
+        const float *st0 = sm_uniform(a.fold_stats0), *st1 = sm_uniform(a.fold_stats1);
+        // gamma / beta of this thread's channels (K <= 1024: at most two) ride with the statistics requests; they are used
+        // two barriers later, by the same thread for the same channels
+        float fgam[2], fbet[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int c = tid + i * SM_NT;
+            fgam[i] = a.fold_gamma[c < K ? c : 0];
+            fbet[i] = a.fold_beta[c < K ? c : 0];
+        }
         for (int c = tid; c < K; c += SM_NT) {
-            const bool first = c < a.c0;
-            const int cl = first ? c : c - a.c0, cw = first ? a.c0 : a.c1;
-            const int fmt = first ? a.fold_fmt0 : a.fold_fmt1, rows = first ? a.fold_rows0 : a.fold_rows1;
-            const float *st = first ? a.fold_stats0 : a.fold_stats1;
+            const bool first = c < fc0;
+            const int cl = first ? c : c - fc0, cw = first ? fc0 : fc1;
+            const int fmt = first ? fmt0 : fmt1, rows = first ? rows0 : rows1;
+            const float *st = first ? st0 : st1;
             double s = 0.0, qq = 0.0;
             if (fmt) {
                 const double *sd = reinterpret_cast<const double *>(st) + ((int64_t)b * cw + cl) * 2;
@@ -187,15 +213,19 @@ __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_arg
             gst[2 * tid + 1] = 1.0 / sqrt(var + (double)a.fold_eps);
         }
         __syncthreads();
-        for (int c = tid; c < Kpad; c += SM_NT) {
-            float scv = 0.f, shv = 0.f;
-            if (c < K) {
-                const int g = c / cpg;
-                const double sc = gst[2 * g + 1] * (double)a.fold_gamma[c];
-                scv = (float)sc;
-                shv = (float)((double)a.fold_beta[c] - gst[2 * g] * sc);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int c = tid + i * SM_NT;
+            if (c < Kpad) {
+                float scv = 0.f, shv = 0.f;
+                if (c < K) {
+                    const int g = c / cpg;
+                    const double sc = gst[2 * g + 1] * (double)fgam[i];
+                    scv = (float)sc;
+                    shv = (float)((double)fbet[i] - gst[2 * g] * sc);
+                }
+                aff_sc[c] = scv; aff_sh[c] = shv;
             }
-            aff_sc[c] = scv; aff_sh[c] = shv;
         }
         __syncthreads();
     } else if (a.gn_scale) {

@@ -356,10 +356,13 @@ __global__ __launch_bounds__(256) void linear_small_kernel(anoddpm_linear_args a
     const int K4 = a.K >> 2;
     for (int k = lane; k < K4; k += 64) {
         const float4 wv = w[k];
+        float4 xin[NB];                                              // every row's request before the first use (clamped row: unconditional)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) xin[b] = reinterpret_cast<const float4 *>(a.in + (int64_t)(b < a.B ? b : a.B - 1) * a.K)[k];
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             if (b < a.B) {
-                float4 xv = reinterpret_cast<const float4 *>(a.in + (int64_t)b * a.K)[k];
+                float4 xv = xin[b];
                 if (a.act_in) { xv.x = silu_f(xv.x); xv.y = silu_f(xv.y); xv.z = silu_f(xv.z); xv.w = silu_f(xv.w); }
                 acc[b] += wv.x * xv.x + wv.y * xv.y + wv.z * xv.z + wv.w * xv.w;
             }

@@ -34,6 +34,17 @@ constexpr int WS_PPX = 100;                // 10 x 10 input pixels: the 8 x 8 ou
 constexpr int WS_VBUF = 16 * 16 * WS_PITCH;    // floats per V buffer [pos][tile][PITCH]
 constexpr int WS_PBUF = 104 * WS_PITCH;        // floats per patch buffer (100 pixels + slack for the unconditional last slot)
 
+// A kernel argument as a scalar VALUE (as sm_uniform of smallmap.hip): a lane-dependent choice between two fields of the argument
+// struct is otherwise a select of their addresses, a global_load from the kernarg segment and s_waitcnt vmcnt(0) in every chunk.
+__device__ __forceinline__ int ws_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+template <typename T>
+__device__ __forceinline__ const T *ws_uniform(const T *p)
+{
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return reinterpret_cast<const T *>(((uint64_t)hi << 32) | lo);
+}
+
 template <int CT>                           // 16-channel column tiles per workgroup: 2 (32 channels) or 4 (64)
 __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args a)
 {
@@ -95,12 +106,13 @@ __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args
     }
     f32x4 praw[2];
     unsigned pvalid = 0;
+    const int ld0 = ws_uniform(a.a0_ld), ld1 = ws_uniform(a.a1_ld);     // the values, not the fields: `first` depends on the lane
     auto load_patch = [&](int chunk) {
         if (chunk >= nchunks) chunk = nchunks - 1;
         const int k = chunk * WS_KCH + 4 * kq;
         const bool first = k < a.c0;
         const float *src = first ? A0 + k : A1 + (k - a.c0);
-        const int ld = first ? a.a0_ld : a.a1_ld;
+        const int ld = first ? ld0 : ld1;
         pvalid = 0;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -152,11 +164,23 @@ __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args
         double *csum = reinterpret_cast<double *>(Vb);           // scratch in the still unused V buffers: K <= 1024 -> 16 KB + 1 KB
         double *gst = csum + 2 * K;
         const int groups = a.fold_groups, cpg = K / groups;
+        const int fc0 = ws_uniform(a.c0), fc1 = ws_uniform(a.c1);
+        const int fmt0 = ws_uniform(a.fold_fmt0), fmt1 = ws_uniform(a.fold_fmt1);
+        const int rows0 = ws_uniform(a.fold_rows0), rows1 = ws_uniform(a.fold_rows1);
+        const float *st0 = ws_uniform(a.fold_stats0), *st1 = ws_uniform(a.fold_stats1);
+        // gamma / beta of this thread's channels (K <= 1024: at most two) ride with the statistics requests
+        float fgam[2], fbet[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int c = tid + i * WS_NT;
+            fgam[i] = a.fold_gamma[c < K ? c : 0];
+            fbet[i] = a.fold_beta[c < K ? c : 0];
+        }
         for (int c = tid; c < K; c += WS_NT) {
-            const bool first = c < a.c0;
-            const int cl = first ? c : c - a.c0, cw = first ? a.c0 : a.c1;
-            const int fmt = first ? a.fold_fmt0 : a.fold_fmt1, rows = first ? a.fold_rows0 : a.fold_rows1;
-            const float *st = first ? a.fold_stats0 : a.fold_stats1;
+            const bool first = c < fc0;
+            const int cl = first ? c : c - fc0, cw = first ? fc0 : fc1;
+            const int fmt = first ? fmt0 : fmt1, rows = first ? rows0 : rows1;
+            const float *st = first ? st0 : st1;
             double s = 0.0, qq = 0.0;
             if (fmt) {
                 const double *sd = reinterpret_cast<const double *>(st) + ((int64_t)b * cw + cl) * 2;
@@ -189,11 +213,15 @@ __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args
             gst[2 * tid + 1] = 1.0 / sqrt(var + (double)a.fold_eps);
         }
         __syncthreads();
-        for (int c = tid; c < K; c += WS_NT) {
-            const int g = c / cpg;
-            const double sc = gst[2 * g + 1] * (double)a.fold_gamma[c];
-            aff_sc[c] = (float)sc;
-            aff_sh[c] = (float)((double)a.fold_beta[c] - gst[2 * g] * sc);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int c = tid + i * WS_NT;
+            if (c < K) {
+                const int g = c / cpg;
+                const double sc = gst[2 * g + 1] * (double)fgam[i];
+                aff_sc[c] = (float)sc;
+                aff_sh[c] = (float)((double)fbet[i] - gst[2 * g] * sc);
+            }
         }
         __syncthreads();
     } else if (a.gn_scale) {
