@@ -28,6 +28,8 @@ BAR_CONV1 = 2e-5                         # 1x1 (cfg 0 / 1 / 4 / 5) and the atten
 BAR_GN = 2e-5                            # OP_GN_BWD dx / dgamma / dbeta and the gnb_partial rows: test_gn_silu_backward,
 #                                          test_f43_data_gradient_writes_the_gn_backward_partials
 BAR_SOFTMAX = 2e-5                       # softmax backward chain: test_softmax_backward_and_transpose, 1e-5 per op, two ops
+# the four bars below are the caps of tests/train_op_cases.py, whose element tests (tests/test_gpu_train_op_elements.py) hold the same
+# kernels per output row to max(FLOOR, 4 r32) under them, and run colsum_fold (exempt here) at the shapes of its unrolled loop
 BAR_LINEAR = 1e-5                        # test_linear_small_backward
 BAR_HEAD = 2e-5                          # test_conv_head_backward, test_conv_stem_backward
 BAR_HEAD_DW = 5e-5                       # test_conv_head_backward (dW)
