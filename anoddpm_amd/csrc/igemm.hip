@@ -25,6 +25,7 @@
 // all 16 16-byte slots of the 256-byte bank row.  B: [k/4][n][4], lanes read consecutive n ->
 // conflict-free by construction.
 #include "common.h"
+#include "gn_stats.h"
 
 using anoddpm::silu_f;
 
@@ -442,56 +443,25 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const anoddpm_igemm_
 // writes (same format as the igemm epilogue's statistics) -- no separate pass over the tensor.
 __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const anoddpm_igemm_args a, const int nslab)
 {
-    __shared__ float lds_s[256 * 4];
-    __shared__ float lds_q[256 * 4];
-    const int P = a.H * a.W, N = a.N, N4 = N >> 2;
+    const int P = a.H * a.W, N = a.N;
     const int Z = a.B * a.heads;                  // heads == 1 here
-    const int TQ = N4 < 256 ? N4 : 256;
-    const int R = 256 / TQ;
-    const int npass = (N4 + TQ - 1) / TQ;
-    const int tid = threadIdx.x;
-    const int tq = tid % TQ, tr = tid / TQ;
     const int z = blockIdx.y, slab = blockIdx.x;
-    const int sp = (P + nslab - 1) / nslab;
-    const int p0 = slab * sp;
-    const int p1 = (p0 + sp < P) ? p0 + sp : P;
     float *st = a.stats + ((int64_t)z * nslab + slab) * N * 2;
-    for (int pass = 0; pass < npass; ++pass) {
-        const int n4 = pass * TQ + tq;
-        f32x4 cs = {0.f, 0.f, 0.f, 0.f}, cq = {0.f, 0.f, 0.f, 0.f};
-        if (tr < R && n4 < N4) {
-            f32x4 add = {0.f, 0.f, 0.f, 0.f};
-            if (a.bias) add += ld4(a.bias + n4 * 4);
-            if (a.temb) add += ld4(a.temb + (int64_t)z * a.temb_ld + n4 * 4);
-            for (int pix = p0 + tr; pix < p1; pix += R) {
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    anoddpm::slab_column_sums(N, P, nslab, slab, st, [&](int n4) {
+        f32x4 add = {0.f, 0.f, 0.f, 0.f};
+        if (a.bias) add += ld4(a.bias + n4 * 4);
+        if (a.temb) add += ld4(a.temb + (int64_t)z * a.temb_ld + n4 * 4);
+        return [&a, add, n4, z, Z, P, N](int pix) {
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
-                for (int ks = 0; ks < a.ksplit; ++ks)
-                    v += ld4(a.ws + ((((int64_t)ks * Z + z) * P + pix) * N) + n4 * 4);
-                v = v * a.alpha + add;
-                if (a.res) v += ld4(a.res + (int64_t)z * a.r_bs + (int64_t)pix * a.res_ld + n4 * 4);
-                *reinterpret_cast<f32x4 *>(a.out + (int64_t)z * a.o_bs + (int64_t)pix * a.out_ld + n4 * 4) = v;
-                cs += v;
-                cq += v * v;
-            }
-        }
-        if (tr < R) {
-            const int o = (tr * TQ + tq) * 4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { lds_s[o + e] = cs[e]; lds_q[o + e] = cq[e]; }
-        }
-        __syncthreads();
-        for (int cl = tid; cl < TQ * 4; cl += 256) {
-            const int c = pass * TQ * 4 + cl;
-            if (c < N) {
-                float s = 0.f, q = 0.f;
-                for (int r = 0; r < R; ++r) { s += lds_s[r * TQ * 4 + cl]; q += lds_q[r * TQ * 4 + cl]; }
-                st[c * 2] = s;
-                st[c * 2 + 1] = q;
-            }
-        }
-        __syncthreads();
-    }
+            for (int ks = 0; ks < a.ksplit; ++ks)
+                v += ld4(a.ws + ((((int64_t)ks * Z + z) * P + pix) * N) + n4 * 4);
+            v = v * a.alpha + add;
+            if (a.res) v += ld4(a.res + (int64_t)z * a.r_bs + (int64_t)pix * a.res_ld + n4 * 4);
+            *reinterpret_cast<f32x4 *>(a.out + (int64_t)z * a.o_bs + (int64_t)pix * a.out_ld + n4 * 4) = v;
+            return v;
+        };
+    });
 }
 
 // Split-K tail partitioned by (GroupNorm group, image): grid (tail_groups, Z).  A block folds the K slabs of ITS channels over
@@ -583,11 +553,8 @@ __global__ __launch_bounds__(GT_NT) void splitk_reduce_gn_kernel(const anoddpm_i
             S += src[0];
             Q += src[1];
         }
-        const double n = (double)P * cpg;
-        const double mean = S / n;
-        double var = Q / n - mean * mean;
-        var = var > 0.0 ? var : 0.0;
-        const double rstd = 1.0 / sqrt(var + (double)a.tail_eps);
+        double mean, rstd;
+        anoddpm::gn_moments(S, Q, (double)P * cpg, a.tail_eps, &mean, &rstd);
         grp[0] = mean;
         grp[1] = rstd;
         if (a.tail_mean) {
@@ -598,9 +565,7 @@ __global__ __launch_bounds__(GT_NT) void splitk_reduce_gn_kernel(const anoddpm_i
     __syncthreads();
     if (tid < cpg) {
         const int c = c_lo + tid;
-        const double sc = grp[1] * (double)a.tail_gamma[c];
-        a.tail_scale[(int64_t)z * C + c] = (float)sc;
-        a.tail_shift[(int64_t)z * C + c] = (float)((double)a.tail_beta[c] - grp[0] * sc);
+        anoddpm::gn_affine(grp[0], grp[1], a.tail_gamma[c], a.tail_beta[c], &a.tail_scale[(int64_t)z * C + c], &a.tail_shift[(int64_t)z * C + c]);
     }
 }
 

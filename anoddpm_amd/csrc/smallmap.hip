@@ -5,7 +5,7 @@
 // fusions as the other contraction kernels -- GroupNorm32-apply + SiLU on the operand (UNet.py:170-171,190-191,113), the virtual
 // torch.cat([h, skip]) (UNet.py:402), bias / timestep-embedding / residual adds, the GroupNorm partial sums of the output -- and one
 // more: the GroupNorm FINALIZE of the operand (UNet.py:409-411) runs in this kernel's prologue from the producer's statistics
-// rows (`fold_*`), so that no anoddpm_gn_finalize launch sits between producer and consumer.
+// rows (`fold_*`, gn_fold_prologue of gn_stats.h), so that no anoddpm_gn_finalize launch sits between producer and consumer.
 //
 // Why another kernel.  On these maps the whole batch is M = B * P <= 1024 output rows against K' = taps * K up to 9216: the
 // 64 x 64-tile kernel (igemm.hip) has to split K over 8-16 workgroups per tile to fill 256 CUs and then needs a second launch
@@ -22,11 +22,13 @@
 // (block id mod 8) share weight columns in their L2.
 #include "buf_load.h"
 #include "common.h"
+#include "gn_stats.h"
 
 using anoddpm::buf_load4;
 using anoddpm::buf_rsrc;
 using anoddpm::f32x4;
 using anoddpm::silu_f;
+using anoddpm::uniform;
 
 namespace {
 
@@ -34,18 +36,6 @@ constexpr int SM_NT = 512;                 // 8 waves: they split K'
 
 __host__ __device__ constexpr int sm_kch(int ks) { return ks == 3 ? 256 : 512; }     // channels per K chunk: 32 / 64 per wave
 __host__ __device__ constexpr int sm_hpix(int ks, int tm, int w) { return ks == 1 ? tm : (tm / w + 2) * (w + 2); }
-
-// A kernel argument as a scalar VALUE.  `lane_cond ? a.x : a.y` on two fields of the argument struct is otherwise compiled as a select
-// of the fields' ADDRESSES and a global_load from the kernarg segment, followed by s_waitcnt vmcnt(0): vmcnt retires in order, so that
-// wait drains every operand request in flight (profiles/r7_small_kernel_waits.txt).
-__device__ __forceinline__ int sm_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-template <typename T>
-__device__ __forceinline__ const T *sm_uniform(const T *p)
-{
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32));
-    return reinterpret_cast<const T *>(((uint64_t)hi << 32) | lo);
-}
 
 template <int KS, int RT, int CT, int LOG2W>
 __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_args a)
@@ -123,7 +113,7 @@ __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_arg
     }
     f32x4 araw[NI];
     unsigned avalid = 0;
-    const int ld0 = sm_uniform(a.a0_ld), ld1 = sm_uniform(a.a1_ld);     // the values, not the fields: `first` depends on the lane
+    const int ld0 = uniform(a.a0_ld), ld1 = uniform(a.a1_ld);     // the values, not the fields: `first` depends on the lane
     auto load_A = [&](int chunk) {
         const int k = chunk * KCH + 4 * kq;
         const bool kv = k < K;
@@ -161,79 +151,9 @@ __global__ __launch_bounds__(SM_NT) void smallmap_kernel(const anoddpm_igemm_arg
     if (a.fold_gamma) {
         // scratch in the (still unused) staging buffers: per-channel fp64 {sum, sumsq}, then per-group {mean, rstd}
         double *csum = reinterpret_cast<double *>(Abuf);
-        double *gst = csum + 2 * Kpad;
-        const int groups = a.fold_groups, cpg = K / groups;
-        const int fc0 = sm_uniform(a.c0), fc1 = sm_uniform(a.c1);
-        const int fmt0 = sm_uniform(a.fold_fmt0), fmt1 = sm_uniform(a.fold_fmt1);
-        const int rows0 = sm_uniform(a.fold_rows0), rows1 = sm_uniform(a.fold_rows1);
-        const float *st0 = sm_uniform(a.fold_stats0), *st1 = sm_uniform(a.fold_stats1);
-        // gamma / beta of this thread's channels (K <= 1024: at most two) ride with the statistics requests; they are used
-        // two barriers later, by the same thread for the same channels
-        float fgam[2], fbet[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int c = tid + i * SM_NT;
-            fgam[i] = a.fold_gamma[c < K ? c : 0];
-            fbet[i] = a.fold_beta[c < K ? c : 0];
-        }
-        for (int c = tid; c < K; c += SM_NT) {
-            const bool first = c < fc0;
-            const int cl = first ? c : c - fc0, cw = first ? fc0 : fc1;
-            const int fmt = first ? fmt0 : fmt1, rows = first ? rows0 : rows1;
-            const float *st = first ? st0 : st1;
-            double s = 0.0, qq = 0.0;
-            if (fmt) {
-                const double *sd = reinterpret_cast<const double *>(st) + ((int64_t)b * cw + cl) * 2;
-                s = sd[0]; qq = sd[1];
-            } else {
-                const float *sr = st + ((int64_t)b * rows * cw + cl) * 2;
-                for (int r0 = 0; r0 < rows; r0 += 4) {           // four independent row loads in flight; summed in row order
-                    float2 v[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int r = r0 + u < rows ? r0 + u : rows - 1;
-                        v[u] = *reinterpret_cast<const float2 *>(sr + (int64_t)r * cw * 2);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (r0 + u < rows) { s += (double)v[u].x; qq += (double)v[u].y; }
-                }
-            }
-            csum[2 * c] = s; csum[2 * c + 1] = qq;
-        }
-        __syncthreads();
-        if (tid < groups) {
-            double S = 0.0, Q = 0.0;
-            for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) { S += csum[2 * c]; Q += csum[2 * c + 1]; }   // channel order
-            const double n = (double)P * cpg;
-            const double mean = S / n;
-            double var = Q / n - mean * mean;
-            var = var > 0.0 ? var : 0.0;
-            gst[2 * tid] = mean;
-            gst[2 * tid + 1] = 1.0 / sqrt(var + (double)a.fold_eps);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int c = tid + i * SM_NT;
-            if (c < Kpad) {
-                float scv = 0.f, shv = 0.f;
-                if (c < K) {
-                    const int g = c / cpg;
-                    const double sc = gst[2 * g + 1] * (double)fgam[i];
-                    scv = (float)sc;
-                    shv = (float)((double)fbet[i] - gst[2 * g] * sc);
-                }
-                aff_sc[c] = scv; aff_sh[c] = shv;
-            }
-        }
-        __syncthreads();
+        anoddpm::gn_fold_prologue<SM_NT>(a, b, tid, K, Kpad, P, csum, csum + 2 * Kpad, aff_sc, aff_sh);
     } else if (a.gn_scale) {
-        for (int c = tid; c < Kpad; c += SM_NT) {
-            aff_sc[c] = c < K ? a.gn_scale[(int64_t)b * a.gn_ld + c] : 0.f;
-            aff_sh[c] = c < K ? a.gn_shift[(int64_t)b * a.gn_ld + c] : 0.f;
-        }
-        __syncthreads();
+        anoddpm::gn_affine_table_copy<SM_NT>(a, b, tid, K, Kpad, aff_sc, aff_sh);
     }
     store_A(0);
     __syncthreads();
@@ -388,12 +308,7 @@ int launch_smallmap(const anoddpm_igemm_args *a, hipStream_t s)
                     "smallmap: pixel strides must be multiples of 4 floats");
     ANODDPM_REQUIRE(!a->tail_csum, "smallmap: no split-K tail");
     ANODDPM_REQUIRE(!a->gn_scale || a->gn_shift, "smallmap: gn_scale without gn_shift");
-    if (a->fold_gamma) {
-        ANODDPM_REQUIRE(a->fold_beta && a->fold_stats0 && (a->c1 == 0 || a->fold_stats1), "smallmap: GroupNorm fold: null pointer");
-        ANODDPM_REQUIRE(a->fold_groups >= 1 && a->fold_groups <= 64 && K % a->fold_groups == 0, "smallmap: GroupNorm fold: bad group count");
-        ANODDPM_REQUIRE((a->fold_fmt0 != 0 || a->fold_rows0 >= 1) && (a->c1 == 0 || a->fold_fmt1 != 0 || a->fold_rows1 >= 1),
-                        "smallmap: GroupNorm fold: statistics rows missing");
-    }
+    if (int rc = check_fold_args(a, K, "smallmap")) return rc;
     const int rt = tile >> 4, ct = tile & 15;
     const int TM = 16 * rt, TN = 16 * ct;
     const int P = a->H * a->W;

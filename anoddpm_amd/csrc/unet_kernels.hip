@@ -3,8 +3,13 @@
 // layers, sinusoidal timestep features, the Cin<=4 stem convolution and the NHWC->NCHW edge copy.
 // All of them stream NHWC fp32 with 16-byte lanes; roofline = HBM.
 #include "common.h"
+#include "gn_stats.h"
 
+using anoddpm::gn_affine;
+using anoddpm::gn_moments;
+using anoddpm::gf_f32x4;
 using anoddpm::silu_f;
+using anoddpm::slab_column_sums;
 
 namespace {
 
@@ -100,66 +105,25 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(anoddpm_gn_args a)
     if (tid < a.groups) {
         double ts = 0.0, tq = 0.0;
         for (int l = 0; l < lanes; ++l) { ts += red_s[l * a.groups + tid]; tq += red_q[l * a.groups + tid]; }
-        const double n = (double)a.P * cpg;
-        const double mean = ts / n;
-        double var = tq / n - mean * mean;
-        var = var > 0.0 ? var : 0.0;
-        mean_s[tid] = mean;
-        rstd_s[tid] = 1.0 / sqrt(var + (double)a.eps);
+        gn_moments(ts, tq, (double)a.P * cpg, a.eps, &mean_s[tid], &rstd_s[tid]);
     }
     __syncthreads();
     for (int c = tid; c < C; c += blockDim.x) {
         const int gg = c / cpg;
-        const double sc = rstd_s[gg] * (double)a.gamma[c];
-        a.scale[(int64_t)b * C + c] = (float)sc;
-        a.shift[(int64_t)b * C + c] = (float)((double)a.beta[c] - mean_s[gg] * sc);
+        gn_affine(mean_s[gg], rstd_s[gg], a.gamma[c], a.beta[c], &a.scale[(int64_t)b * C + c], &a.shift[(int64_t)b * C + c]);
     }
 }
 
-// Per-channel partial sums (same format as the igemm epilogue's fused statistics).
+// Per-channel partial sums (same format as the igemm epilogue's fused statistics): grid (nslab, B).
 __global__ __launch_bounds__(256) void chan_stats_kernel(anoddpm_chan_stats_args a)
 {
-    __shared__ float lds_s[256 * 4];
-    __shared__ float lds_q[256 * 4];
-    const int C4 = a.C >> 2;
-    const int TQ = C4 < 256 ? C4 : 256;
-    const int R = 256 / TQ;
-    const int npass = (C4 + TQ - 1) / TQ;
-    const int tid = threadIdx.x;
-    const int tq = tid % TQ, tr = tid / TQ;
     const int b = blockIdx.y, slab = blockIdx.x;
-    const int sp = (a.P + a.nslab - 1) / a.nslab;
-    const int p0 = slab * sp;
-    const int p1 = (p0 + sp < a.P) ? p0 + sp : a.P;
-    float *out = a.stats + ((int64_t)b * a.nslab + slab) * a.C * 2;
-    for (int pass = 0; pass < npass; ++pass) {
-        const int quad = pass * TQ + tq;
-        float s0 = 0, s1 = 0, s2 = 0, s3 = 0, q0 = 0, q1 = 0, q2 = 0, q3 = 0;
-        if (tr < R && quad < C4) {
-            const float *src = a.a + (int64_t)b * a.a_bs + quad * 4;
-            for (int p = p0 + tr; p < p1; p += R) {
-                const float4 v = *reinterpret_cast<const float4 *>(src + (int64_t)p * a.a_ld);
-                s0 += v.x; s1 += v.y; s2 += v.z; s3 += v.w;
-                q0 += v.x * v.x; q1 += v.y * v.y; q2 += v.z * v.z; q3 += v.w * v.w;
-            }
-        }
-        if (tr < R) {
-            const int o = (tr * TQ + tq) * 4;
-            lds_s[o] = s0; lds_s[o + 1] = s1; lds_s[o + 2] = s2; lds_s[o + 3] = s3;
-            lds_q[o] = q0; lds_q[o + 1] = q1; lds_q[o + 2] = q2; lds_q[o + 3] = q3;
-        }
-        __syncthreads();
-        for (int cl = tid; cl < TQ * 4; cl += 256) {
-            const int c = pass * TQ * 4 + cl;
-            if (c < a.C) {
-                float s = 0.f, q = 0.f;
-                for (int r = 0; r < R; ++r) { s += lds_s[r * TQ * 4 + cl]; q += lds_q[r * TQ * 4 + cl]; }
-                out[c * 2] = s;
-                out[c * 2 + 1] = q;
-            }
-        }
-        __syncthreads();
-    }
+    float *row = a.stats + ((int64_t)b * a.nslab + slab) * a.C * 2;
+    slab_column_sums(a.C, a.P, a.nslab, slab, row, [&](int quad) {
+        const float *src = a.a + (int64_t)b * a.a_bs + quad * 4;
+        const int ld = a.a_ld;
+        return [=](int p) { return *reinterpret_cast<const gf_f32x4 *>(src + (int64_t)p * ld); };
+    });
 }
 
 // grid (groups, B): fold per-channel partials of up to two sources into scale/shift for one group.
@@ -242,16 +206,11 @@ __global__ __launch_bounds__(256) void gn_finalize2_kernel(anoddpm_gn_finalize_a
     __syncthreads();
     const double ts = ((red_s[0] + red_s[1]) + red_s[2]) + red_s[3];
     const double tq = ((red_q[0] + red_q[1]) + red_q[2]) + red_q[3];
-    const double n = (double)a.P * cpg;
-    const double mean = ts / n;
-    double var = tq / n - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    const double rstd = 1.0 / sqrt(var + (double)a.eps);
+    double mean, rstd;
+    gn_moments(ts, tq, (double)a.P * cpg, a.eps, &mean, &rstd);
     if (tid < cpg) {
         const int c = g * cpg + tid;
-        const double sc = rstd * (double)a.gamma[c];
-        a.scale[(int64_t)b * C + c] = (float)sc;
-        a.shift[(int64_t)b * C + c] = (float)((double)a.beta[c] - mean * sc);
+        gn_affine(mean, rstd, a.gamma[c], a.beta[c], &a.scale[(int64_t)b * C + c], &a.shift[(int64_t)b * C + c]);
     }
     if (tid == 0 && a.mean_out) {
         a.mean_out[(int64_t)b * a.groups + g] = (float)mean;

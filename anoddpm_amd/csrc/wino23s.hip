@@ -3,7 +3,7 @@
 // Replaces, on those maps, what winograd.hip does in two or three launches: the 3x3 convolutions of the ResBlocks
 // (UNet.py:172,193) with GroupNorm32-apply + SiLU (UNet.py:170-171,190-191), the nearest-x2 of an up block (UNet.py:89,206),
 // the virtual torch.cat([h, skip]) (UNet.py:402), bias / timestep-embedding / residual adds, the GroupNorm partial sums of the
-// output -- and, as smallmap.hip, the GroupNorm FINALIZE of the operand in the prologue (`fold_*`, UNet.py:409-411).
+// output -- and the GroupNorm FINALIZE of the operand in the prologue (`fold_*`, UNet.py:409-411; gn_fold_prologue of gn_stats.h).
 //
 // Why.  winograd.hip's workgroup is 32 tiles x 128 channels: a 16x16 map of a batch of four is 8 such patches, so it splits K
 // over eight workgroups per patch to fill 256 CUs and needs a tail launch to fold the slabs (plus a GroupNorm finalize for its
@@ -19,11 +19,13 @@
 // patch(c+3).  The B operand streams from L2 through a register ring (buffer loads, scalar offsets), two steps ahead.
 #include "buf_load.h"
 #include "common.h"
+#include "gn_stats.h"
 
 using anoddpm::buf_load4;
 using anoddpm::buf_rsrc;
 using anoddpm::f32x4;
 using anoddpm::silu_f;
+using anoddpm::uniform;
 
 namespace {
 
@@ -33,17 +35,6 @@ constexpr int WS_PITCH = WS_KCH + 4;       // floats between pixels (patch) / ti
 constexpr int WS_PPX = 100;                // 10 x 10 input pixels: the 8 x 8 outputs of a workgroup + halo
 constexpr int WS_VBUF = 16 * 16 * WS_PITCH;    // floats per V buffer [pos][tile][PITCH]
 constexpr int WS_PBUF = 104 * WS_PITCH;        // floats per patch buffer (100 pixels + slack for the unconditional last slot)
-
-// A kernel argument as a scalar VALUE (as sm_uniform of smallmap.hip): a lane-dependent choice between two fields of the argument
-// struct is otherwise a select of their addresses, a global_load from the kernarg segment and s_waitcnt vmcnt(0) in every chunk.
-__device__ __forceinline__ int ws_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-template <typename T>
-__device__ __forceinline__ const T *ws_uniform(const T *p)
-{
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32));
-    return reinterpret_cast<const T *>(((uint64_t)hi << 32) | lo);
-}
 
 template <int CT>                           // 16-channel column tiles per workgroup: 2 (32 channels) or 4 (64)
 __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args a)
@@ -106,7 +97,7 @@ __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args
     }
     f32x4 praw[2];
     unsigned pvalid = 0;
-    const int ld0 = ws_uniform(a.a0_ld), ld1 = ws_uniform(a.a1_ld);     // the values, not the fields: `first` depends on the lane
+    const int ld0 = uniform(a.a0_ld), ld1 = uniform(a.a1_ld);     // the values, not the fields: `first` depends on the lane
     auto load_patch = [&](int chunk) {
         if (chunk >= nchunks) chunk = nchunks - 1;
         const int k = chunk * WS_KCH + 4 * kq;
@@ -159,77 +150,13 @@ __global__ __launch_bounds__(WS_NT) void wino23s_kernel(const anoddpm_igemm_args
     };
 
     load_patch(0);
-    // ---- GroupNorm affine of the operand: given, or finished here from the producers' statistics (as smallmap.hip) ----
+    // ---- GroupNorm affine of the operand: given, or finished here from the producers' statistics ----
     if (a.fold_gamma) {
         double *csum = reinterpret_cast<double *>(Vb);           // scratch in the still unused V buffers: K <= 1024 -> 16 KB + 1 KB
-        double *gst = csum + 2 * K;
-        const int groups = a.fold_groups, cpg = K / groups;
-        const int fc0 = ws_uniform(a.c0), fc1 = ws_uniform(a.c1);
-        const int fmt0 = ws_uniform(a.fold_fmt0), fmt1 = ws_uniform(a.fold_fmt1);
-        const int rows0 = ws_uniform(a.fold_rows0), rows1 = ws_uniform(a.fold_rows1);
-        const float *st0 = ws_uniform(a.fold_stats0), *st1 = ws_uniform(a.fold_stats1);
-        // gamma / beta of this thread's channels (K <= 1024: at most two) ride with the statistics requests
-        float fgam[2], fbet[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int c = tid + i * WS_NT;
-            fgam[i] = a.fold_gamma[c < K ? c : 0];
-            fbet[i] = a.fold_beta[c < K ? c : 0];
-        }
-        for (int c = tid; c < K; c += WS_NT) {
-            const bool first = c < fc0;
-            const int cl = first ? c : c - fc0, cw = first ? fc0 : fc1;
-            const int fmt = first ? fmt0 : fmt1, rows = first ? rows0 : rows1;
-            const float *st = first ? st0 : st1;
-            double s = 0.0, qq = 0.0;
-            if (fmt) {
-                const double *sd = reinterpret_cast<const double *>(st) + ((int64_t)b * cw + cl) * 2;
-                s = sd[0]; qq = sd[1];
-            } else {
-                const float *sr = st + ((int64_t)b * rows * cw + cl) * 2;
-                for (int r0 = 0; r0 < rows; r0 += 4) {
-                    float2 v[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int r = r0 + u < rows ? r0 + u : rows - 1;
-                        v[u] = *reinterpret_cast<const float2 *>(sr + (int64_t)r * cw * 2);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (r0 + u < rows) { s += (double)v[u].x; qq += (double)v[u].y; }
-                }
-            }
-            csum[2 * c] = s; csum[2 * c + 1] = qq;
-        }
-        __syncthreads();
-        if (tid < groups) {
-            double S = 0.0, Q = 0.0;
-            for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) { S += csum[2 * c]; Q += csum[2 * c + 1]; }
-            const double n = (double)(up ? P / 4 : P) * cpg;    // the statistics are those of the (possibly half-resolution) source
-            const double mean = S / n;
-            double var = Q / n - mean * mean;
-            var = var > 0.0 ? var : 0.0;
-            gst[2 * tid] = mean;
-            gst[2 * tid + 1] = 1.0 / sqrt(var + (double)a.fold_eps);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int c = tid + i * WS_NT;
-            if (c < K) {
-                const int g = c / cpg;
-                const double sc = gst[2 * g + 1] * (double)fgam[i];
-                aff_sc[c] = (float)sc;
-                aff_sh[c] = (float)((double)fbet[i] - gst[2 * g] * sc);
-            }
-        }
-        __syncthreads();
+        // the statistics are those of the (possibly half-resolution) source
+        anoddpm::gn_fold_prologue<WS_NT>(a, b, tid, K, K, up ? P / 4 : P, csum, csum + 2 * K, aff_sc, aff_sh);
     } else if (a.gn_scale) {
-        for (int c = tid; c < K; c += WS_NT) {
-            aff_sc[c] = a.gn_scale[(int64_t)b * a.gn_ld + c];
-            aff_sh[c] = a.gn_shift[(int64_t)b * a.gn_ld + c];
-        }
-        __syncthreads();
+        anoddpm::gn_affine_table_copy<WS_NT>(a, b, tid, K, K, aff_sc, aff_sh);
     }
     // prologue: patch(0) -> LDS -> V(0); patch(1) -> LDS; patch(2) requested
     store_patch(0);
@@ -378,12 +305,7 @@ int launch_wino23s(const anoddpm_igemm_args *a, hipStream_t s)
     ANODDPM_REQUIRE(!a->tail_csum, "wino23s: no split-K tail");
     ANODDPM_REQUIRE(!a->gn_scale || a->gn_shift, "wino23s: gn_scale without gn_shift");
     ANODDPM_REQUIRE((int64_t)16 * K * a->N * 4 < ((int64_t)1 << 31), "wino23s: transformed weights exceed 32-bit buffer offsets");
-    if (a->fold_gamma) {
-        ANODDPM_REQUIRE(a->fold_beta && a->fold_stats0 && (a->c1 == 0 || a->fold_stats1), "wino23s: GroupNorm fold: null pointer");
-        ANODDPM_REQUIRE(a->fold_groups >= 1 && a->fold_groups <= 64 && K % a->fold_groups == 0, "wino23s: GroupNorm fold: bad group count");
-        ANODDPM_REQUIRE((a->fold_fmt0 != 0 || a->fold_rows0 >= 1) && (a->c1 == 0 || a->fold_fmt1 != 0 || a->fold_rows1 >= 1),
-                        "wino23s: GroupNorm fold: statistics rows missing");
-    }
+    if (int rc = check_fold_args(a, K, "wino23s")) return rc;
     const size_t lds = (size_t)(2 * K + 2 * WS_VBUF + 2 * WS_PBUF) * sizeof(float);
     ANODDPM_REQUIRE(lds <= 160 * 1024, "wino23s: LDS budget exceeded");
     dim3 grid((unsigned)(a->N / (16 * ct)), (unsigned)(a->B * (a->H / 8) * (a->W / 8)));

@@ -674,12 +674,17 @@ class _Plan:
 
     fuse_gn_tail = True          # split-K tails fold the consumer's GroupNorm in (anoddpm_igemm_args.tail_*); see gn()
 
+    def stats_triple(self, src):
+        """(pointer, rows, fmt) of the partial sums of tensor `src`: fmt 0 = `rows` fp32 rows per image, fmt 1 = one fp64 row."""
+        kind, buf, extra = self.stats_of[src.data_ptr()]
+        return (buf.data_ptr(), extra, 0) if kind == "rows" else (buf.data_ptr(), 1, 1)
+
     def stats_source(self, st, which, src, c):
         """Point the `which`-th statistics source of a GnFinalizeArgs at the partial sums of tensor `src`."""
-        kind, buf, extra = self.stats_of[src.data_ptr()]
-        setattr(st, f"stats{which}", buf.data_ptr())
-        setattr(st, f"rows{which}", extra if kind == "rows" else 1)
-        setattr(st, f"fmt{which}", 0 if kind == "rows" else 1)
+        ptr, rows, fmt = self.stats_triple(src)
+        setattr(st, f"stats{which}", ptr)
+        setattr(st, f"rows{which}", rows)
+        setattr(st, f"fmt{which}", fmt)
 
     def gn_tail_job(self, srcs, gamma, beta, want_mean=False):
         """GroupNorm over `srcs` finished inside the split-K tail that produces srcs[0] (no launch of its own): possible when that
@@ -761,10 +766,7 @@ class _Plan:
         if fold and C % 32 == 0:
             d = _GnFold()
             d.gamma, d.beta, d.groups, d.eps = gamma, beta, 32, 1e-5
-            d.src = []
-            for s in srcs:
-                kind, buf, extra = self.stats_of[s[0].data_ptr()]
-                d.src.append((buf.data_ptr(), extra if kind == "rows" else 1, 0 if kind == "rows" else 1))
+            d.src = [self.stats_triple(s[0]) for s in srcs]
             return d
         return self.gn_finalize(srcs, P, gamma, beta)
 

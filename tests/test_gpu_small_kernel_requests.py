@@ -77,7 +77,20 @@ SMALLMAP = [
     (2, (128, 384), 32, 8, 3, "fold", 1, (4, 4)),      # statistics rows as an 8x8 producer writes them
     (1, (256, 768), 32, 16, 1, "no", 0, None),         # 1x1: two 512-channel chunks, the first one straddles
     (1, (256, 768), 32, 16, 1, "fold", 0, (16, 8)),
+    # 12 channels per group: group 21 lies in both sources; row counts that are no multiples of four; Kpad = 512 > K (zero fill)
+    (2, (256, 128), 32, 8, 3, "fold", 1, (3, 5)),
+    # the second source hands over one fp64 row (fmt 1), as a split-K tail's tail_csum; group 10 straddles
+    (2, (128, 256), 32, 8, 3, "fold", 1, (3, "fp64")),
 ]
+
+
+def fold_stats(src, rows):
+    """(statistics tensor, fmt) of one NHWC source: `rows` fp32 rows from chan_stats, or the fp64 sums [B][c][2] of a split-K tail."""
+    import hipops
+    if rows != "fp64":
+        return hipops.chan_stats(src, nslab=rows), 0
+    of = src.double().reshape(src.shape[0], -1, src.shape[-1])
+    return torch.stack([of.sum(1), (of * of).sum(1)], dim=-1).contiguous(), 1
 
 
 @pytest.mark.parametrize("case", SMALLMAP, ids=[f"{c[4]}x{c[4]}_{c[3]}x{c[3]}_{c[1][0]}+{c[1][1]}_{c[5]}" for c in SMALLMAP])
@@ -99,7 +112,7 @@ def test_smallmap_pitched_concat(case):
     if gn_mode == "given":
         gn = hipops.gn_affine(srcs, gamma.to(dev()), beta.to(dev()))
     elif gn_mode == "fold":
-        fold = dict(stats=[(hipops.chan_stats(s_, nslab=r_), 0) for s_, r_ in zip(srcs, rows)], gamma=gamma.to(dev()), beta=beta.to(dev()))
+        fold = dict(stats=[fold_stats(s_, r_) for s_, r_ in zip(srcs, rows)], gamma=gamma.to(dev()), beta=beta.to(dev()))
     got, got_p = run_both(srcs, w, b, [(8, 4), (4, 24)], Hout=H, ks=ks, gn=gn, act=act, fold=fold, temb=temb.to(dev()),
                           res=hipops.nhwc(res.to(dev())), cfg=5, stats_out=[])
     e, ep = relerr(hipops.nchw(got), ref), relerr(hipops.nchw(got_p), ref)
@@ -108,16 +121,23 @@ def test_smallmap_pitched_concat(case):
     assert torch.equal(got, got_p)
 
 
-WINO23S = [(ct, a_mode) for ct in (2, 4) for a_mode in (0, 1)]
+WINO23S = [(ct, a_mode, c0, c1, rows) for (c0, c1, rows) in ((96, 160, (4, 16)), (256, 128, (3, 5))) for ct in (2, 4) for a_mode in (0, 1)]
+WINO23S.append((2, 1, 96, 160, (4, "fp64")))         # fmt 1 on the second source, normalised at the half resolution
 
 
-@pytest.mark.parametrize("ct,a_mode", WINO23S, ids=[f"ct{c}_amode{m}" for c, m in WINO23S])
-def test_wino23s_pitched_concat_fold(ct, a_mode):
-    """16x16 map, batch 1, K = 96 + 160; the output widths are the smallest at which the launcher's tile rule picks the 32- (ct 2)
-    and the 64-channel (ct 4) workgroup for four 8x8 blocks.  Fold from 4 statistics rows on one source and 16 on the other."""
+def wino23s_id(c):
+    ct, a_mode, c0, c1, rows = c
+    return f"ct{ct}_amode{a_mode}" + ("" if (c0, c1) == (96, 160) and rows == (4, 16) else f"_{c0}+{c1}_rows{rows[0]}+{rows[1]}")
+
+
+@pytest.mark.parametrize("ct,a_mode,c0,c1,rows", WINO23S, ids=[wino23s_id(c) for c in WINO23S])
+def test_wino23s_pitched_concat_fold(ct, a_mode, c0, c1, rows):
+    """16x16 map, batch 1, K = 96 + 160 or 256 + 128 (12 channels per group: group 21 lies in both sources); the output widths are
+    the smallest at which the launcher's tile rule picks the 32- (ct 2) and the 64-channel (ct 4) workgroup for four 8x8 blocks.
+    Fold from `rows` statistics rows per source (fp32 rows, or "fp64": the one fp64 row a split-K tail hands over)."""
     import hipops
     from anoddpm_amd._lib import lib
-    B, c0, c1, H = 1, 96, 160, 16
+    B, H = 1, 16
     N = 1024 if ct == 2 else 3200
     C = c0 + c1
     assert lib().anoddpm_wino23s_tile(H, H, C, c0, N, B, a_mode) == ct
@@ -130,12 +150,11 @@ def test_wino23s_pitched_concat_fold(ct, a_mode):
     ref = fused_reference(x, w, b, gamma, beta, True, 1, a_mode=a_mode, temb=temb, res=res)
     xs = hipops.nhwc(x.to(dev()))
     srcs = [xs[..., :c0].contiguous(), xs[..., c0:].contiguous()]
-    fold = dict(stats=[(hipops.chan_stats(srcs[0], nslab=4), 0), (hipops.chan_stats(srcs[1], nslab=16), 0)],
-                gamma=gamma.to(dev()), beta=beta.to(dev()))
+    fold = dict(stats=[fold_stats(s_, r_) for s_, r_ in zip(srcs, rows)], gamma=gamma.to(dev()), beta=beta.to(dev()))
     got, got_p = run_both(srcs, w, b, [(4, 12), (16, 0)], Hout=H, ks=3, act=1, a_mode=a_mode, fold=fold, temb=temb.to(dev()),
                           res=hipops.nhwc(res.to(dev())), cfg=6, stats_out=[])
     e, ep = relerr(hipops.nchw(got), ref), relerr(hipops.nchw(got_p), ref)
-    print(f"wino23s ct {ct} a_mode {a_mode}: contiguous {e:.2e}  pitched {ep:.2e}  (bar 1e-4)")
+    print(f"wino23s ct {ct} a_mode {a_mode} {c0}+{c1} rows {rows}: contiguous {e:.2e}  pitched {ep:.2e}  (bar 1e-4)")
     assert e < 1e-4 and ep < 1e-4
     assert torch.equal(got, got_p)
 
