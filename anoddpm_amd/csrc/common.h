@@ -60,6 +60,32 @@ int launch_wgrad43(const anoddpm_wgrad_args *a, hipStream_t s);      // wgrad43.
 int wgrad43_groups(int K, int N, int B, int H, int W);
 int wgrad43_colsum_items(int K, int N, int B, int H, int W);      // column-sum rows per image of algo 1
 
+// Pixel tiles per image of the anoddpm_igemm kernels (host).  Every launcher takes its grid from these and
+// anoddpm_igemm_stats_rows (igemm.hip) the statistics rows the launch writes, so that grid and row count cannot drift apart.
+struct direct_tiling { int log2TW, TH, tiles_x, tiles_y; };
+inline direct_tiling direct_tiles(int ks, int H, int W, int BM)      // cfg 0 / 1: BM pixels, two statistics rows (wave rows) each
+{
+    direct_tiling t;
+    if (ks == 1) {                    // the image as one row of P pixels
+        t.TH = 1;
+        t.log2TW = (BM == 128) ? 7 : 6;
+        t.tiles_x = (int)(((int64_t)H * W + BM - 1) / BM);
+        t.tiles_y = 1;
+    } else {
+        const int TW = W < 32 ? W : 32;
+        t.log2TW = 0;
+        while ((1 << t.log2TW) < TW) ++t.log2TW;
+        t.TH = BM / TW;
+        t.tiles_x = W / TW;
+        t.tiles_y = (H + t.TH - 1) / t.TH;
+    }
+    return t;
+}
+inline int wino_tiles(int H, int W, int wmw) { return (H / (8 * wmw)) * (W / 16); }   // cfg 2: 8 wmw x 16 pixels, 2 wmw rows each
+inline int f43_tiles(int H, int W) { return (H / 16) * (W / 16); }                   // cfg 3 / 7: 16 x 16 pixels, one row each
+inline int smallmap_tiles(int P, int tile) { return P / (16 * (tile >> 4)); }        // cfg 5: TM pixels (smallmap_tile), one row each
+inline int wino23s_tiles(int H, int W) { return (H / 8) * (W / 8); }                 // cfg 6: 8 x 8 pixels, one row each
+
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 __device__ __forceinline__ float silu_f(float x)

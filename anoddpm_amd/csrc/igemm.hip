@@ -586,7 +586,49 @@ void launch_splitk_tail(const anoddpm_igemm_args *a, int64_t Z, int64_t P, hipSt
     }
 }
 
+// The 3x3 shapes the direct kernels (cfg 0 / 1) refuse: the halo tile of direct_tiles must fit their LDS.
+int direct_shape_ok(int ks, int H, int W, int BM)
+{
+    if (ks == 1) return ANODDPM_OK;
+    ANODDPM_REQUIRE((W & (W - 1)) == 0 && W >= 2, "igemm: 3x3 path needs power-of-two width >= 2");
+    const anoddpm::direct_tiling t = anoddpm::direct_tiles(ks, H, W, BM);
+    ANODDPM_REQUIRE((t.TH + 2) * ((1 << t.log2TW) + 2) <= (BM == 128 ? 204 : 136), "igemm: halo tile exceeds LDS budget for this shape");
+    return ANODDPM_OK;
+}
+
 }  // namespace
+
+extern "C" int anoddpm_igemm_stats_rows(const anoddpm_igemm_args *a)
+{
+    ANODDPM_REQUIRE(a, "igemm_stats_rows: null pointer");
+    ANODDPM_REQUIRE(a->cfg >= 0 && a->cfg <= 7 && (a->ks == 1 || a->ks == 3), "igemm_stats_rows: cfg must be 0 .. 7 and ks 1 or 3");
+    ANODDPM_REQUIRE(a->H >= 1 && a->W >= 1 && a->c0 > 0 && a->c1 >= 0 && a->N >= 1 && a->B >= 1 && a->ksplit >= 1, "igemm_stats_rows: bad sizes");
+    if (a->cfg == 4) return 0;                                       // the streaming 1x1 kernel writes none
+    if (a->ksplit > 1) {                                             // the split-K reduction writes them: grid.x = stats_rows
+        ANODDPM_REQUIRE(a->stats_rows >= 1, "igemm_stats_rows: split-K statistics need stats_rows");
+        return a->stats_rows;
+    }
+    const int K = a->c0 + a->c1;
+    if (a->cfg == 5) {
+        const int tile = anoddpm::smallmap_tile(a->ks, a->H, a->W, K, a->c0, a->N, a->B);
+        ANODDPM_REQUIRE(tile != 0, "igemm_stats_rows: cfg 5 does not take this shape (anoddpm_smallmap_tile)");
+        return anoddpm::smallmap_tiles(a->H * a->W, tile);
+    }
+    if (a->cfg == 6) {
+        ANODDPM_REQUIRE(a->ks == 3 && anoddpm::wino23s_tile(a->H, a->W, K, a->c0, a->N, a->B, a->a_mode) != 0,
+                        "igemm_stats_rows: cfg 6 does not take this shape (anoddpm_wino23s_tile)");
+        return anoddpm::wino23s_tiles(a->H, a->W);
+    }
+    if (a->cfg == 2 || a->cfg == 3 || a->cfg == 7) {
+        ANODDPM_REQUIRE(a->ks == 3 && a->H % 16 == 0 && a->W % 16 == 0, "igemm_stats_rows: the Winograd kernels need ks 3 and H, W multiples of 16");
+        // cfg 2: 2 wmw rows in each of wino_tiles(H, W, wmw) tiles -- H * W / 64 in either workgroup shape (wmw 1 or 2)
+        return a->cfg == 2 ? 2 * anoddpm::wino_tiles(a->H, a->W, 1) : anoddpm::f43_tiles(a->H, a->W);
+    }
+    const int BM = a->cfg == 0 ? 128 : 64;
+    if (int rc = direct_shape_ok(a->ks, a->H, a->W, BM)) return rc;
+    const anoddpm::direct_tiling t = anoddpm::direct_tiles(a->ks, a->H, a->W, BM);
+    return 2 * t.tiles_x * t.tiles_y;
+}
 
 extern "C" int anoddpm_igemm(const anoddpm_igemm_args *a, void *stream)
 {
@@ -627,7 +669,7 @@ extern "C" int anoddpm_igemm(const anoddpm_igemm_args *a, void *stream)
                                        (!a->res || (a->res_ld % 4 == 0 && al16(a->res))) && (!a->bias || al16(a->bias)) &&
                                        (!a->temb || (a->temb_ld % 4 == 0 && al16(a->temb)))),
                     "igemm: split-K needs a workspace and 16-byte aligned epilogue operands");
-    int H = a->H, W = a->W, log2TW, TH;
+    const int H = a->H, W = a->W;
     ANODDPM_REQUIRE(H >= 1 && W >= 1, "igemm: bad image size");
     const int64_t P = (int64_t)H * W;
     if (a->cfg == 3) {
@@ -647,22 +689,11 @@ extern "C" int anoddpm_igemm(const anoddpm_igemm_args *a, void *stream)
         return anoddpm::check_launch("igemm(winograd split-K tail)");
     }
     anoddpm_igemm_args k = *a;
-    int tiles_x, tiles_y;
+    if (int rc = direct_shape_ok(a->ks, H, W, BM)) return rc;
+    const anoddpm::direct_tiling t = anoddpm::direct_tiles(a->ks, H, W, BM);
+    const int log2TW = t.log2TW, TH = t.TH, tiles_x = t.tiles_x, tiles_y = t.tiles_y;
     if (a->ks == 1) {                 // treat the image as one row of P pixels
-        k.H = 1; k.W = (int)P; H = 1; W = (int)P;
-        TH = 1;
-        log2TW = (BM == 128) ? 7 : 6;
-        tiles_x = (int)((P + BM - 1) / BM);
-        tiles_y = 1;
-    } else {
-        ANODDPM_REQUIRE((W & (W - 1)) == 0 && W >= 2, "igemm: 3x3 path needs power-of-two width >= 2");
-        const int TW = W < 32 ? W : 32;
-        log2TW = 0;
-        while ((1 << log2TW) < TW) ++log2TW;
-        TH = BM / TW;
-        tiles_x = W / TW;
-        tiles_y = (H + TH - 1) / TH;
-        ANODDPM_REQUIRE((TH + 2) * (TW + 2) <= (BM == 128 ? 204 : 136), "igemm: halo tile exceeds LDS budget for this shape");
+        k.H = 1; k.W = (int)P;
     }
     const int64_t Z = (int64_t)a->B * a->heads;
     dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)((a->N + BN - 1) / BN), (unsigned)(Z * a->ksplit));

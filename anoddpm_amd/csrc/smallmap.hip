@@ -322,7 +322,7 @@ int launch_smallmap(const anoddpm_igemm_args *a, hipStream_t s)
     if (stage < redb) stage = redb;
     const size_t lds = (size_t)2 * Kpad * sizeof(float) + stage;
     ANODDPM_REQUIRE(lds <= 160 * 1024, "smallmap: LDS budget exceeded");
-    dim3 grid((unsigned)(a->N / TN), (unsigned)((int64_t)a->B * P / TM));
+    dim3 grid((unsigned)(a->N / TN), (unsigned)((int64_t)a->B * smallmap_tiles(P, tile)));
 #define SM_LAUNCH(KS_, RT_, CT_, LW_)                                                                                     \
     do {                                                                                                                  \
         static bool attr_done[ANODDPM_MAX_DEV];                                                                           \

@@ -308,7 +308,7 @@ int launch_wino23s(const anoddpm_igemm_args *a, hipStream_t s)
     if (int rc = check_fold_args(a, K, "wino23s")) return rc;
     const size_t lds = (size_t)(2 * K + 2 * WS_VBUF + 2 * WS_PBUF) * sizeof(float);
     ANODDPM_REQUIRE(lds <= 160 * 1024, "wino23s: LDS budget exceeded");
-    dim3 grid((unsigned)(a->N / (16 * ct)), (unsigned)(a->B * (a->H / 8) * (a->W / 8)));
+    dim3 grid((unsigned)(a->N / (16 * ct)), (unsigned)(a->B * wino23s_tiles(a->H, a->W)));
     static bool attr_done2[ANODDPM_MAX_DEV], attr_done4[ANODDPM_MAX_DEV];
     if (int rc = allow_big_lds(reinterpret_cast<const void *>(&wino23s_kernel<2>), attr_done2, "igemm(wino23s)")) return rc;
     if (int rc = allow_big_lds(reinterpret_cast<const void *>(&wino23s_kernel<4>), attr_done4, "igemm(wino23s)")) return rc;

@@ -477,7 +477,7 @@ int launch_winograd(const anoddpm_igemm_args *a, hipStream_t s)
 #endif
     const int wnw = (wmw == 1 && dbg != 2 && !probe && a->N % 128 == 0) ? 4 : 2;
     const int wbn = 32 * wnw;
-    dim3 grid((unsigned)((a->H / (8 * wmw)) * (a->W / 16)), (unsigned)((a->N + wbn - 1) / wbn), (unsigned)(a->B * a->ksplit));
+    dim3 grid((unsigned)wino_tiles(a->H, a->W, wmw), (unsigned)((a->N + wbn - 1) / wbn), (unsigned)(a->B * a->ksplit));
     ANODDPM_REQUIRE(grid.y <= 65535 && (int64_t)a->B * a->ksplit <= 65535, "winograd: grid too large");
     ANODDPM_REQUIRE((int64_t)16 * K * a->N * 4 < ((int64_t)1 << 31), "winograd: transformed weights exceed 32-bit buffer offsets");
     ANODDPM_REQUIRE((int64_t)a->H * a->W * (a->a0_ld > a->a1_ld ? a->a0_ld : a->a1_ld) * 4 < ((int64_t)1 << 31),

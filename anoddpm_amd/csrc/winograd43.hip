@@ -454,7 +454,7 @@ int launch_winograd43(const anoddpm_igemm_args *a, hipStream_t s)
     ANODDPM_REQUIRE(!a->gnb_partial || (a->ksplit == 1 && anoddpm_f43_channel_sliced(a->H, a->W, a->N, a->B) == 1),
                     "winograd43: gnb_partial needs the channel-sliced 128-channel kernel (anoddpm_f43_channel_sliced) and ksplit 1");
     const int nblk = half ? 64 : 128;
-    dim3 grid((unsigned)((a->H / 16) * (a->W / 16)), (unsigned)(a->N / nblk), (unsigned)a->B);
+    dim3 grid((unsigned)f43_tiles(a->H, a->W), (unsigned)(a->N / nblk), (unsigned)a->B);
     ANODDPM_REQUIRE(a->B <= 65535, "winograd43: batch too large");
     const bool fast = (a->gn_scale || a->fold_gamma) && a->act;
     ANODDPM_REQUIRE(a->res_mode == 0 || (a->res_mode == 1 && a->res && a->ksplit == 1), "winograd43: res_mode 1 needs a residual and ksplit 1");

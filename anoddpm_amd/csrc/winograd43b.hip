@@ -328,7 +328,7 @@ int launch_winograd43b(const anoddpm_igemm_args *a, hipStream_t s)
     ANODDPM_REQUIRE(a->B <= 65535, "winograd43b: batch too large");
     static bool attr_done[ANODDPM_MAX_DEV];
     if (int rc = allow_big_lds(reinterpret_cast<const void *>(&wino43b_kernel), attr_done, "igemm(winograd43b)")) return rc;
-    dim3 grid((unsigned)((a->H / 16) * (a->W / 16)), (unsigned)(a->N / 128), (unsigned)a->B);
+    dim3 grid((unsigned)f43_tiles(a->H, a->W), (unsigned)(a->N / 128), (unsigned)a->B);
     hipLaunchKernelGGL(wino43b_kernel, grid, dim3(B4_NT), B4_LDS_BYTES, s, *a);
     return check_launch("igemm(winograd43b)");
 }

@@ -570,7 +570,7 @@ namespace anoddpm {
 // Called by launch_winograd43 for the 128-channel grid (arguments validated there).
 int launch_winograd43r(const anoddpm_igemm_args *a, hipStream_t s)
 {
-    dim3 grid((unsigned)((a->H / 16) * (a->W / 16)), (unsigned)(a->N / 128), (unsigned)(a->B * a->ksplit));
+    dim3 grid((unsigned)f43_tiles(a->H, a->W), (unsigned)(a->N / 128), (unsigned)(a->B * a->ksplit));
     const bool fast = (a->gn_scale || a->fold_gamma) && a->act;
     ANODDPM_REQUIRE(!(a->gn_scale || a->fold_gamma) || a->c0 + a->c1 <= R4_KMAX, "winograd43r: GroupNorm affine table holds %d input channels", R4_KMAX);
 #ifdef ANODDPM_ABLATE           // timing ablations (wrong results) and ring-depth variants: measurement builds only

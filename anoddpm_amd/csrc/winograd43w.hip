@@ -370,7 +370,7 @@ namespace anoddpm {
 // the one-wave-per-SIMD kernel; arguments validated there.  No split-K form.
 int launch_winograd43w(const anoddpm_igemm_args *a, hipStream_t s, int tsplit)
 {
-    dim3 grid((unsigned)((a->H / 16) * (a->W / 16)), (unsigned)(a->N / 128), (unsigned)a->B);
+    dim3 grid((unsigned)f43_tiles(a->H, a->W), (unsigned)(a->N / 128), (unsigned)a->B);
     const bool fast = (a->gn_scale || a->fold_gamma) && a->act;
     ANODDPM_REQUIRE(a->ksplit == 1, "winograd43w: no split-K form");
     ANODDPM_REQUIRE(!(a->gn_scale || a->fold_gamma) || a->c0 + a->c1 <= W4_KMAX, "winograd43w: GroupNorm affine table holds %d input channels", W4_KMAX);

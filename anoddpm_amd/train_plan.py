@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from ._lib import (ColsumFoldArgs, DropoutArgs, GnBwdArgs, HeadBwdArgs, LinearBwdArgs, LinearBwdBatchArgs, Op, PackArgs, SoftmaxBwdArgs,
                    StemBwdArgs, TransposeArgs, Wgrad1Args, WgradArgs, check, lib)
-from .unet import _Plan, _op_array, _pack_table, pack_floats, pack_kind
+from .unet import _Plan, _Srcs, _op_array, _pack_table, pack_floats, pack_kind
 
 __all__ = ["TrainPlan", "TrainPlanFunction", "eligible"]
 
@@ -206,9 +206,8 @@ class TrainPlan(_Plan):
     def wgrad3(self, srcs, Hs, H, gn, a_mode, dy, N, wkey, bkey, d_emb=None):
         """3x3 weight gradient (+ the column sums of dy: bias gradient and, optionally, the per-image embedding gradient)."""
         B = self.B
-        c0 = srcs[0][1]
-        c1 = srcs[1][1] if len(srcs) > 1 else 0
-        K = c0 + c1
+        a = _Srcs(srcs)
+        K, c0, c1 = a.K, a.c0, a.c1
         W = H
         tiles = -(-K // 64) * -(-N // 64)
         TW = next(t for t in (32, 16, 8, 4, 2) if W % t == 0)
@@ -225,8 +224,7 @@ class TrainPlan(_Plan):
                    and B <= 15 and H * W >= int(os.environ.get("ANODDPM_WGRAD43_MIN_PIXELS", 16 * 16))   # round 6: the 16x16 maps too (40.55 -> 40.32 ms per config-3 step, profiles/r6_knob_sweep_c3.txt; 32x32 was the limit before)
                    and os.environ.get("ANODDPM_NO_WGRAD43", "0") != "1")
         wa = WgradArgs()
-        wa.a0 = srcs[0][0].data_ptr()
-        wa.a1 = srcs[1][0].data_ptr() if c1 else None
+        wa.a0, wa.a1, wa.c0, wa.c1, wa.a0_ld, wa.a1_ld = a.p0, a.p1, c0, c1, a.ld0, a.ld1
         wa.gn_scale, wa.gn_shift = (gn[0].data_ptr(), gn[1].data_ptr()) if gn is not None else (None, None)
         wa.dy, wa.dw = dy.data_ptr(), self.dW(wkey)
         wa.algo = algo
@@ -236,9 +234,7 @@ class TrainPlan(_Plan):
         else:
             wa.ws_floats = nitems * 9 * K * N
         self.tws(wa, "ws", wa.ws_floats)
-        Ps = Hs * Hs
-        wa.a0_bs, wa.a1_bs, wa.dy_bs = Ps * c0, Ps * c1, H * W * N
-        wa.c0, wa.c1, wa.a0_ld, wa.a1_ld, wa.dy_ld = c0, c1, c0, (c1 if c1 else 4), N
+        (wa.a0_bs, wa.a1_bs), wa.dy_bs, wa.dy_ld = a.strides(Hs * Hs), H * W * N, N
         wa.H, wa.W, wa.N, wa.B = H, W, N, B
         wa.a_mode, wa.act, wa.gn_ld, wa.band, wa.accumulate = a_mode, (1 if gn is not None else 0), K, band, 1
         colsum = self.buf(B, ipb, N)
@@ -259,24 +255,21 @@ class TrainPlan(_Plan):
 
     def wgrad1(self, srcs, P, gn, act, dy, dy_ld, N, wkey, bkey):
         B = self.B
-        c0 = srcs[0][1]
-        c1 = srcs[1][1] if len(srcs) > 1 else 0
-        K = c0 + c1
+        a = _Srcs(srcs)
+        K = a.K
         tiles = -(-K // 128) * -(-N // 128)
         want_items = max(1, 512 // tiles)
         span = max(32, (B * P // want_items + 31) // 32 * 32)
         span = min(span, (P + 31) // 32 * 32)
         nitems = B * -(-P // span)
         st = Wgrad1Args()
-        st.a0 = srcs[0][0].data_ptr()
-        st.a1 = srcs[1][0].data_ptr() if c1 else None
+        st.a0, st.a1, st.c0, st.c1, st.a0_ld, st.a1_ld = a.p0, a.p1, a.c0, a.c1, a.ld0, a.ld1
         st.gn_scale = gn[0].data_ptr() if gn else None
         st.gn_shift = gn[1].data_ptr() if gn else None
         st.dy, st.dw, st.dbias = dy if isinstance(dy, int) else dy.data_ptr(), self.dW(wkey), self.dW(bkey)
         st.ws_floats = nitems * (K * N + N)
         self.tws(st, "ws", st.ws_floats)
-        st.a0_bs, st.a1_bs, st.dy_bs = P * c0, P * c1, P * dy_ld
-        st.c0, st.c1, st.a0_ld, st.a1_ld, st.dy_ld = c0, c1, c0, (c1 if c1 else 4), dy_ld
+        (st.a0_bs, st.a1_bs), st.dy_bs, st.dy_ld = a.strides(P), P * dy_ld, dy_ld
         st.P, st.N, st.B, st.act, st.gn_ld, st.span, st.accumulate = P, N, B, act, K, span, 1
         self.badd(_lib.OP_WGRAD1, st)
 
@@ -285,17 +278,15 @@ class TrainPlan(_Plan):
         fused = (partial buffer, rows per image) when the data-gradient launch that produced `da` already wrote the
         reduction pass's partial sums (dgrad3(..., gnb=...)): fold + elementwise launches only."""
         B = self.B
-        c0 = srcs[0][1]
-        c1 = srcs[1][1] if len(srcs) > 1 else 0
-        C = c0 + c1
+        x = _Srcs(srcs)
+        C, c0, c1 = x.K, x.c0, x.c1
         P = Hs * Hs
         nslab = max(1, min(int(os.environ.get("ANODDPM_GNBWD_SLABS", 256)), P // 16))     # >= 4 workgroups per CU on the large maps
         if fused is not None:
             assert a_mode == 0 and act == 1
             nslab = fused[1]
         ga = GnBwdArgs()
-        ga.x0 = srcs[0][0].data_ptr()
-        ga.x1 = srcs[1][0].data_ptr() if c1 else None
+        ga.x0, ga.x1, ga.c0, ga.c1, ga.x0_ld, ga.x1_ld = x.p0, x.p1, c0, c1, x.ld0, x.ld1
         ga.da = da.data_ptr()
         ga.gamma, ga.beta = self.W(prefix + ".weight"), self.W(prefix + ".bias")
         ga.mean, ga.rstd = gnp[2].data_ptr(), gnp[3].data_ptr()
@@ -306,15 +297,13 @@ class TrainPlan(_Plan):
             g1 = self.G(srcs[1][0])
             ga.dx1 = g1.data_ptr()
             acc |= self.gacc(srcs[1][0]) << 1
-        else:
-            ga.dx1 = None
         ga.dgamma, ga.dbeta = self.dW(prefix + ".weight"), self.dW(prefix + ".bias")
         part = fused[0] if fused is not None else self.buf(B * nslab * C * 2, dtype=torch.float64)
         coef = self.buf(B * C * 4)
         ga.partial, ga.coef = part.data_ptr(), coef.data_ptr()
         ga.partial_ready = 1 if fused is not None else 0
-        ga.x0_bs, ga.x1_bs, ga.da_bs, ga.dx0_bs, ga.dx1_bs = P * c0, P * c1, da_P * C, P * c0, P * c1
-        ga.c0, ga.c1, ga.x0_ld, ga.x1_ld, ga.da_ld, ga.dx0_ld, ga.dx1_ld = c0, c1, c0, (c1 if c1 else 4), C, c0, (c1 if c1 else 4)
+        (ga.x0_bs, ga.x1_bs), (ga.dx0_bs, ga.dx1_bs), ga.da_bs = x.strides(P), x.strides(P), da_P * C
+        ga.da_ld, ga.dx0_ld, ga.dx1_ld = C, x.ld0, x.ld1           # (the gradients have their sources' layout)
         ga.Hs, ga.Ws, ga.B, ga.groups, ga.nslab = Hs, Hs, B, 32, nslab
         ga.act, ga.a_mode, ga.acc_dx = act, a_mode, acc
         if dres is not None:
@@ -344,9 +333,9 @@ class TrainPlan(_Plan):
             for st, field in self._ws_patch:
                 setattr(st, field, tws.data_ptr())
 
-    def gn(self, srcs, P, prefix, into=None):
+    def gn(self, srcs, P, prefix, consumer=None):
         """GroupNorm statistics -> (scale, shift, mean, rstd), always as tensors (the backward reads mean / rstd) and never folded
-        into the consumer `into`; parameters are read in place."""
+        into the `consumer`; parameters are read in place."""
         self.gn_sums(srcs, P)
         gamma, beta = self.W(prefix + ".weight"), self.W(prefix + ".bias")
         return self.gn_tail_job(srcs, gamma, beta, want_mean=True) or self.gn_finalize(srcs, P, gamma, beta, want_mean=True)
@@ -426,20 +415,17 @@ class TrainPlan(_Plan):
             return da
         fused = None
         xs, gnp, gprefix = gnb
-        xc0 = xs[0][1]
+        x = _Srcs(xs)
+        xc0 = x.c0
         if (os.environ.get("ANODDPM_NO_GNB_FUSE", "0") != "1" and st.cfg == 3 and st.ksplit == 1 and xc0 % 16 == 0
-                and sum(x[1] for x in xs) == Kc and lib().anoddpm_f43_channel_sliced(Hout, Hout, Kc, B) == 1):
+                and x.K == Kc and lib().anoddpm_f43_channel_sliced(Hout, Hout, Kc, B) == 1):
             rows = (Hout // 16) * (Hout // 16)
             part = self.buf(B * rows * Kc * 2, dtype=torch.float64)
             st.gnb_partial = part.data_ptr()
-            st.gnb_x0 = xs[0][0].data_ptr()
-            st.gnb_x1 = xs[1][0].data_ptr() if len(xs) > 1 else None
+            st.gnb_x0, st.gnb_x1, st.gnb_c0, st.gnb_x0_ld, st.gnb_x1_ld, st.gnb_groups = x.p0, x.p1, xc0, x.ld0, x.ld1, 32
             st.gnb_gamma, st.gnb_beta = self.W(gprefix + ".weight"), self.W(gprefix + ".bias")
             st.gnb_mean, st.gnb_rstd = gnp[2].data_ptr(), gnp[3].data_ptr()
-            P = Hout * Hout
-            xc1 = xs[1][1] if len(xs) > 1 else 0
-            st.gnb_x0_bs, st.gnb_x1_bs = P * xc0, P * xc1
-            st.gnb_c0, st.gnb_x0_ld, st.gnb_x1_ld, st.gnb_groups = xc0, xc0, (xc1 if xc1 else 4), 32
+            st.gnb_x0_bs, st.gnb_x1_bs = x.strides(Hout * Hout)
             fused = (part, rows)
         return da, fused
 

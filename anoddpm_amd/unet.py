@@ -367,6 +367,49 @@ class _GnFold:
     of the one or two concatenated tensors + the affine parameters."""
 
 
+class _Stats:
+    """Where the per-channel GroupNorm sums of a tensor are (_Plan.stats_of): kind "rows" = `rows` fp32 partial rows per image,
+    [B][rows][C][2]; kind "sums" = one complete fp64 row per image, [B][C][2].  `tail`: the split-K launch whose tail wrote the
+    sums and can still take the consumer's GroupNorm (gn_tail_job), if any."""
+
+    def __init__(self, kind, buf, rows=1, tail=None):
+        self.kind, self.buf, self.rows, self.tail = kind, buf, rows, tail
+
+    def triple(self):
+        """(pointer, rows, fmt) as a finalize launch or a fold reads them: fmt 0 = `rows` fp32 rows per image, fmt 1 = one fp64 row."""
+        return (self.buf.data_ptr(), self.rows, 0) if self.kind == "rows" else (self.buf.data_ptr(), 1, 1)
+
+
+class _Srcs:
+    """The one- or two-source operand (a virtual concat) every launch struct describes the same way: entries (tensor | address,
+    channels[, leading dimension]) -> pointers, channel counts, leading dimensions (a missing second source has none: 4)."""
+
+    def __init__(self, srcs):
+        self.c0 = srcs[0][1]
+        self.c1 = srcs[1][1] if len(srcs) > 1 else 0
+        self.K = self.c0 + self.c1
+        self.p0 = srcs[0][0] if isinstance(srcs[0][0], int) else srcs[0][0].data_ptr()
+        self.p1 = srcs[1][0].data_ptr() if self.c1 else None
+        self.ld0 = srcs[0][2] if len(srcs[0]) > 2 else self.c0
+        self.ld1 = (srcs[1][2] if len(srcs[1]) > 2 else self.c1) if self.c1 else 4
+
+    def strides(self, P):                                        # batch strides at `P` pixels per image
+        return P * self.ld0, (P * self.ld1 if self.c1 else 0)
+
+
+class _ConvChoice:
+    """The kernel ONE anoddpm_igemm launch runs on, chosen once (_Plan.conv_choice) and read by the GroupNorm in front of it
+    (_Plan.gn) and by the launch (_Plan.igemm): cfg (after the bf16split3 promotion of 3 to 7), ksplit, and `fold` -- which
+    GroupNorm the launch can finish in its own prologue: "any" statistics (cfg 5 / 6), fp64 "sums" only (F(4x4,3x3)), or None."""
+
+    def __init__(self, cfg, ksplit, fold):
+        self.cfg, self.ksplit, self.fold = cfg, ksplit, fold
+
+    def takes(self, fmts):
+        """True when a GroupNorm over sources of the statistics formats `fmts` (0 rows, 1 fp64 sums) can be folded into the launch."""
+        return self.fold == "any" or (self.fold == "sums" and all(f == 1 for f in fmts))
+
+
 def _use_winograd():
     import os
     return os.environ.get("ANODDPM_NO_WINOGRAD", "0") != "1"
@@ -670,18 +713,13 @@ class _Plan:
         st.a, st.stats, st.a_bs = buf.data_ptr(), stats.data_ptr(), P * C
         st.C, st.a_ld, st.P, st.B, st.nslab = C, C, P, B, nslab
         self.add(_lib.OP_CHAN_STATS, st)
-        self.stats_of[buf.data_ptr()] = ("rows", stats, nslab)
+        self.stats_of[buf.data_ptr()] = _Stats("rows", stats, nslab)
 
     fuse_gn_tail = True          # split-K tails fold the consumer's GroupNorm in (anoddpm_igemm_args.tail_*); see gn()
 
-    def stats_triple(self, src):
-        """(pointer, rows, fmt) of the partial sums of tensor `src`: fmt 0 = `rows` fp32 rows per image, fmt 1 = one fp64 row."""
-        kind, buf, extra = self.stats_of[src.data_ptr()]
-        return (buf.data_ptr(), extra, 0) if kind == "rows" else (buf.data_ptr(), 1, 1)
-
     def stats_source(self, st, which, src, c):
         """Point the `which`-th statistics source of a GnFinalizeArgs at the partial sums of tensor `src`."""
-        ptr, rows, fmt = self.stats_triple(src)
+        ptr, rows, fmt = self.stats_of[src.data_ptr()].triple()
         setattr(st, f"stats{which}", ptr)
         setattr(st, f"rows{which}", rows)
         setattr(st, f"fmt{which}", fmt)
@@ -696,15 +734,15 @@ class _Plan:
         c1 = srcs[1][1] if len(srcs) > 1 else 0
         C = c0 + c1
         ent = self.stats_of.get(srcs[0][0].data_ptr())
-        if ent is None or ent[0] != "csum" or ent[2].tail_gamma or C % 32 or (C // 32) % 4 or C // 32 > 64:
+        if ent is None or ent.tail is None or ent.tail.tail_gamma or C % 32 or (C // 32) % 4 or C // 32 > 64:
             return None
         other = None
         if c1:
             e1 = self.stats_of.get(srcs[1][0].data_ptr())
-            if e1 is None or e1[0] not in ("csum", "asum"):         # both hold [B][c1][2] fp64 sums, complete before this launch
+            if e1 is None or e1.kind != "sums":                     # [B][c1][2] fp64 sums, complete before this launch
                 return None
-            other = e1[1]
-        st = ent[2]
+            other = e1.buf
+        st = ent.tail
         scale, shift = self.buf(B, C), self.buf(B, C)
         st.tail_gamma, st.tail_beta = gamma, beta
         st.tail_scale, st.tail_shift = scale.data_ptr(), shift.data_ptr()
@@ -732,8 +770,6 @@ class _Plan:
         self.stats_source(st, 0, srcs[0][0], c0)
         if c1:
             self.stats_source(st, 1, srcs[1][0], c1)
-        else:
-            st.stats1, st.rows1, st.fmt1 = None, 0, 0
         st.gamma, st.beta = gamma, beta
         out = (self.buf(B, c0 + c1), self.buf(B, c0 + c1))
         st.scale, st.shift = out[0].data_ptr(), out[1].data_ptr()
@@ -744,29 +780,21 @@ class _Plan:
         self.add(_lib.OP_GN_FINALIZE, st)
         return out
 
-    def gn(self, srcs, P, prefix, into=None):
+    def gn(self, srcs, P, prefix, consumer=None):
         """GroupNorm(32) affine `prefix`.weight / .bias of one or two concatenated sources from their per-channel partial sums
-        (emitted by the producing igemm's epilogue).  Returns (scale, shift) [B][Ctot] -- or, when its only consumer `into` =
-        (H, N, ks, a_mode) is a contraction that finishes the GroupNorm in its own prologue (cfg 5 / 6, or F(4x4,3x3) over fp64
+        (emitted by the producing igemm's epilogue).  Returns (scale, shift) [B][Ctot] -- or, when its only consumer is a
+        contraction whose _ConvChoice `consumer` finishes the GroupNorm in its own prologue (cfg 5 / 6, or F(4x4,3x3) over fp64
         sums), a _GnFold descriptor and NO launch."""
         self.gn_sums(srcs, P)
         gamma, beta = self.param(prefix + ".weight"), self.param(prefix + ".bias")
         job = self.gn_tail_job(srcs, gamma, beta)
         if job is not None:
             return job
-        c0 = srcs[0][1]
-        C = sum(s[1] for s in srcs)
-        fold = False
-        if into is not None:
-            H, N, ks, a_mode = into
-            fold = (self.small(H, H, C, N, ks=ks, a_mode=a_mode, c0=c0) or
-                    (ks == 3 and self.f43_fold(H, H, C, N, a_mode=a_mode, c0=c0, c1=C - c0)))
-        if fold == "f43" and not all(self.stats_of[s_[0].data_ptr()][0] in ("csum", "asum") for s_ in srcs):
-            fold = False                      # an F(4x4,3x3) consumer folds fp64 sums only: a rows source keeps the finalize launch
-        if fold and C % 32 == 0:
+        src = [self.stats_of[s[0].data_ptr()].triple() for s in srcs]
+        if consumer is not None and consumer.takes([fmt for _, _, fmt in src]) and sum(s[1] for s in srcs) % 32 == 0:
             d = _GnFold()
             d.gamma, d.beta, d.groups, d.eps = gamma, beta, 32, 1e-5
-            d.src = [self.stats_triple(s[0]) for s in srcs]
+            d.src = src
             return d
         return self.gn_finalize(srcs, P, gamma, beta)
 
@@ -777,20 +805,6 @@ class _Plan:
         v = self._csum_arena[self._csum_used:self._csum_used + n]
         self._csum_used += n
         return v
-
-    def f43_fold(self, H, W, K, N, *, a_mode=0, c0=None, c1=0):
-        """"f43" when a 3x3 contraction with these parameters will run on the F(4x4,3x3) kernels without split-K -- they finish a
-        GroupNorm whose sources are all fp64 sums in their prologue (gn) -- else False."""
-        if not self.csum_mode or self.arith != "fp32" or a_mode not in (0, 1) or os.environ.get("ANODDPM_CSUM_NOFOLD", "0") == "1":
-            return False
-        cfg, ksplit = choose_conv_cfg(H, W, K, N, self.B, ks=3, a_mode=a_mode, c0=(K if c0 is None else c0), c1=c1,
-                                      wino=True, f43=True, plain=False, small=True)
-        return "f43" if (cfg == 3 and ksplit == 1 and K <= F43_MAX_GN_K) else False
-
-    def small(self, H, W, K, N, *, ks, a_mode=0, c0=None):
-        """True when the contraction with these parameters will run on cfg 5 / 6 (so its GroupNorm can be folded into it)."""
-        return (smallmap_ok(H, W, K, N, self.B, ks=ks, a_mode=a_mode, c0=c0) or
-                wino23s_ok(H, W, K, N, self.B, ks=ks, a_mode=a_mode, c0=c0))
 
     def attention(self, qkv, att, L, heads, ch, probs=None):
         """One fused launch for softmax(q^T k / sqrt(ch)) v (csrc/attention.hip) when the shape allows it; False otherwise (the
@@ -809,36 +823,66 @@ class _Plan:
         self.igemm_flops += fl
         return True
 
-    def igemm(self, *, srcs, H, W, ks, N, bmat, out, out_ld=None, gn=None, act=0, a_mode=0, bias=None,
-              temb=None, temb_ld=0, res=None, res_ld=0, b_mode=0, ldb=0, heads=1, alpha=1.0,
-              a_strides=None, b_strides=(0, 0), o_strides=None, r_strides=None, kind="conv3", want_stats=False,
-              wino=None, wino43=None, res_up=None):
-        B = self.B
-        P = H * W
-        c0 = srcs[0][1]
-        c1 = srcs[1][1] if len(srcs) > 1 else 0
-        K = c0 + c1
+    def conv_choice(self, *, srcs, H, W, ks, N, a_mode=0, b_mode=0, heads=1, wino=False, f43=False, plain=False):
+        """The _ConvChoice of the anoddpm_igemm launch with these parameters: `wino` / `f43` = the Winograd-domain / F(4x4,3x3)
+        weight layouts exist, `plain` = the launch carries no GroupNorm, activation or statistics.  The ONE place a plan selects a
+        convolution kernel (choose_conv_cfg holds the policy)."""
+        a = _Srcs(srcs)
+        K, c0, c1, Z = a.K, a.c0, a.c1, self.B * heads
+        cfg, ksplit = choose_conv_cfg(H, W, K, N, Z, ks=ks, a_mode=a_mode, b_mode=b_mode, heads=heads, c0=c0, c1=c1,
+                                      wino=bool(wino), f43=bool(f43), plain=plain, small=True)
+        if (cfg == 3 and self.arith == "bf16split3" and ksplit == 1 and N % 128 == 0 and K % 32 == 0 and (c1 == 0 or c0 % 32 == 0)
+                and (H // 16) * (W // 16) * (N // 128) * Z >= 200):
+            cfg = 7                                             # the 128-channel grids (what winograd43r.hip runs) on split-bf16 products
+        # cfg 5 / 6 finish a GroupNorm over rows or sums; an F(4x4,3x3) launch fp64 sums only: a rows source keeps the finalize launch
+        sums = (cfg == 3 and ksplit == 1 and self.csum_mode and self.arith == "fp32" and a_mode in (0, 1) and K <= F43_MAX_GN_K
+                and os.environ.get("ANODDPM_CSUM_NOFOLD", "0") != "1")
+        return _ConvChoice(cfg, ksplit, "any" if cfg in (5, 6) else ("sums" if sums else None))
+
+    def igemm(self, *, srcs, H, W, ks, N, bmat, out, gn=None, act=0, a_mode=0, b_mode=0, heads=1, kind="conv3", want_stats=False,
+              wino=None, wino43=None, res_up=None, choice=None, **epilogue):
+        """One anoddpm_igemm launch in three steps: the operand / epilogue fields (igemm_operands), the kernel `choice` -- made here
+        for the callers that had no GroupNorm to place in front of it -- with what depends on it (igemm_kernel), and the route of
+        the output's GroupNorm sums (igemm_stats)."""
+        if choice is None:
+            choice = self.conv_choice(srcs=srcs, H=H, W=W, ks=ks, N=N, a_mode=a_mode, b_mode=b_mode, heads=heads, wino=wino, f43=wino43,
+                                      plain=(gn is None and act == 0 and not want_stats))
         st = IgemmArgs()
-        st.a0 = srcs[0][0] if isinstance(srcs[0][0], int) else srcs[0][0].data_ptr()
-        st.a1 = (srcs[1][0].data_ptr() if c1 else None)
-        a0_ld = srcs[0][2] if len(srcs[0]) > 2 else c0
-        a1_ld = (srcs[1][2] if len(srcs[1]) > 2 else c1) if c1 else 4
-        st.a0_ld, st.a1_ld = a0_ld, a1_ld
+        self.igemm_operands(st, srcs=srcs, H=H, W=W, ks=ks, N=N, out=out, gn=gn, act=act, a_mode=a_mode, b_mode=b_mode, heads=heads,
+                            choice=choice, **epilogue)
+        self.igemm_kernel(st, choice, bmat, wino, wino43, res_up)
+        fused = self.igemm_stats(st, choice, out) if want_stats else True
+        self.add(_lib.OP_IGEMM, st)
+        P, K, Z, cfg = H * W, st.c0 + st.c1, self.B * heads, choice.cfg
+        self.igemm_log.append(dict(wino=(cfg in (2, 3, 6, 7)), f43=(cfg in (3, 7)), kind=kind, H=H, W=W, K=K, N=N, ks=ks, a_mode=a_mode, b_mode=b_mode, heads=heads,
+                                   cfg=cfg, ksplit=choice.ksplit, dual=bool(st.c1), gflop=2.0 * K * N * ks * ks * P * Z / 1e9,
+                                   # the fused residual the epilogue reads: 0 none, 1 full resolution, 0.25 nearest-x2 source (res_mode 1)
+                                   res=(0.0 if not st.res else (0.25 if st.res_mode == 1 else 1.0))))
+        if not fused:
+            self.chan_stats(out, N, P)
+        self.igemm_flops += 2.0 * K * N * ks * ks * P * Z
+        return st
+
+    def igemm_operands(self, st, *, srcs, H, W, ks, N, out, gn, act, a_mode, b_mode, heads, choice, out_ld=None, bias=None, temb=None,
+                       temb_ld=0, res=None, res_ld=0, ldb=0, alpha=1.0, a_strides=None, b_strides=(0, 0), o_strides=None, r_strides=None):
+        """Step 1: operands, GroupNorm of the operand (from tensors, or folded), epilogue operands, shape (unset fields of a fresh struct are 0 / NULL)."""
+        P = H * W
+        a = _Srcs(srcs)
+        st.a0, st.a1, st.c0, st.c1, st.a0_ld, st.a1_ld = a.p0, a.p1, a.c0, a.c1, a.ld0, a.ld1
         if a_strides is None:
-            Pin = P if a_mode == 0 else (P // 4 if a_mode == 1 else P * 4)
-            st.a0_bs, st.a0_hs, st.a1_bs, st.a1_hs = Pin * a0_ld, 0, Pin * a1_ld if c1 else 0, 0
+            st.a0_bs, st.a1_bs = a.strides(P if a_mode == 0 else (P // 4 if a_mode == 1 else P * 4))
         else:
             st.a0_bs, st.a0_hs = a_strides
-            st.a1_bs = st.a1_hs = 0
         fold = gn if isinstance(gn, _GnFold) else None
         st.gn_scale = gn[0].data_ptr() if (gn and fold is None) else None
         st.gn_shift = gn[1].data_ptr() if (gn and fold is None) else None
-        st.gn_ld = K
-        st.fold_gamma = st.fold_beta = st.fold_stats0 = st.fold_stats1 = None
+        st.gn_ld = a.K
         if fold is not None:
+            if not choice.takes([fmt for _, _, fmt in fold.src]):
+                raise _lib.AnoddpmError("plan: a folded GroupNorm needs a cfg 5 / 6 consumer, or a cfg 3 one with fp64-sum sources")
             st.fold_gamma, st.fold_beta, st.fold_groups, st.fold_eps = fold.gamma, fold.beta, fold.groups, fold.eps
             st.fold_stats0, st.fold_rows0, st.fold_fmt0 = fold.src[0]
-            if c1:
+            if a.c1:
                 st.fold_stats1, st.fold_rows1, st.fold_fmt1 = fold.src[1]
         st.b_bs, st.b_hs = b_strides
         st.bias = (bias if isinstance(bias, int) else bias.data_ptr()) if bias is not None else None
@@ -848,30 +892,17 @@ class _Plan:
         out_ld = out_ld or N
         st.out = out if isinstance(out, int) else out.data_ptr()
         st.out_ld, st.res_ld = out_ld, (res_ld or N)
-        if o_strides is None:
-            st.o_bs, st.o_hs = P * out_ld, 0
-        else:
-            st.o_bs, st.o_hs = o_strides
-        if r_strides is None:
-            st.r_bs, st.r_hs = P * (res_ld or N), 0
-        else:
-            st.r_bs, st.r_hs = r_strides
-        st.c0, st.c1 = c0, c1
+        st.o_bs, st.o_hs = (P * out_ld, 0) if o_strides is None else o_strides
+        st.r_bs, st.r_hs = (P * (res_ld or N), 0) if r_strides is None else r_strides
         st.H, st.W, st.ks, st.a_mode, st.act = H, W, ks, a_mode, act
         st.b_mode, st.ldb, st.N = b_mode, ldb, N
-        st.B, st.heads, st.alpha = B, heads, alpha
-        Z = B * heads
-        cfg, ksplit = choose_conv_cfg(H, W, K, N, Z, ks=ks, a_mode=a_mode, b_mode=b_mode, heads=heads, c0=c0, c1=c1,
-                                      wino=bool(wino), f43=bool(wino43),
-                                      plain=(gn is None and act == 0 and not want_stats), small=True)
-        if fold is not None and not (cfg in (5, 6) or (cfg == 3 and ksplit == 1 and st.fold_fmt0 == 1 and (not c1 or st.fold_fmt1 == 1))):
-            raise _lib.AnoddpmError("plan: a folded GroupNorm needs a cfg 5 / 6 consumer, or a cfg 3 one with fp64-sum sources")
-        if (cfg == 3 and self.arith == "bf16split3" and ksplit == 1 and N % 128 == 0 and K % 32 == 0 and (c1 == 0 or c0 % 32 == 0)
-                and (H // 16) * (W // 16) * (N // 128) * Z >= 200):
-            cfg = 7                                             # the 128-channel grids (what winograd43r.hip runs) on split-bf16 products
-        bm = 128 if cfg == 0 else 64
-        st.cfg, st.ksplit = cfg, ksplit
-        st.res_mode = 0
+        st.B, st.heads, st.alpha = self.B, heads, alpha
+
+    def igemm_kernel(self, st, choice, bmat, wino, wino43, res_up):
+        """Step 2: what follows from the choice -- the weight layout (packed lazily: only the one the launch uses), the residual
+        of an up-sampling ResBlock, the split-K workspace."""
+        B, P, N = self.B, st.H * st.W, st.N
+        cfg, ksplit = st.cfg, st.ksplit = choice.cfg, choice.ksplit
         if res_up is not None:
             # residual = nearest x2 of the half-resolution tensor `res_up` (the x_upd path of an up-sampling ResBlock, UNet.py:196-198):
             # the F(4x4,3x3) kernels repeat the source pixels on the read (res_mode 1: no resample launch, a quarter of the residual
@@ -883,7 +914,7 @@ class _Plan:
                 sk = self.buf(B, P, N)
                 rs = ResampleArgs()
                 rs.inp, rs.out = res_up.data_ptr(), sk.data_ptr()
-                rs.B, rs.H, rs.W, rs.C, rs.mode = B, H // 2, W // 2, N, 1
+                rs.B, rs.H, rs.W, rs.C, rs.mode = B, st.H // 2, st.W // 2, N, 1
                 self.add(_lib.OP_RESAMPLE, rs)
                 st.res = sk.data_ptr()
         if cfg == 7:
@@ -893,65 +924,46 @@ class _Plan:
         elif cfg in (2, 6):
             bmat = wino()                                      # Winograd-domain weights for this layer
         elif callable(bmat):
-            bmat = bmat()                                      # packed lazily: only the layout this launch uses
+            bmat = bmat()
         st.bmat = bmat if isinstance(bmat, int) else bmat.data_ptr()
-        st.ws = None                      # patched after the build (one shared workspace)
-        if ksplit > 1:
-            self._ws_need = max(self._ws_need, ksplit * Z * P * N)
-        st.stats = None
-        if want_stats and cfg in (5, 6):
-            # one row per workgroup tile: TM pixels (cfg 5) / 8x8 pixels (cfg 6)
-            rows = P // 64 if cfg == 6 else P // (16 * (lib().anoddpm_smallmap_tile(ks, H, W, K, c0, N, B) >> 4))
-            stats = self.buf(B, rows, N, 2)
-            st.stats = stats.data_ptr()
-            self.stats_of[out.data_ptr()] = ("rows", stats, rows)
-        elif (want_stats and ksplit == 1 and heads == 1 and cfg == 3 and self.csum_mode
-              and 2 * N * (H // 16) * (W // 16) * B <= int(os.environ.get("ANODDPM_CSUM_MAX_ATOMICS", 100000))):
+        if ksplit > 1:                    # (st.ws: one shared workspace, patched in after the build)
+            self._ws_need = max(self._ws_need, ksplit * B * st.heads * P * N)
+
+    def igemm_stats(self, st, choice, out):
+        """Step 3: where the GroupNorm sums of the output come from; False when the launch cannot emit them (the caller adds a
+        chan_stats pass).  Row counts are the library's (anoddpm_igemm_stats_rows, beside the kernels that write the rows)."""
+        B, P, N = self.B, st.H * st.W, st.N
+        if st.heads != 1:
+            return False
+        if choice.ksplit > 1:
+            if (N % 128 == 0 and self.fuse_gn_tail and P <= int(os.environ.get("ANODDPM_GN_TAIL_MAX_P", 256))
+                    and os.environ.get("ANODDPM_NO_GN_TAIL", "0") != "1"):
+                # group-partitioned tail: folded per-channel sums now, the consumer's GroupNorm attached later by gn()
+                csum = self.buf(B, N, 2, dtype=torch.float64)
+                st.tail_csum, st.tail_groups, st.tail_c1, st.tail_eps = csum.data_ptr(), 32, 0, 1e-5
+                self.stats_of[out.data_ptr()] = _Stats("sums", csum, tail=st)
+                return True
+            # the split-K reduction emits the statistics: one row per pixel slab
+            rows_per_block = 256 // min(N // 4, 256)          # pixel rows a 256-thread block covers per pass
+            st.stats_rows = max(1, -(-P // (4 * rows_per_block)))     # <= 4 pixels per thread: the k-slab loads are serial
+        elif (choice.cfg == 3 and self.csum_mode
+              and 2 * N * (st.H // 16) * (st.W // 16) * B <= int(os.environ.get("ANODDPM_CSUM_MAX_ATOMICS", 100000))):
             # (measured, profiles/r6_csum_by_layer.txt: the chip retires about 33 of these atomics per ns, so a launch pays
             # 2 N tiles B / 33 ns for them -- 8-15 us on the 256x256 maps of a batch of four, more than the 4.7 us finalize launch
             # it replaces, 0.5-2 us on the 128x128 / 64x64 maps: only launches below the threshold accumulate atomically)
             # F(4x4,3x3): per-channel sums accumulated atomically into ONE fp64 row per image (no rows to fold)
             csum = self.csum_take(B * N * 2)
             st.stats_csum = csum.data_ptr()
-            self.stats_of[out.data_ptr()] = ("asum", csum, None)
-        elif want_stats and ksplit == 1 and heads == 1:
-            # the epilogue emits per-channel {sum, sumsq} per wave-row of every pixel tile
-            if cfg in (2, 3, 7):
-                tiles = (H // 16) * (W // 16)
-            elif ks == 1:
-                tiles = -(-P // bm)
-            else:
-                tw = min(W, 32)
-                tiles = (W // tw) * -(-H // (bm // tw))
-            rows = tiles * {2: 4, 3: 1, 7: 1}.get(cfg, 2)      # partial rows per pixel tile (F(4x4,3x3): one per workgroup)
-            stats = self.buf(B, rows, N, 2)
-            st.stats = stats.data_ptr()
-            self.stats_of[out.data_ptr()] = ("rows", stats, rows)
-        st.stats_rows = 0
-        st.tail_csum = None
-        if (want_stats and ksplit > 1 and heads == 1 and N % 128 == 0 and self.fuse_gn_tail
-                and P <= int(os.environ.get("ANODDPM_GN_TAIL_MAX_P", 256)) and os.environ.get("ANODDPM_NO_GN_TAIL", "0") != "1"):
-            # group-partitioned tail: folded per-channel sums now, the consumer's GroupNorm attached later by gn()
-            csum = self.buf(B, N, 2, dtype=torch.float64)
-            st.tail_csum, st.tail_groups, st.tail_c1, st.tail_eps = csum.data_ptr(), 32, 0, 1e-5
-            st.tail_gamma = st.tail_beta = st.tail_scale = st.tail_shift = st.tail_other = st.tail_mean = st.tail_rstd = None
-            self.stats_of[out.data_ptr()] = ("csum", csum, st)
-        elif want_stats and ksplit > 1 and heads == 1:
-            # the split-K reduction emits the statistics: one row per pixel slab
-            rows_per_block = 256 // min(N // 4, 256)          # pixel rows a 256-thread block covers per pass
-            nslab = max(1, -(-P // (4 * rows_per_block)))     # <= 4 pixels per thread: the k-slab loads are serial
-            stats = self.buf(B, nslab, N, 2)
-            st.stats, st.stats_rows = stats.data_ptr(), nslab
-            self.stats_of[out.data_ptr()] = ("rows", stats, nslab)
-        self.add(_lib.OP_IGEMM, st)
-        self.igemm_log.append(dict(wino=(cfg in (2, 3, 6, 7)), f43=(cfg in (3, 7)), kind=kind, H=H, W=W, K=K, N=N, ks=ks, a_mode=a_mode, b_mode=b_mode, heads=heads,
-                                   cfg=cfg, ksplit=ksplit, dual=bool(c1), gflop=2.0 * K * N * ks * ks * P * Z / 1e9,
-                                   # the fused residual the epilogue reads: 0 none, 1 full resolution, 0.25 nearest-x2 source (res_mode 1)
-                                   res=(0.0 if not st.res else (0.25 if st.res_mode == 1 else 1.0))))
-        if want_stats and st.stats is None and not st.tail_csum and not st.stats_csum:
-            self.chan_stats(out, N, P)
-        self.igemm_flops += 2.0 * K * N * ks * ks * P * Z
-        return st
+            self.stats_of[out.data_ptr()] = _Stats("sums", csum)
+            return True
+        rows = lib().anoddpm_igemm_stats_rows(ctypes.byref(st))
+        check(min(rows, 0), "plan: statistics rows of a convolution")
+        if rows == 0:
+            return False
+        stats = self.buf(B, rows, N, 2)
+        st.stats = stats.data_ptr()
+        self.stats_of[out.data_ptr()] = _Stats("rows", stats, rows)
+        return True
 
     # -- network ------------------------------------------------------------------------------
     # The forward, stated once for the inference plan and the training plan (train_plan.TrainPlan inherits it).  One method per
@@ -1049,7 +1061,7 @@ class _Plan:
             # GroupNorm partial sums of the stem output from the stem kernel itself (no chan_stats pass over it)
             sstats = self.buf(B, rows, cout, 2)
             self.stem.stats, self.stem.stats_rows = sstats.data_ptr(), rows
-            self.stats_of[h0.data_ptr()] = ("rows", sstats, rows)
+            self.stats_of[h0.data_ptr()] = _Stats("rows", sstats, rows)
         self.add(_lib.OP_STEM, self.stem)
         return SimpleNamespace(out=h0, C=cout, H=S, prefix=prefix, cin=cin)
 
@@ -1059,21 +1071,25 @@ class _Plan:
         Hout = Hin * 2 if resample == "up" else (Hin // 2 if resample == "down" else Hin)
         Pin, Pout = Hin * Hin, Hout * Hout
         am = {None: 0, "up": 1, "down": 2}[resample]
-        g1 = self.gn(srcs, Pin, prefix + ".in_layers.0", into=(None if resample == "down" else (Hout, cout, 3, am)))
-        emb_ptr, emb_ld = self.emb_of(prefix, cout)
-        h1 = self.buf(B, Pout, cout)
+        conv = dict(H=Hout, W=Hout, ks=3, N=cout)
         pooled = None
         if resample == "down" and self.pool_act():
             assert len(srcs) == 1                                # (the down path has no concatenated input)
             pooled, sk_pool = self.buf(B, Pout, cin), self.buf(B, Pout, cin)
+        op1 = dict(srcs=[(pooled, cin)]) if pooled is not None else dict(srcs=srcs, a_mode=am)
+        ch1 = self.conv_choice(**conv, **op1, wino=True, f43=True)
+        # (a pooled operand is normalised and activated by the pooling pass, from tensors: that GroupNorm has no launch to fold into)
+        g1 = self.gn(srcs, Pin, prefix + ".in_layers.0", consumer=(None if pooled is not None else ch1))
+        emb_ptr, emb_ld = self.emb_of(prefix, cout)
+        h1 = self.buf(B, Pout, cout)
+        if pooled is not None:
             st = self.resample(srcs[0][0], Hin, cin, 2, sk_pool)
             st.gn_scale, st.gn_shift, st.out_act = g1[0].data_ptr(), g1[1].data_ptr(), pooled.data_ptr()
-        self.igemm(srcs=([(pooled, cin)] if pooled is not None else srcs), H=Hout, W=Hout, ks=3, N=cout,
-                   gn=(None if pooled is not None else g1), act=(0 if pooled is not None else 1),
-                   a_mode=(0 if pooled is not None else am),
+        self.igemm(**conv, **op1, choice=ch1, gn=(None if pooled is not None else g1), act=(0 if pooled is not None else 1),
                    **self.conv_weights(prefix + ".in_layers.2.weight"), bias=self.param(prefix + ".in_layers.2.bias"),
                    temb=emb_ptr, temb_ld=emb_ld, out=h1, want_stats=True)
-        g2 = self.gn([(h1, cout)], Pout, prefix + ".out_layers.0", into=(Hout, cout, 3, 0))
+        ch2 = self.conv_choice(**conv, srcs=[(h1, cout)], wino=True, f43=True)
+        g2 = self.gn([(h1, cout)], Pout, prefix + ".out_layers.0", consumer=ch2)
         skip = "resample"
         if cin != cout:
             assert resample is None
@@ -1101,8 +1117,7 @@ class _Plan:
         h2 = self.buf(B, Pout, cout)
         # with dropout the dropped activation is materialised and the second convolution sees a plain operand
         a2 = self.dropout(h1, g2, Pout, cout) if self.p_drop > 0 else None
-        self.igemm(srcs=[(h1 if a2 is None else a2, cout)], H=Hout, W=Hout, ks=3, N=cout,
-                   gn=(g2 if a2 is None else None), act=(1 if a2 is None else 0),
+        self.igemm(**conv, srcs=[(h1 if a2 is None else a2, cout)], choice=ch2, gn=(g2 if a2 is None else None), act=(1 if a2 is None else 0),
                    **self.conv_weights(prefix + ".out_layers.3.weight"), bias=self.param(prefix + ".out_layers.3.bias"),
                    res=sk, res_up=(srcs[0][0] if (resample == "up" and sk is None) else None), out=h2, want_stats=True)
         return SimpleNamespace(out=h2, C=cout, H=Hout, prefix=prefix, srcs=srcs, Hin=Hin, cin=cin, a_mode=am, resample=resample,
@@ -1115,9 +1130,11 @@ class _Plan:
         ch = C // heads
         if ch % 4:
             raise NotImplementedError(f"attention head width {ch} must be a multiple of 4")
-        g = self.gn([(x, C)], L, prefix + ".norm", into=(Hc, 3 * C, 1, 0))
+        to_qkv = dict(srcs=[(x, C)], H=Hc, W=Hc, ks=1, N=3 * C)
+        choice = self.conv_choice(**to_qkv)
+        g = self.gn([(x, C)], L, prefix + ".norm", consumer=choice)
         qkv = self.buf(B, L, 3 * C)
-        self.igemm(srcs=[(x, C)], H=Hc, W=Hc, ks=1, N=3 * C, gn=g, act=0, kind="qkvproj",
+        self.igemm(**to_qkv, choice=choice, gn=g, act=0, kind="qkvproj",
                    bmat=self.weight(prefix + ".to_qkv.weight", "conv"), bias=self.param(prefix + ".to_qkv.bias"), out=qkv)
         att = self.buf(B, L, C)
         probs = self.buf(B * heads, L, L) if self.keep_probs else None
@@ -1156,21 +1173,26 @@ class _Plan:
         elif kind == "downsample":
             wkey = prefix + ".downsample.weight"
             full = self.buf(B, Hc * Hc, C)                          # the stride-1 result; the stride-2 output = its even pixels
-            self.igemm(srcs=[(x, C)], H=Hc, W=Hc, ks=3, N=C, act=0, **self.conv_weights(wkey),
+            conv_ = dict(srcs=[(x, C)], H=Hc, W=Hc, ks=3, N=C)
+            self.igemm(**conv_, choice=self.conv_choice(**conv_, wino=True, f43=True, plain=True), act=0, **self.conv_weights(wkey),
                        bias=self.param(prefix + ".downsample.bias"), out=full)
             self.resample(full, Hc, C, 3, out)
         else:
             wkey = prefix + ".conv.weight"
-            self.igemm(srcs=[(x, C)], H=Ho, W=Ho, ks=3, N=C, act=0, a_mode=1, **self.conv_weights(wkey),      # nearest x2 fused into the operand load
+            conv_ = dict(srcs=[(x, C)], H=Ho, W=Ho, ks=3, N=C, a_mode=1)                                      # nearest x2 fused into the operand load
+            self.igemm(**conv_, choice=self.conv_choice(**conv_, wino=True, f43=True), act=0, **self.conv_weights(wkey),
                        bias=self.param(prefix + ".conv.bias"), out=out, want_stats=True)
         return SimpleNamespace(out=out, C=C, H=Ho, prefix=prefix, kind=kind, conv=conv, x=x, Hin=Hc, full=full, wkey=wkey)
 
     def head_block(self, hfin, cfin):
         """Head: GN + SiLU + 3x3 conv to in_channels (UNet.py:384-388,405)."""
         B, S = self.B, self.S
-        g = self.gn([(hfin, cfin)], S * S, "out.0")
         nout = self.model.in_channels
-        if nout <= 4 and S % 8 == 0 and (100 * (cfin + 16) + 9 * cfin * nout) * 4 <= 64 * 1024:
+        conv = dict(srcs=[(hfin, cfin)], H=S, W=S, ks=3, N=nout)
+        dedicated = nout <= 4 and S % 8 == 0 and (100 * (cfin + 16) + 9 * cfin * nout) * 4 <= 64 * 1024
+        choice = None if dedicated else self.conv_choice(**conv)
+        g = self.gn([(hfin, cfin)], S * S, "out.0", consumer=choice)
+        if dedicated:
             # dedicated HBM-bound head kernel, writes the caller's NCHW layout directly (train_plan.eligible() admits only these shapes)
             self.y = self.buf(B, nout, S, S)
             st = HeadArgs()
@@ -1182,7 +1204,7 @@ class _Plan:
             self.add(_lib.OP_HEAD, st)
         else:
             y_nhwc = self.buf(B, S * S, nout)
-            self.igemm(srcs=[(hfin, cfin)], H=S, W=S, ks=3, N=nout, gn=g, act=1,
+            self.igemm(**conv, choice=choice, gn=g, act=1,
                        bmat=self.weight("out.2.weight", "conv"), bias=self.param("out.2.bias"), out=y_nhwc)
             if nout == 1:
                 self.y = y_nhwc.view(B, 1, S, S)

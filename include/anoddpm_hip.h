@@ -327,6 +327,11 @@ typedef struct {
 } anoddpm_igemm_args;
 
 int anoddpm_igemm(const anoddpm_igemm_args *a, void *stream);
+/* Statistics rows per image the launch `a` writes to `stats` ([B][rows][N][2]), from cfg, ksplit, H, W, ks, c0, c1, N, B and
+ * stats_rows -- the tile count its launcher takes its grid from, times the rows a tile writes: stats_rows for split-K, 0 for a
+ * configuration that writes none (cfg 4), a negative ANODDPM_E* code (anoddpm_last_error) for a shape the configuration refuses.
+ * The caller sizes the buffer with it; pointers of `a` are not read. */
+int anoddpm_igemm_stats_rows(const anoddpm_igemm_args *a);
 /* 1 when a cfg 3 launch of this shape (ksplit 1) runs on the channel-sliced 128-channel kernel (winograd43r.hip) -- the one that
  * takes gnb_partial -- 0 when the launcher picks 64-channel workgroups (grids that would leave CUs idle, N % 128 != 0) */
 int anoddpm_f43_channel_sliced(int32_t H, int32_t W, int32_t N, int32_t B);

@@ -162,12 +162,7 @@ def conv_igemm(srcs, w, bias=None, *, Hout, ks, gn=None, act=0, a_mode=0, temb=N
             csum_out.append(torch.zeros(B, N, 2, dtype=torch.float64, device=dev))
             csum_out = csum_out[-1]
         st.stats_csum = csum_out.data_ptr()
-    if cfg in (5, 6) and stats_out is not None:
-        tm = 64 if cfg == 6 else 16 * (lib().anoddpm_smallmap_tile(ks, Hout, Hout, c0 + c1, c0, N, B) >> 4)
-        stats = torch.full((B, P // tm, N, 2), float("nan"), device=dev)
-        st.stats = stats.data_ptr()
-        stats_out.append(stats)
-    elif gn_tail is not None:
+    if gn_tail is not None:
         # split-K tail with the consumer GroupNorm folded in: gn_tail = dict(gamma, beta[, other_csum], want_mean) -> filled with
         # csum / scale / shift / mean / rstd
         assert ksplit > 1
@@ -186,18 +181,12 @@ def conv_igemm(srcs, w, bias=None, *, Hout, ks, gn=None, act=0, a_mode=0, temb=N
                 gn_tail["mean"] = torch.full((B, 32), float("nan"), device=dev)
                 gn_tail["rstd"] = torch.full((B, 32), float("nan"), device=dev)
                 st.tail_mean, st.tail_rstd = gn_tail["mean"].data_ptr(), gn_tail["rstd"].data_ptr()
-    elif stats_out is not None and ksplit > 1:
-        nslab = 3 if P > 16 else 1
-        stats = torch.full((B, nslab, N, 2), float("nan"), device=dev)
-        st.stats, st.stats_rows = stats.data_ptr(), nslab
-        stats_out.append(stats)
     elif stats_out is not None:
-        bm = 128 if cfg == 0 else 64
-        if cfg in (2, 3, 7):
-            tiles = (Hout // 16) ** 2
-        else:
-            tiles = -(-P // bm) if ks == 1 else (Hout // min(Hout, 32)) * -(-Hout // (bm // min(Hout, 32)))
-        stats = torch.full((B, tiles * {2: 4, 3: 1, 7: 1}.get(cfg, 2), N, 2), float("nan"), device=dev)
+        # the library says how many rows the launch writes (split-K: the slabs asked for here; cfg 5 / 6 by their tile)
+        st.stats_rows = (3 if P > 16 else 1) if ksplit > 1 else 0
+        rows = lib().anoddpm_igemm_stats_rows(ctypes.byref(st))
+        check(min(rows, 0), "igemm_stats_rows")
+        stats = torch.full((B, rows, N, 2), float("nan"), device=dev)
         st.stats = stats.data_ptr()
         stats_out.append(stats)
     if gnb is not None:

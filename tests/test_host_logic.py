@@ -296,6 +296,107 @@ def test_host_side_shape_helpers_of_the_library():
     assert L.anoddpm_f43_channel_sliced(60, 64, 128, 4) == 0 and L.anoddpm_f43_channel_sliced(0, 64, 128, 4) == 0
 
 
+def test_igemm_stats_rows_is_what_the_kernels_write():
+    """anoddpm_igemm_stats_rows -- the library's statement, taken from the tile counts its launchers take their grids from, of the
+    statistics rows per image a launch writes (the plans and tests/hipops.py size the buffer with it) -- against the independent
+    statement forward_ledger.producer_rows (the row index of each kernel's epilogue), wherever the configuration takes the shape;
+    a shape it refuses is a negative return with the error text set."""
+    import ctypes
+    import forward_ledger as fl
+    from anoddpm_amd._lib import IgemmArgs, lib
+    L = lib()
+
+    def launch(cfg, ks, H, W, c0, c1, N, B, ksplit=1, stats_rows=0):
+        st = IgemmArgs()
+        st.cfg, st.ks, st.H, st.W, st.c0, st.c1, st.N, st.B, st.heads, st.ksplit, st.stats_rows = cfg, ks, H, W, c0, c1, N, B, 1, ksplit, stats_rows
+        return st
+
+    def taken(st):
+        K = st.c0 + st.c1
+        if st.cfg == 5:
+            return L.anoddpm_smallmap_tile(st.ks, st.H, st.W, K, st.c0, st.N, st.B) != 0
+        if st.cfg == 6:
+            return st.ks == 3 and L.anoddpm_wino23s_tile(st.H, st.W, K, st.c0, st.N, st.B, 0) != 0
+        if st.cfg in (2, 3, 7):
+            return st.ks == 3 and st.H % 16 == 0 and st.W % 16 == 0
+        return st.ks == 1 or (st.W & (st.W - 1)) == 0                      # cfg 0 / 1: a 3x3 tile is a power-of-two strip of rows
+
+    maps = [(h, h) for h in (4, 8, 16, 32, 64)]
+    checked = {}
+    for cfg in (0, 1, 2, 3, 5, 6, 7):
+        for ks in (1, 3):
+            for (H, W) in maps + ([(32, 16)] if cfg in (3, 7) else []) + ([(10, 10)] if ks == 1 else []):
+                for N in (32, 64, 96, 128, 256):
+                    for B in (1, 4):
+                        for (c0, c1) in ((64, 0),) + (((32, 32), (64, 192)) if cfg == 5 else ()):
+                            st = launch(cfg, ks, H, W, c0, c1, N, B)
+                            rows = L.anoddpm_igemm_stats_rows(ctypes.byref(st))
+                            if taken(st):
+                                assert rows == fl.producer_rows(st) > 0, (cfg, ks, H, W, c0, c1, N, B, rows)
+                                checked[cfg, ks] = checked.get((cfg, ks), 0) + 1
+                            else:
+                                assert rows < 0 and L.anoddpm_last_error(), (cfg, ks, H, W, c0, c1, N, B, rows)
+    # every configuration was compared on shapes it takes (the Winograd family: 3x3 only; cfg 5 on both kernel sizes)
+    assert sorted(checked) == [(0, 1), (0, 3), (1, 1), (1, 3), (2, 3), (3, 3), (5, 1), (5, 3), (6, 3), (7, 3)], sorted(checked)
+    # a wrong count is an out-of-bounds device write: a few values by hand (csrc/igemm.hip, winograd.hip, winograd43*.hip, wino23s.hip)
+    rows = lambda *a, **k: L.anoddpm_igemm_stats_rows(ctypes.byref(launch(*a, **k)))
+    assert rows(0, 3, 64, 64, 64, 0, 128, 4) == 2 * 2 * 16 and rows(1, 1, 10, 10, 64, 0, 64, 1) == 2 * 2       # 32 x 4 pixel tiles; 100 pixels in 64s
+    assert rows(2, 3, 32, 32, 64, 0, 128, 4) == 16 and rows(3, 3, 32, 16, 64, 0, 128, 4) == 2 and rows(6, 3, 16, 16, 64, 0, 256, 4) == 4
+    # split-K: the reduction writes the rows the caller asked for; the streaming 1x1 kernel writes none
+    for cfg in (0, 1, 2, 3):
+        assert rows(cfg, 3, 16, 16, 64, 0, 128, 4, ksplit=4, stats_rows=3) == 3
+    assert rows(1, 3, 16, 16, 64, 0, 128, 4, ksplit=4, stats_rows=0) < 0
+    assert rows(4, 1, 64, 64, 128, 0, 128, 4) == 0
+
+
+_PLAN_MODELS = {"i32_b32_h2_a16_8": dict(img_size=32, base_channels=32, n_heads=2, attention_resolutions="16,8"),
+                "c2_256_b128": dict(img_size=256, base_channels=128, n_heads=2, attention_resolutions="16,8")}
+
+
+@pytest.mark.parametrize("name,B,folds", [("i32_b32_h2_a16_8", 2, None), ("c2_256_b128", 1, None), ("c2_256_b128", 4, (31, 55))])
+def test_plans_size_statistics_buffers_and_place_folds_consistently(monkeypatch, name, B, folds):
+    """The inference and the training plan, built over host buffers (default and ANODDPM_CSUM=1): every contraction that writes
+    statistics rows owns a buffer of exactly B x producer_rows x N x 2 floats (forward_ledger.producer_rows: the independent
+    statement of what the kernels write); a launch that finishes a GroupNorm in its prologue runs on a configuration, and reads
+    statistics formats, that can (cfg 5 / 6, or cfg 3 without split-K over fp64 sums); and a folded GroupNorm has no finalize
+    launch.  `folds`: the launches of the product configuration that carry a fold (of its 126 contractions), default / CSUM."""
+    import forward_ledger as fl
+    from anoddpm_amd import _lib, train_plan
+    from anoddpm_amd.unet import UNetModel, _Plan
+    torch.manual_seed(0)
+    kw = _PLAN_MODELS[name]
+    model = UNetModel(**kw)
+    dev = torch.device("cpu")
+
+    def audit(plan, ops):
+        numel = {t.data_ptr(): t.numel() for t in plan.keep if isinstance(t, torch.Tensor) and t.dtype == torch.float32}
+        igemms = [st for code, st in ops if code == _lib.OP_IGEMM]
+        folded = set()
+        for st in igemms:
+            if st.stats:
+                assert numel[st.stats] == B * fl.producer_rows(st) * st.N * 2, (st.cfg, st.ksplit, st.H, st.W, st.ks, st.N)
+            if st.fold_gamma:
+                assert st.cfg in (5, 6) or (st.cfg == 3 and st.ksplit == 1 and st.fold_fmt0 == 1 and (st.c1 == 0 or st.fold_fmt1 == 1)), \
+                    (st.cfg, st.ksplit, st.fold_fmt0, st.fold_fmt1)
+                assert st.fold_stats0 and (st.c1 == 0 or st.fold_stats1) and not st.gn_scale
+                folded.add(st.fold_gamma)
+        finalized = {st.gamma for code, st in ops if code == _lib.OP_GN_FINALIZE}
+        assert not (folded & finalized)
+        return len(igemms), sum(1 for st in igemms if st.fold_gamma), sum(1 for st in igemms if st.stats)
+
+    for csum in ("0", "1"):
+        monkeypatch.setenv("ANODDPM_CSUM", csum)
+        plan = _Plan(model, B, kw["img_size"], dev)
+        n, nfold, nstats = audit(plan, plan.ops)
+        assert nfold > 0 and nstats > 0
+        if folds is not None:
+            assert (n, nfold) == (126, folds[int(csum)])
+    monkeypatch.setenv("ANODDPM_CSUM", "0")
+    tp = train_plan.TrainPlan(model, B, kw["img_size"], dev)
+    n, nfold, nstats = audit(tp, tp.ops + tp.bops)
+    assert nfold == 0 and nstats > 0                          # the training plan never folds: its backward reads mean / rstd as tensors
+
+
 def test_reverse_chain_reuse_keys():
     """Which reverse chains may be restarted on their buffers (ReverseChain.reset): keyed by the noise source the captured
     graph contains -- 'gauss' / 'random' / a gaussian default noise_fn share one key, every simplex parameter set has its own,

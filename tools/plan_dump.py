@@ -31,8 +31,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SWITCHES = ["ANODDPM_CSUM=1", "ANODDPM_CSUM=1 ANODDPM_CSUM_NOFOLD=1", "ANODDPM_ARITH=bf16split3", "ANODDPM_NO_POOL_ACT=1",
             "ANODDPM_NO_RES_UP=1", "ANODDPM_NO_STEM_STATS=1", "ANODDPM_NO_FUSED_ATTENTION=1", "ANODDPM_NO_GN_TAIL=1",
             "ANODDPM_NO_GNB_FUSE=1", "ANODDPM_PACK_BATCH=0", "ANODDPM_BATCH_EMB_FWD=0", "ANODDPM_BATCH_EMB_BWD=0",
-            "ANODDPM_NO_WINOGRAD=1"]
-SWITCH_MODELS = [("c2_256_b128", 4), ("i32_b32_h2_a16_8", 2)]
+            "ANODDPM_NO_WINOGRAD=1",
+            # the kernel-selection switches (unet.choose_conv_cfg / smallmap_ok / wino23s_ok and the statistics routes of _Plan.igemm)
+            "ANODDPM_NO_SMALLMAP=1", "ANODDPM_NO_WINO23S=1", "ANODDPM_WINO23S_MAXK=128", "ANODDPM_SMALLMAP_CONV_MAXM=64",
+            "ANODDPM_NO_F43=1", "ANODDPM_F43_32=0", "ANODDPM_F43_DEEP_SPLITK=0", "ANODDPM_F43_MIN_PIXELS=1024",
+            "ANODDPM_NO_STREAM1X1=1", "ANODDPM_NO_WINOGRAD_SPLITK=1", "ANODDPM_SPLITK_TARGET=256", "ANODDPM_GN_TAIL_MAX_P=64",
+            "ANODDPM_CSUM=1 ANODDPM_CSUM_MAX_ATOMICS=0", "ANODDPM_CSUM=1 ANODDPM_ARITH=bf16split3"]
+# (batch 1 of c2_256_b128: the configuration whose 16x16 maps move between cfg 5 and the Winograd kernels)
+SWITCH_MODELS = [("c2_256_b128", 4), ("c2_256_b128", 1), ("i32_b32_h2_a16_8", 2)]
 FROZEN_PREFIX = "down."          # the frozen-subset cells freeze every parameter of the down path
 IGEMM_HEAD_MODEL = ("i32_b32_c5", dict(img_size=32, base_channels=32, in_channels=5))     # inference only: train_plan.eligible() refuses it
 
