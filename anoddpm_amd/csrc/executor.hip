@@ -31,34 +31,40 @@ struct ProfState {
 };
 static ProfState g_prof;
 
+// Every op anoddpm_run_ops executes, named once: ANODDPM_OP_<code>, the struct its `args` points to, the entry point that takes it.
+#define ANODDPM_OPS(X) \
+    X(IGEMM,            anoddpm_igemm_args,            anoddpm_igemm) \
+    X(GN_STATS,         anoddpm_gn_args,               anoddpm_gn_stats) \
+    X(SOFTMAX,          anoddpm_softmax_args,          anoddpm_softmax_rows) \
+    X(RESAMPLE,         anoddpm_resample_args,         anoddpm_resample2x) \
+    X(LINEAR,           anoddpm_linear_args,           anoddpm_linear_small) \
+    X(POSEMB,           anoddpm_posemb_args,           anoddpm_posemb) \
+    X(STEM,             anoddpm_stem_args,             anoddpm_conv_stem) \
+    X(LAYOUT,           anoddpm_layout_args,           anoddpm_nhwc_to_nchw) \
+    X(CHAN_STATS,       anoddpm_chan_stats_args,       anoddpm_chan_stats) \
+    X(HEAD,             anoddpm_head_args,             anoddpm_conv_head) \
+    X(GN_FINALIZE,      anoddpm_gn_finalize_args,      anoddpm_gn_finalize) \
+    X(WGRAD3,           anoddpm_wgrad_args,            anoddpm_conv3x3_wgrad) \
+    X(WGRAD1,           anoddpm_wgrad1_args,           anoddpm_wgrad_pointwise) \
+    X(GN_BWD,           anoddpm_gn_bwd_args,           anoddpm_gn_silu_backward) \
+    X(PACK,             anoddpm_pack_args,             anoddpm_pack_weights) \
+    X(SOFTMAX_BWD,      anoddpm_softmax_bwd_args,      anoddpm_softmax_rows_backward) \
+    X(TRANSPOSE,        anoddpm_transpose_args,        anoddpm_transpose_square) \
+    X(LINEAR_BWD,       anoddpm_linear_bwd_args,       anoddpm_linear_small_backward) \
+    X(STEM_BWD,         anoddpm_stem_bwd_args,         anoddpm_conv_stem_backward) \
+    X(HEAD_BWD,         anoddpm_head_bwd_args,         anoddpm_conv_head_backward) \
+    X(COLSUM_FOLD,      anoddpm_colsum_fold_args,      anoddpm_colsum_fold) \
+    X(ATTENTION,        anoddpm_attention_args,        anoddpm_attention) \
+    X(PACK_BATCH,       anoddpm_pack_batch_args,       anoddpm_pack_batch) \
+    X(DROPOUT,          anoddpm_dropout_args,          anoddpm_dropout) \
+    X(LINEAR_BWD_BATCH, anoddpm_linear_bwd_batch_args, anoddpm_linear_small_backward_batch)
+
 static int dispatch(const anoddpm_op &op, void *stream)
 {
     switch (op.code) {
-        case ANODDPM_OP_IGEMM: return anoddpm_igemm(static_cast<const anoddpm_igemm_args *>(op.args), stream);
-        case ANODDPM_OP_GN_STATS: return anoddpm_gn_stats(static_cast<const anoddpm_gn_args *>(op.args), stream);
-        case ANODDPM_OP_SOFTMAX: return anoddpm_softmax_rows(static_cast<const anoddpm_softmax_args *>(op.args), stream);
-        case ANODDPM_OP_RESAMPLE: return anoddpm_resample2x(static_cast<const anoddpm_resample_args *>(op.args), stream);
-        case ANODDPM_OP_LINEAR: return anoddpm_linear_small(static_cast<const anoddpm_linear_args *>(op.args), stream);
-        case ANODDPM_OP_POSEMB: return anoddpm_posemb(static_cast<const anoddpm_posemb_args *>(op.args), stream);
-        case ANODDPM_OP_STEM: return anoddpm_conv_stem(static_cast<const anoddpm_stem_args *>(op.args), stream);
-        case ANODDPM_OP_LAYOUT: return anoddpm_nhwc_to_nchw(static_cast<const anoddpm_layout_args *>(op.args), stream);
-        case ANODDPM_OP_CHAN_STATS: return anoddpm_chan_stats(static_cast<const anoddpm_chan_stats_args *>(op.args), stream);
-        case ANODDPM_OP_HEAD: return anoddpm_conv_head(static_cast<const anoddpm_head_args *>(op.args), stream);
-        case ANODDPM_OP_GN_FINALIZE: return anoddpm_gn_finalize(static_cast<const anoddpm_gn_finalize_args *>(op.args), stream);
-        case ANODDPM_OP_WGRAD3: return anoddpm_conv3x3_wgrad(static_cast<const anoddpm_wgrad_args *>(op.args), stream);
-        case ANODDPM_OP_WGRAD1: return anoddpm_wgrad_pointwise(static_cast<const anoddpm_wgrad1_args *>(op.args), stream);
-        case ANODDPM_OP_GN_BWD: return anoddpm_gn_silu_backward(static_cast<const anoddpm_gn_bwd_args *>(op.args), stream);
-        case ANODDPM_OP_PACK: return anoddpm_pack_weights(static_cast<const anoddpm_pack_args *>(op.args), stream);
-        case ANODDPM_OP_SOFTMAX_BWD: return anoddpm_softmax_rows_backward(static_cast<const anoddpm_softmax_bwd_args *>(op.args), stream);
-        case ANODDPM_OP_TRANSPOSE: return anoddpm_transpose_square(static_cast<const anoddpm_transpose_args *>(op.args), stream);
-        case ANODDPM_OP_LINEAR_BWD: return anoddpm_linear_small_backward(static_cast<const anoddpm_linear_bwd_args *>(op.args), stream);
-        case ANODDPM_OP_STEM_BWD: return anoddpm_conv_stem_backward(static_cast<const anoddpm_stem_bwd_args *>(op.args), stream);
-        case ANODDPM_OP_HEAD_BWD: return anoddpm_conv_head_backward(static_cast<const anoddpm_head_bwd_args *>(op.args), stream);
-        case ANODDPM_OP_COLSUM_FOLD: return anoddpm_colsum_fold(static_cast<const anoddpm_colsum_fold_args *>(op.args), stream);
-        case ANODDPM_OP_ATTENTION: return anoddpm_attention(static_cast<const anoddpm_attention_args *>(op.args), stream);
-        case ANODDPM_OP_PACK_BATCH: return anoddpm_pack_batch(static_cast<const anoddpm_pack_batch_args *>(op.args), stream);
-        case ANODDPM_OP_DROPOUT: return anoddpm_dropout(static_cast<const anoddpm_dropout_args *>(op.args), stream);
-        case ANODDPM_OP_LINEAR_BWD_BATCH: return anoddpm_linear_small_backward_batch(static_cast<const anoddpm_linear_bwd_batch_args *>(op.args), stream);
+#define X(code, args_t, fn) case ANODDPM_OP_##code: return fn(static_cast<const args_t *>(op.args), stream);
+        ANODDPM_OPS(X)
+#undef X
         default: set_error("run_ops: unknown op code %d", op.code); return ANODDPM_EINVAL;
     }
 }
@@ -93,7 +99,7 @@ extern "C" int anoddpm_ablate_build(void)
 #endif
 }
 
-extern "C" int anoddpm_abi_version(void) { return 31; }
+extern "C" int anoddpm_abi_version(void) { return ANODDPM_ABI_VERSION; }
 
 extern "C" const char *anoddpm_last_error(void) { return g_err; }
 
@@ -192,53 +198,27 @@ extern "C" int anoddpm_prof_list(int32_t *codes, float *ms, int32_t cap)
     return n;
 }
 
-// sizeof() of every ABI struct, so that the Python ctypes mirror can verify its layout at load time.
-extern "C" int anoddpm_struct_size(int32_t which)
+// sizeof() of every struct of the ABI by its name, so that the Python binding can verify the layouts it derives from the header at
+// load time.  Each struct is named once; the order does not matter.
+#define ANODDPM_STRUCTS(X) \
+    X(anoddpm_simplex_args) X(anoddpm_p_update_args) X(anoddpm_igemm_args) X(anoddpm_gn_args) X(anoddpm_softmax_args) \
+    X(anoddpm_resample_args) X(anoddpm_linear_args) X(anoddpm_posemb_args) X(anoddpm_stem_args) X(anoddpm_layout_args) \
+    X(anoddpm_op) X(anoddpm_adamw_args) X(anoddpm_chan_stats_args) X(anoddpm_gn_finalize_args) X(anoddpm_head_args) \
+    X(anoddpm_anomaly_args) X(anoddpm_vlb_args) X(anoddpm_wgrad_args) X(anoddpm_gn_bwd_args) X(anoddpm_wgrad1_args) \
+    X(anoddpm_pack_args) X(anoddpm_softmax_bwd_args) X(anoddpm_transpose_args) X(anoddpm_linear_bwd_args) \
+    X(anoddpm_stem_bwd_args) X(anoddpm_head_bwd_args) X(anoddpm_colsum_fold_args) X(anoddpm_mri_slice_args) \
+    X(anoddpm_resize_args) X(anoddpm_attention_args) X(anoddpm_pack_batch_args) X(anoddpm_linear_bwd_batch_args) \
+    X(anoddpm_loss_args) X(anoddpm_dropout_args) X(anoddpm_roc_args) X(anoddpm_ssim_args) X(anoddpm_component_areas_args) \
+    X(anoddpm_pro_args) X(anoddpm_distance_args) X(anoddpm_surface_args) X(anoddpm_median_args) X(anoddpm_erode_args) \
+    X(anoddpm_components_args)
+
+extern "C" int anoddpm_struct_size(const char *name)
 {
-    switch (which) {
-        case 0: return (int)sizeof(anoddpm_simplex_args);
-        case 1: return (int)sizeof(anoddpm_p_update_args);
-        case 2: return (int)sizeof(anoddpm_igemm_args);
-        case 3: return (int)sizeof(anoddpm_gn_args);
-        case 4: return (int)sizeof(anoddpm_softmax_args);
-        case 5: return (int)sizeof(anoddpm_resample_args);
-        case 6: return (int)sizeof(anoddpm_linear_args);
-        case 7: return (int)sizeof(anoddpm_posemb_args);
-        case 8: return (int)sizeof(anoddpm_stem_args);
-        case 9: return (int)sizeof(anoddpm_layout_args);
-        case 10: return (int)sizeof(anoddpm_op);
-        case 11: return (int)sizeof(anoddpm_adamw_args);
-        case 12: return (int)sizeof(anoddpm_chan_stats_args);
-        case 13: return (int)sizeof(anoddpm_gn_finalize_args);
-        case 14: return (int)sizeof(anoddpm_head_args);
-        case 15: return (int)sizeof(anoddpm_anomaly_args);
-        case 16: return (int)sizeof(anoddpm_vlb_args);
-        case 17: return (int)sizeof(anoddpm_wgrad_args);
-        case 18: return (int)sizeof(anoddpm_gn_bwd_args);
-        case 19: return (int)sizeof(anoddpm_wgrad1_args);
-        case 20: return (int)sizeof(anoddpm_pack_args);
-        case 21: return (int)sizeof(anoddpm_softmax_bwd_args);
-        case 22: return (int)sizeof(anoddpm_transpose_args);
-        case 23: return (int)sizeof(anoddpm_linear_bwd_args);
-        case 24: return (int)sizeof(anoddpm_stem_bwd_args);
-        case 25: return (int)sizeof(anoddpm_head_bwd_args);
-        case 26: return (int)sizeof(anoddpm_colsum_fold_args);
-        case 27: return (int)sizeof(anoddpm_mri_slice_args);
-        case 28: return (int)sizeof(anoddpm_resize_args);
-        case 29: return (int)sizeof(anoddpm_attention_args);
-        case 30: return (int)sizeof(anoddpm_pack_batch_args);
-        case 31: return (int)sizeof(anoddpm_linear_bwd_batch_args);
-        case 32: return (int)sizeof(anoddpm_loss_args);
-        case 33: return (int)sizeof(anoddpm_dropout_args);
-        case 34: return (int)sizeof(anoddpm_roc_args);
-        case 35: return (int)sizeof(anoddpm_ssim_args);
-        case 36: return (int)sizeof(anoddpm_component_areas_args);
-        case 37: return (int)sizeof(anoddpm_pro_args);
-        case 38: return (int)sizeof(anoddpm_distance_args);
-        case 39: return (int)sizeof(anoddpm_surface_args);
-        case 40: return (int)sizeof(anoddpm_median_args);
-        case 41: return (int)sizeof(anoddpm_erode_args);
-        case 42: return (int)sizeof(anoddpm_components_args);
-        default: return -1;
-    }
+    // Until ABI 31 the argument was an index (0 ... 42).  A caller written for that form hands one over as the pointer: no string
+    // lives in the first page, so such a value (NULL included) is answered with -1 like any unknown name, not dereferenced.
+    if (reinterpret_cast<uintptr_t>(name) < 4096) return -1;
+#define X(s) if (strcmp(name, #s) == 0) return (int)sizeof(s);
+    ANODDPM_STRUCTS(X)
+#undef X
+    return -1;
 }

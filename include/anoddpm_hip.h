@@ -28,10 +28,17 @@ extern "C" {
 #define ANODDPM_ELAUNCH (-2)  /* HIP reported a launch / runtime error          */
 #define ANODDPM_ENODEV (-3)   /* no HIP device visible                          */
 
-int anoddpm_abi_version(void);          /* bumps whenever a struct below changes */
+/* The version of this file, stated here only: the library returns it and the Python binding, which derives its ctypes structs,
+ * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
+ * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
+ * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
+#define ANODDPM_ABI_VERSION 32
+
+int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
 int anoddpm_device_count(void);
-int anoddpm_struct_size(int32_t which); /* sizeof of the n-th *_args struct, in declaration order */
+int anoddpm_struct_size(const char *name);   /* sizeof of the struct typedef'd as `name` ("anoddpm_igemm_args"); -1 for any other name,
+                                                 for NULL, and for the small index this function took until version 31 */
 
 /* ------------------------------------------------------------------ simplex ------------ */
 

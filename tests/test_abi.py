@@ -29,10 +29,67 @@ def test_library_exports_every_declared_symbol():
 
 def test_abi_version_and_struct_sizes():
     L = _lib.lib()
-    assert L.anoddpm_abi_version() == _lib.ABI_VERSION
-    for i, st in enumerate(_lib._STRUCTS):
-        assert L.anoddpm_struct_size(i) == ctypes.sizeof(st), st.__name__
-    assert L.anoddpm_struct_size(99) == -1
+    assert L.anoddpm_abi_version() == _lib.ABI_VERSION == _lib._CONSTS["ANODDPM_ABI_VERSION"]
+    assert len(_lib._STRUCTS) == len(_lib._C_STRUCTS) >= 43
+    for name, st in zip(_lib._C_STRUCTS, _lib._STRUCTS):
+        assert L.anoddpm_struct_size(name.encode()) == ctypes.sizeof(st), name
+    assert L.anoddpm_struct_size(b"anoddpm_no_such_args") == -1 and L.anoddpm_struct_size(b"") == -1 and L.anoddpm_struct_size(None) == -1
+    assert [L.anoddpm_struct_size(i) for i in (1, 42, 99)] == [-1, -1, -1]                    # an index, as until ABI 31: refused, not read as a pointer
+
+
+def test_binding_is_derived_from_the_whole_header():
+    """Counts made on the raw header, independently of the parser: it saw every struct and every prototype, and names them as the
+    callers do."""
+    raw = open(_lib.HEADER).read()
+    assert len(re.findall(r"\btypedef\s+struct\b", raw)) == len(_lib._C_STRUCTS) == len(_lib._STRUCTS)
+    assert header_symbols() == sorted(_lib._PROTOS) == sorted(_lib.SYMBOLS) and len(_lib.SYMBOLS) == len(set(_lib.SYMBOLS))
+    assert [st.__name__ for st in _lib._STRUCTS[:3]] == ["SimplexArgs", "PUpdateArgs", "IgemmArgs"]          # declaration order
+    assert _lib.Wgrad1Args is _lib._STRUCTS[list(_lib._C_STRUCTS).index("anoddpm_wgrad1_args")] and _lib.Op.__name__ == "Op"
+    assert (_lib.OP_IGEMM, _lib.OP_DROPOUT, _lib.OP_MAX, _lib.ROC_NAN, _lib.ROC_CURVE_TRUNCATED) == (1, 29, 32, 1, 16)
+    assert [n for n, _ in _lib.ResampleArgs._fields_][:2] == ["inp", "out"]                                    # `in` is a Python keyword
+    ptr_or = lambda cls, name: dict(cls._fields_)[name]                                                        # noqa: E731
+    assert ptr_or(_lib.MriSliceArgs, "affine") is ctypes.c_void_p and ptr_or(_lib.DropoutArgs, "seed") is ctypes.c_uint64
+    assert ptr_or(_lib.SimplexArgs, "persistence") is ctypes.c_double and ptr_or(_lib.IgemmArgs, "alpha") is ctypes.c_float
+    L = _lib.lib()
+    assert L.anoddpm_igemm.argtypes == [ctypes.POINTER(_lib.IgemmArgs), ctypes.c_void_p] and L.anoddpm_abi_version.argtypes == []
+    assert L.anoddpm_roc_workspace_bytes.restype is ctypes.c_int64 and L.anoddpm_last_error.restype is ctypes.c_char_p
+    assert L.anoddpm_prof_collect.argtypes == [ctypes.c_void_p, ctypes.c_void_p]
+
+
+def test_field_offsets_match_the_c_compiler(tmp_path):
+    """offsetof of every field and sizeof of every struct, as a C compiler lays the header out, against the ctypes classes derived
+    from it: a field of the wrong type, or two fields swapped, moves an offset even where the struct's size stays the same."""
+    import shutil
+    import subprocess
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("gcc not available")
+    lines = []
+    for cname, fields in _lib._C_STRUCTS.items():
+        lines.append(f'  printf("{cname} - %zu\\n", sizeof({cname}));\n')
+        lines += [f'  printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));\n' for f, _, _ in fields]
+    src = tmp_path / "offsets.c"
+    src.write_text('#include "anoddpm_hip.h"\n#include <stddef.h>\n#include <stdio.h>\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
+    exe = tmp_path / "offsets"
+    subprocess.run([gcc, "-std=c99", "-I", os.path.dirname(_lib.HEADER), str(src), "-o", str(exe)], check=True)
+    got = [tuple(ln.split()) for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()]
+    want = []
+    for cname, st in zip(_lib._C_STRUCTS, _lib._STRUCTS):
+        assert len(st._fields_) == len(_lib._C_STRUCTS[cname])
+        want.append((cname, "-", str(ctypes.sizeof(st))))
+        want += [(cname, c, str(getattr(st, py).offset)) for (c, _, _), (py, _) in zip(_lib._C_STRUCTS[cname], st._fields_)]
+    assert len(want) > 600 and got == want, [x for x in zip(got, want) if x[0] != x[1]][:5]
+
+
+@pytest.mark.parametrize("text, what", [
+    ("typedef struct { int32_t n; float w[4]; } anoddpm_x_args;", "not a plain declaration"),                 # an array field
+    ("typedef struct { size_t n; } anoddpm_x_args;", "no ctypes mapping for type 'size_t'"),                 # an unknown type
+    ("int anoddpm_f(int32_t n);\nstatic int g_count;", "not understood"),                                     # a stray declaration
+    ("#define ANODDPM_SCALE 1.5f", "not an integer constant"),
+])
+def test_parser_refuses_what_it_does_not_understand(text, what):
+    with pytest.raises(_lib.AnoddpmError, match=re.escape(what)):
+        _lib.parse_header(text)
 
 
 def test_argument_validation_without_gpu():

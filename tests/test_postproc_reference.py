@@ -169,10 +169,9 @@ def test_struct_sizes_and_version():
     from anoddpm_amd import _lib
     L = _lib.lib()
     assert _lib.ABI_VERSION >= 28
-    assert _lib._STRUCTS[-3:] == [_lib.MedianArgs, _lib.ErodeArgs, _lib.ComponentsArgs]          # appended after the existing entries
-    for st in _lib._STRUCTS[-3:]:
-        assert L.anoddpm_struct_size(_lib._STRUCTS.index(st)) == ctypes.sizeof(st)
-    assert _lib._STRUCTS.index(_lib.SsimArgs) == 35
+    assert L.anoddpm_abi_version() == _lib.ABI_VERSION
+    for name, st in (("median", _lib.MedianArgs), ("erode", _lib.ErodeArgs), ("components", _lib.ComponentsArgs), ("ssim", _lib.SsimArgs)):
+        assert st in _lib._STRUCTS and L.anoddpm_struct_size(b"anoddpm_%s_args" % name.encode()) == ctypes.sizeof(st)
 
 
 def test_median_abi_validation_without_gpu():

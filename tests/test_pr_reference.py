@@ -87,7 +87,7 @@ def test_pr_abi_validation_without_gpu():
     from anoddpm_amd import _lib
     L = _lib.lib()
     assert _lib.ABI_VERSION >= 27 and L.anoddpm_abi_version() == _lib.ABI_VERSION
-    assert L.anoddpm_struct_size(_lib._STRUCTS.index(_lib.RocArgs)) == ctypes.sizeof(_lib.RocArgs)
+    assert L.anoddpm_struct_size(b"anoddpm_roc_args") == ctypes.sizeof(_lib.RocArgs)
     names = [f[0] for f in _lib.RocArgs._fields_]
     assert {"ap", "best_dice", "best_thr", "best_counts", "curve_mode"} <= set(names)
     assert names.index("S") < min(names.index(k) for k in ("ap", "best_dice", "best_thr", "best_counts", "curve_mode"))      # appended

@@ -91,7 +91,7 @@ def test_ragged_case_is_what_it_is_for():
 def test_roc_abi_validation_without_gpu():
     from anoddpm_amd import _lib
     L = _lib.lib()
-    assert _lib.ABI_VERSION >= 25 and L.anoddpm_struct_size(_lib._STRUCTS.index(_lib.RocArgs)) == ctypes.sizeof(_lib.RocArgs)
+    assert _lib.ABI_VERSION >= 25 and L.anoddpm_struct_size(b"anoddpm_roc_args") == ctypes.sizeof(_lib.RocArgs)
     assert L.anoddpm_roc_auc(None, None) == -1 and b"null args" in L.anoddpm_last_error()
     a = _lib.RocArgs()
     assert L.anoddpm_roc_auc(ctypes.byref(a), None) == -1 and b"null pointer" in L.anoddpm_last_error()

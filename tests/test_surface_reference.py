@@ -207,10 +207,8 @@ def test_abi_moves_together():
     from anoddpm_amd import _lib
     L = _lib.lib()
     assert L.anoddpm_abi_version() == _lib.ABI_VERSION
-    for st in (_lib.DistanceArgs, _lib.SurfaceArgs):
-        assert L.anoddpm_struct_size(_lib._STRUCTS.index(st)) == ctypes.sizeof(st)
-    # additions only: the two structs sit between the entries earlier tests pin, and no existing struct or entry point changed
-    assert (_lib._STRUCTS.index(_lib.DistanceArgs), _lib._STRUCTS.index(_lib.SurfaceArgs)) == (38, 39)
+    for name, st in ((b"anoddpm_distance_args", _lib.DistanceArgs), (b"anoddpm_surface_args", _lib.SurfaceArgs)):
+        assert st in _lib._STRUCTS and L.anoddpm_struct_size(name) == ctypes.sizeof(st)
     for name in ("anoddpm_distance_transform", "anoddpm_surface_distance", "anoddpm_surface_workspace_bytes"):
         assert name in _lib.SYMBOLS and hasattr(L, name)
     assert (_lib.SURFACE_EMPTY_PRED, _lib.SURFACE_EMPTY_REF) == (sc.EMPTY_PRED, sc.EMPTY_REF)
