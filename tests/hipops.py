@@ -272,76 +272,116 @@ def softmax_rows_backward(p, dp):
     return buf[:rows * L].reshape(p.shape), buf[rows * L:]
 
 
-def resample(x, mode, gn=None):
-    """x NHWC.  mode 1 nearest x2, 2 average 2x2; with gn = (scale, shift) [B][C] mode 2 also returns the pooled ACTIVATED tensor."""
+def _launch(rc, what, raw):
+    """raw: hand back the entry point's status (an argument check of a test); otherwise raise on an error and wait for the launch."""
+    if raw:
+        return rc
+    check(rc, what)
+    torch.cuda.synchronize()
+    return rc
+
+
+def resample(x, mode, gn=None, *, out=None, act=None, raw=False):
+    """x NHWC [B, H, W, C].  mode 1 nearest x2, 2 average 2x2, 3 the even pixels, 4 the adjoint of 3 (values on the even pixels of a
+    2H x 2W map, zeros elsewhere); with gn = (scale, shift) [B][C] mode 2 also returns the pooled ACTIVATED tensor.
+    out, act: the caller's buffers (a guarded buffer of a test) instead of fresh ones; the result is then their leading elements."""
     B, H, W, C = x.shape
-    Ho = H * 2 if mode == 1 else H // 2
-    out = torch.full((B, Ho, Ho, C), float("nan"), device=x.device)
+    Ho, Wo = (H * 2, W * 2) if mode in (1, 4) else (H // 2, W // 2)
+    n = B * Ho * Wo * C
+    out = torch.full((B, Ho, Wo, C), float("nan"), device=x.device) if out is None else out
     st = ResampleArgs()
     st.inp, st.out, st.B, st.H, st.W, st.C, st.mode = x.data_ptr(), out.data_ptr(), B, H, W, C, mode
-    act = None
     if gn is not None:
-        act = torch.full((B, Ho, Ho, C), float("nan"), device=x.device)
+        act = torch.full((B, Ho, Wo, C), float("nan"), device=x.device) if act is None else act
         st.gn_scale, st.gn_shift, st.out_act = gn[0].data_ptr(), gn[1].data_ptr(), act.data_ptr()
-    check(lib().anoddpm_resample2x(ctypes.byref(st), current_stream()), "resample")
-    torch.cuda.synchronize()
-    return out if gn is None else (out, act)
+    rc = _launch(lib().anoddpm_resample2x(ctypes.byref(st), current_stream()), "resample", raw)
+    if raw:
+        return rc
+    out = out.view(-1)[:n].view(B, Ho, Wo, C)
+    return out if gn is None else (out, act.view(-1)[:n].view(B, Ho, Wo, C))
 
 
-def linear(x, w, b, act_in=0, act_out=0):
-    B, K = x.shape
+def linear(x, w, b, act_in=0, act_out=0, *, out=None, B=None, K=None, raw=False):
+    """out (the caller's buffer), B, K (the sizes the struct states, where a test's differ from the tensor's) are optional."""
+    B, K = x.shape[0] if B is None else B, x.shape[1] if K is None else K
     N = w.shape[0]
-    out = torch.full((B, N), float("nan"), device=x.device)
+    out = torch.full((B, N), float("nan"), device=x.device) if out is None else out
     st = LinearArgs()
     st.inp, st.w, st.bias, st.out = x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, out.data_ptr()
     st.B, st.K, st.N, st.act_in, st.act_out = B, K, N, act_in, act_out
-    check(lib().anoddpm_linear_small(ctypes.byref(st), current_stream()), "linear")
-    torch.cuda.synchronize()
-    return out
+    rc = _launch(lib().anoddpm_linear_small(ctypes.byref(st), current_stream()), "linear", raw)
+    return rc if raw else out.view(-1)[:B * N].view(B, N)
 
 
-def posemb(t, freqs, dim):
+def posemb(t, freqs, dim, scale=1.0, *, zero=None, zero_doubles=0, out=None, raw=False):
+    """zero: a float64 buffer whose first zero_doubles elements the launch clears (the plan's statistics accumulators)."""
     B = t.numel()
-    out = torch.full((B, dim), float("nan"), device=t.device)
+    out = torch.full((B, dim), float("nan"), device=t.device) if out is None else out
     st = PosembArgs()
-    st.t, st.freqs, st.out, st.B, st.dim, st.scale = t.data_ptr(), freqs.data_ptr(), out.data_ptr(), B, dim, 1.0
-    check(lib().anoddpm_posemb(ctypes.byref(st), current_stream()), "posemb")
-    torch.cuda.synchronize()
-    return out
+    st.t, st.freqs, st.out, st.B, st.dim, st.scale = t.data_ptr(), freqs.data_ptr(), out.data_ptr(), B, dim, scale
+    st.zero, st.zero_doubles = (zero.data_ptr() if zero is not None else None), zero_doubles
+    rc = _launch(lib().anoddpm_posemb(ctypes.byref(st), current_stream()), "posemb", raw)
+    return rc if raw else out.view(-1)[:B * dim].view(B, dim)
 
 
-def stem(x, w, b, with_stats=False):
-    """-> NHWC output [, fused GroupNorm partial sums [B][rows][Cout][2] (None when the shape has no fused form)]"""
-    B, Cin, H, W = x.shape
+def stem(x, w, b, with_stats=False, *, stats_rows=None, stats=None, out=None, x_offset=0, shape=None, raw=False):
+    """-> NHWC output [, fused GroupNorm partial sums [B][rows][Cout][2] (None when the shape has no fused form)].
+    stats_rows: the caller's rows per image instead of anoddpm_stem_stats_rows'; stats, out: the caller's buffers; x_offset, shape:
+    x is a flat buffer that holds x_offset floats in front of the [B, Cin, H, W] = shape input, and the launch reads from behind
+    them (an input pointer without the alignment of an allocation)."""
+    B, Cin, H, W = x.shape if shape is None else shape
     Cout = w.shape[0]
     wp = w.permute(2, 3, 1, 0).reshape(-1, Cout).contiguous()
-    out = torch.full((B, H, W, Cout), float("nan"), device=x.device)
+    out = torch.full((B, H, W, Cout), float("nan"), device=x.device) if out is None else out
     st = StemArgs()
-    st.x, st.w, st.bias, st.out = x.data_ptr(), wp.data_ptr(), b.data_ptr(), out.data_ptr()
+    st.x, st.w, st.bias, st.out = x.data_ptr() + 4 * x_offset, wp.data_ptr(), b.data_ptr(), out.data_ptr()
     st.B, st.H, st.W, st.Cin, st.Cout = B, H, W, Cin, Cout
-    stats = None
+    rows = 0
     if with_stats:
-        rows = lib().anoddpm_stem_stats_rows(H, W, Cin, Cout)
+        rows = lib().anoddpm_stem_stats_rows(H, W, Cin, Cout) if stats_rows is None else stats_rows
         if rows > 0:
-            stats = torch.full((B, rows, Cout, 2), float("nan"), device=x.device)
+            stats = torch.full((B, rows, Cout, 2), float("nan"), device=x.device) if stats is None else stats
             st.stats, st.stats_rows = stats.data_ptr(), rows
-    check(lib().anoddpm_conv_stem(ctypes.byref(st), current_stream()), "stem")
-    torch.cuda.synchronize()
+        else:
+            stats = None
+    rc = _launch(lib().anoddpm_conv_stem(ctypes.byref(st), current_stream()), "stem", raw)
+    if raw:
+        return rc
+    out = out.view(-1)[:B * H * W * Cout].view(B, H, W, Cout)
+    if with_stats and stats is not None:
+        stats = stats.view(-1)[:B * rows * Cout * 2].view(B, rows, Cout, 2)
     return (out, stats) if with_stats else out
 
 
-def head(x, w, b, scale, shift):
+def head(x, w, b, scale, shift, *, out=None, raw=False):
     """x NHWC, w OIHW (O <= 4) -> NCHW output."""
     B, H, W, C = x.shape
     Cout = w.shape[0]
     wp = w.permute(2, 3, 1, 0).reshape(-1, Cout).contiguous()
-    out = torch.full((B, Cout, H, W), float("nan"), device=x.device)
+    out = torch.full((B, Cout, H, W), float("nan"), device=x.device) if out is None else out
     st = HeadArgs()
     st.x, st.w, st.bias, st.gn_scale, st.gn_shift, st.out = x.data_ptr(), wp.data_ptr(), b.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr()
     st.B, st.H, st.W, st.C, st.Cout = B, H, W, C, Cout
-    check(lib().anoddpm_conv_head(ctypes.byref(st), current_stream()), "conv_head")
-    torch.cuda.synchronize()
-    return out
+    rc = _launch(lib().anoddpm_conv_head(ctypes.byref(st), current_stream()), "conv_head", raw)
+    return rc if raw else out.view(-1)[:B * Cout * H * W].view(B, Cout, H, W)
+
+
+def softmax_rows(buf, rows, L):
+    """anoddpm_softmax_rows in place on the first rows x L floats of buf."""
+    sm = SoftmaxArgs()
+    sm.x, sm.rows, sm.L = buf.data_ptr(), rows, L
+    _launch(lib().anoddpm_softmax_rows(ctypes.byref(sm), current_stream()), "softmax_rows", False)
+    return buf.view(-1)[:rows * L].view(rows, L)
+
+
+def nhwc_to_nchw(x, B, P, C, in_ld, *, first=0, out=None, raw=False):
+    """anoddpm_nhwc_to_nchw: x holds [B][P][in_ld] floats, of which channels first .. first + C go to out [B][C][P]."""
+    from anoddpm_amd._lib import LayoutArgs
+    out = torch.full((B, C, P), float("nan"), device=x.device) if out is None else out
+    st = LayoutArgs()
+    st.inp, st.out, st.B, st.P, st.C, st.in_ld = x.data_ptr() + 4 * first, out.data_ptr(), B, P, C, in_ld
+    rc = _launch(lib().anoddpm_nhwc_to_nchw(ctypes.byref(st), current_stream()), "nhwc_to_nchw", raw)
+    return rc if raw else out.view(-1)[:B * C * P].view(B, C, P)
 
 
 def conv_wgrad(srcs, dy, *, gn=None, act=0, a_mode=0, band=None, accumulate_into=None, colsum_out=None, algo=0, bias_out=None):
