@@ -37,6 +37,7 @@ SOURCES = {
     "surface.hip": ["-ffp-contract=off"],
     "ssim.hip": ["-ffp-contract=off"],
     "postproc.hip": [],
+    "smooth.hip": ["-ffp-contract=off"],
     "wgrad.hip": [],
     "wgrad43.hip": [],
     "gn_backward.hip": [],

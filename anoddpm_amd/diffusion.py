@@ -636,6 +636,9 @@ class GaussianDiffusionModel:
     # opt-in boundary distances of the detection records (Hausdorff, HD95, average symmetric surface distance of the thresholded
     # map against the mask); see _score_settings.  A plain attribute like `postprocess`.
     surface_metrics = False
+    # opt-in image-level scores of the detection records (metrics.image_scores' `top`: an int k or a fraction in (0, 1]): the maximum
+    # and the top-k mean of every image's squared-error map; see _score_settings.  A plain attribute like `pro_limit`.
+    image_top = None
     # opt-in strided reverse sampler (StridedSampler; None: the reference's ancestral sampler, and none of the strided code runs).
     # Read by ReverseChain / reverse_chain / forward_backward and the detection loops unless they are handed `sampler=`; also set at
     # construction from ANODDPM_SAMPLER="<stride>[,<eta>]".  A plain attribute like `postprocess`.
@@ -1290,7 +1293,9 @@ class GaussianDiffusionModel:
     _RECORD_SCORES = tuple((k, ()) for k in ("auc", "auc_status", "ap", "best_dice", "best_threshold", "ssim")) \
         + tuple((k, ("postprocess",)) for k in ("sqerr_pp", "auc_pp", "ap_pp", "best_dice_pp", "best_threshold_pp")) \
         + (("aupro", ("pro_limit",)), ("aupro_pp", ("pro_limit", "postprocess"))) \
-        + tuple((k, None) for k in ("hd", "hd95", "assd", "hd_pp", "hd95_pp", "assd_pp"))
+        + tuple((k, None) for k in ("hd", "hd95", "assd", "hd_pp", "hd95_pp", "assd_pp")) \
+        + tuple((k, ("image_top",)) for k in ("image_max", "image_topk")) \
+        + tuple((k, ("image_top", "postprocess")) for k in ("image_max_pp", "image_topk_pp"))
 
     def _score_settings(self, settings, outputs, total_avg, x_0, mask):
         """The end of detection_A / detection_B: settings[j] (the keys that name a setting) owns the `total_avg` chains
@@ -1299,7 +1304,8 @@ class GaussianDiffusionModel:
         `metrics.score_maps` over all settings (one launch per step for the whole sweep; fp64 device scalars, `ssim` [B] per record;
         never synchronises).  `auc` ... `ssim` stay None where nothing fills them (no mask, images below the SSIM window); the opt-in
         `self.postprocess` (with `self.postprocess_roi`) and `self.pro_limit` add their keys, None without a mask;
-        `self.surface_metrics` adds `hd`, `hd95`, `assd` (and `_pp`) only with a mask.  All unset: exactly the first six."""
+        `self.surface_metrics` adds `hd`, `hd95`, `assd` (and `_pp`) only with a mask; `self.image_top` adds `image_max` and
+        `image_topk` (and `_pp`), [B] per record, mask or not.  All unset: exactly the first six."""
         from . import metrics
         self.last_detection, stacks = [], {"mean": [], "sqerr": [], "thr_img": []}
         for j, extra in enumerate(settings):
@@ -1311,7 +1317,8 @@ class GaussianDiffusionModel:
         if not settings:
             return
         scores = metrics.score_maps(x_0, *(torch.stack(stacks[k]) for k in ("mean", "sqerr", "thr_img")), mask, postprocess=self.postprocess,
-                                    roi=self.postprocess_roi, pro_limit=self.pro_limit, surface=bool(self.surface_metrics))
+                                    roi=self.postprocess_roi, pro_limit=self.pro_limit, surface=bool(self.surface_metrics),
+                                    image_top=self.image_top)
         for j, rec in enumerate(self.last_detection):
             for key, options in self._RECORD_SCORES:
                 if key in scores:

@@ -53,6 +53,14 @@ prediction against its reference or against one shared reference, in four launch
 selected on the integer squared distances and the means are fp64 sums in a fixed order, so the same input gives the same bits.
 `HD95` returns a Python float.  Pixel units only (no `sampling=`), 2-D planes only, one threshold per call.
 
+Texture protocol (Bergmann et al.; the reference evaluates DAGM carpet and MVTec leather with the brain-MRI code path).  Published
+pipelines smooth the anomaly map with `scipy.ndimage.gaussian_filter(map, sigma=4)` before AUROC / PRO and report an image-level
+AUROC of one score per image first.  `gaussian_filter` is that filter on the device (`anoddpm_gauss2d`, csrc/smooth.hip: one launch
+over all planes of a batch, scipy's fp64 taps in scipy's order, bit for bit scipy's for finite inputs), `image_scores` the maximum,
+mean and top-k mean of every image from ONE launch (`anoddpm_map_scores`: the k-th largest value is selected on the bit pattern,
+the sums are fp64 in a fixed order), `image_auc` the AUROC of N such scores against N image labels (`roc_auc` of one segment).
+`PostProcess(gaussian=sigma)` puts the filter in front of the median; `score_maps(..., image_top=)` adds the image scores.
+
 `score_maps` states the scoring pipeline once: R stacks of maps in, one launch per step whatever R is -- curve scores, SSIM, and
 opt-in the post-processing with its own curve scores, AUPRO and the boundary distances -- a dict of device tensors with a leading
 R axis out, without a host synchronisation; a score that cannot be computed has no key.  Its callers only say how a result
@@ -67,12 +75,12 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs, ErodeArgs, MedianArgs, ProArgs, RocArgs, SsimArgs, SurfaceArgs, check,
-                   current_stream, lib)
+from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs, ErodeArgs, GaussArgs, MapScoresArgs, MedianArgs, ProArgs, RocArgs, SsimArgs,
+                   SurfaceArgs, check, current_stream, lib)
 
 __all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "median_filter", "erode_mask",
            "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "aupro", "pro_points", "AUPRO", "distance_transform",
-           "surface_distance", "HD95", "anomaly_metrics_surface", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
+           "surface_distance", "HD95", "anomaly_metrics_surface", "gaussian_filter", "image_scores", "image_auc", "anomaly_metrics_image", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
 
 NC = _lib.ANOMALY_NCOUNTS
@@ -501,13 +509,122 @@ def remove_small_components(pred, min_size=7, connectivity=1, return_counts=Fals
     return (out, counts) if return_counts else out
 
 
-class PostProcess:
+def _gauss_radius(sigma, truncate, what):
+    """scipy's radius `int(truncate * sigma + 0.5)` of positive finite floats; ValueError unless it is in 1 ... GAUSS_MAX_RADIUS."""
+    ok = all(isinstance(v, (int, float)) and not isinstance(v, bool) and 0.0 < float(v) < float("inf") for v in (sigma, truncate))
+    radius = int(float(truncate) * float(sigma) + 0.5) if ok else 0
+    if not 1 <= radius <= _lib.GAUSS_MAX_RADIUS:
+        raise ValueError(f"{what}: sigma and truncate must be positive finite numbers whose radius int(truncate * sigma + 0.5) is in "
+                         f"1 ... {_lib.GAUSS_MAX_RADIUS}, got sigma={sigma!r}, truncate={truncate!r}")
+    return radius
+
+
+_GAUSS_TABLES = {}                                                   # (sigma, truncate, device) -> fp64 [radius + 1] on that device
+
+
+def _gauss_table(sigma, truncate, radius, dev):
+    """The taps `anoddpm_gauss2d` reads, outermost first, as scipy's `_gaussian_kernel1d` computes them with numpy in fp64.  Made
+    and copied to the device once per (sigma, truncate, device): the first call allocates and copies, later ones only launch."""
+    key = (float(sigma), float(truncate), dev)
+    if key not in _GAUSS_TABLES:
+        import numpy as np
+        x = np.arange(-radius, radius + 1)
+        w = np.exp(-0.5 / (float(sigma) * float(sigma)) * x ** 2)
+        w = w / w.sum()
+        _GAUSS_TABLES[key] = torch.from_numpy(w[:radius + 1].copy()).to(dev)
+    return _GAUSS_TABLES[key]
+
+
+def gaussian_filter(score, sigma=4.0, truncate=4.0, batched=None):
+    """`scipy.ndimage.gaussian_filter(plane, sigma, truncate=truncate)` (order 0, reflect border, the same sigma on both axes) of
+    every H x W plane of score: [S, ..., H, W], batching and strides as `median_filter`.  Returns an fp32 device tensor shaped
+    like score, bit for bit scipy's on the fp32 planes for finite inputs, in ONE launch and without a host synchronisation; a
+    plane may be narrower than the radius.  `sigma` and `truncate`: positive finite numbers whose radius `int(truncate * sigma +
+    0.5)` is in 1 ... 32 (sigma 4: 16), else ValueError.  NaN / inf spread within their radius by IEEE rules; no other plane is
+    touched.  The tap table is cached per (sigma, truncate, device): after its first use a call only launches (graph-capture-safe)."""
+    if not isinstance(score, torch.Tensor):
+        raise TypeError("gaussian_filter: score must be a device tensor")
+    radius = _gauss_radius(sigma, truncate, "gaussian_filter")
+    S, C, H, W = _planes(score, _is_batched(score, batched), "gaussian_filter")
+    sc, s_stride = _plane_rows(score, S, C, H, W, "gaussian_filter(score)")
+    dev = sc.device
+    out = torch.empty(tuple(score.shape), dtype=torch.float32, device=dev)
+    a = GaussArgs()
+    a.src, a.dst, a.w, a.src_stride = sc.data_ptr(), out.data_ptr(), _gauss_table(sigma, truncate, radius, dev).data_ptr(), s_stride
+    a.S, a.H, a.W, a.radius = S * C, H, W, radius
+    _launch("gauss2d", a, dev)
+    return out
+
+
+def image_scores(score, top=0.01, batched=None, return_status=False):
+    """One score per image: score [S, ...] (`batched`; the default is `roc_auc`'s), every value of `score[s]` -- all channels
+    -- pooled into image s.  Returns a dict of [S] device tensors from ONE launch, no host synchronisation, the same bits every
+    run: `max` (fp32), `mean` (fp64) and `topk` (fp64): the mean of the k largest values (as a multiset: ties cannot matter).
+    `top`: an int is k; a float in (0, 1] the fraction of the n values of an image, `k = max(1, int(top * n))`.  Values must be
+    finite and >= 0 as for `roc_auc` (-0.0 counts as +0.0): an image that breaks this gets NaN and a non-zero status word
+    (`return_status=True` returns `(dict, status)`, status int32 [S]).  n is at most 2^24 (one workgroup per image)."""
+    if not isinstance(score, torch.Tensor):
+        raise TypeError("image_scores: score must be a device tensor")
+    S = score.shape[0] if _is_batched(score, batched) else 1
+    if score.numel() == 0 or S < 1:
+        raise ValueError("image_scores: empty score")
+    sc, n, s_stride = _segments(score, S, "image_scores(score)")
+    if isinstance(top, bool) or not isinstance(top, (int, float)):
+        raise ValueError(f"image_scores: top must be an int k or a float fraction in (0, 1], got {top!r}")
+    if isinstance(top, int):
+        k = top
+    elif 0.0 < top <= 1.0:
+        k = max(1, int(top * n))
+    else:
+        raise ValueError(f"image_scores: a float top must be in (0, 1], got {top!r}")
+    if not 1 <= k <= n:
+        raise ValueError(f"image_scores: k = {k} is outside 1 ... n = {n}")
+    if n > _lib.MAP_SCORES_MAX_N:
+        raise ValueError(f"image_scores: an image of {n} values exceeds {_lib.MAP_SCORES_MAX_N}")
+    dev = sc.device
+    out = {"max": torch.empty((S,), dtype=torch.float32, device=dev), "mean": torch.empty((S,), dtype=torch.float64, device=dev),
+           "topk": torch.empty((S,), dtype=torch.float64, device=dev), "status": torch.empty((S,), dtype=torch.int32, device=dev)}
+    a = MapScoresArgs()
+    a.src, a.max, a.mean, a.topk_mean, a.status = sc.data_ptr(), out["max"].data_ptr(), out["mean"].data_ptr(), out["topk"].data_ptr(), out["status"].data_ptr()
+    a.src_stride, a.n, a.k, a.S = s_stride, n, k, S
+    _launch("map_scores", a, dev)
+    status = out.pop("status")
+    for key in tuple(out):
+        out[key] = torch.where(status != 0, torch.full_like(out[key], float("nan")), out[key])
+    return (out, status) if return_status else out
+
+
+def image_auc(labels, scores, return_status=False):
+    """Image-level AUROC: `roc_auc` of ONE segment of N image scores (a device tensor of N values, e.g. `image_scores(...)["max"]`
+    of a test set; ranked as fp32) against N 0 / 1 image labels.  Returns a [1] fp64 device tensor without a host synchronisation:
+    NaN when a class is empty or the scores break `roc_auc`'s precondition (`return_status=True` also returns the status word)."""
+    if not isinstance(labels, torch.Tensor) or not isinstance(scores, torch.Tensor):
+        raise TypeError("image_auc: labels and scores must be device tensors")
+    if labels.numel() != scores.numel():
+        raise ValueError(f"image_auc: {labels.numel()} labels for {scores.numel()} scores")
+    return roc_auc(labels.reshape(-1), scores.reshape(-1), batched=False, return_status=return_status)
+
+
+class _PostProcessType(type):
+    """`PostProcess(..., gaussian=sigma)`: the trailing keyword is taken here, by the call of the class, and `__init__` keeps the
+    five positional settings and the signature it has had since it was written (callers and tests read it with `inspect`)."""
+
+    def __call__(cls, *args, gaussian=None, **kw):
+        self = super().__call__(*args, **kw)
+        if gaussian is not None:
+            _gauss_radius(gaussian, 4.0, "PostProcess: gaussian")
+            object.__setattr__(self, "gaussian", float(gaussian))
+        return self
+
+
+class PostProcess(metaclass=_PostProcessType):
     """Settings of the post-processing between the squared error and its scores; immutable.  `median`: window of the median
     filter (3, 5, 7; None: off).  `erode`: erosions of the region of interest (0 ... 8; 0: used as it is).  `roi_level`: when not
     None the region of interest is `real > roi_level` (the images live in [-1, 1] with a -1 background) unless the caller hands
     one in.  `min_size` / `connectivity`: components of the thresholded map below that many pixels are dropped (0: off).  The
-    defaults are the values common in published pipelines."""
-    __slots__ = ("median", "erode", "roi_level", "min_size", "connectivity")
+    defaults are the values common in published pipelines.  `gaussian` (keyword only; None: off): sigma of a Gaussian filter
+    (`gaussian_filter`, truncate 4.0) applied before the median -- the smoothing of the texture protocol."""
+    __slots__ = ("median", "erode", "roi_level", "min_size", "connectivity", "gaussian")
 
     def __init__(self, median=5, erode=3, roi_level=None, min_size=7, connectivity=1):
         if median is not None and median not in _lib.MEDIAN_SIZES:
@@ -518,6 +635,7 @@ class PostProcess:
             raise ValueError(f"PostProcess: min_size must be an integer >= 0, got {min_size!r}")
         if connectivity not in (1, 2):
             raise ValueError(f"PostProcess: connectivity must be 1 or 2, got {connectivity!r}")
+        object.__setattr__(self, "gaussian", None)                   # _PostProcessType.__call__ sets it
         for k, v in (("median", median), ("erode", int(erode)), ("roi_level", None if roi_level is None else float(roi_level)),
                      ("min_size", int(min_size)), ("connectivity", int(connectivity))):
             object.__setattr__(self, k, v)
@@ -528,8 +646,13 @@ class PostProcess:
     def __delattr__(self, name):
         raise AttributeError("PostProcess is immutable")
 
+    def _settings(self):
+        """The settings that are spelled out: `gaussian` only when it is set, so that key, hash, repr and pickle of everything from
+        before it existed are what they were."""
+        return [k for k in self.__slots__ if k != "gaussian" or self.gaussian is not None]
+
     def _key(self):
-        return tuple(getattr(self, k) for k in self.__slots__)
+        return tuple(getattr(self, k) for k in self._settings())
 
     def __eq__(self, other):
         return isinstance(other, PostProcess) and self._key() == other._key()
@@ -538,10 +661,16 @@ class PostProcess:
         return hash(self._key())
 
     def __repr__(self):
-        return "PostProcess(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+        return "PostProcess(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self._settings()) + ")"
 
     def __reduce__(self):
-        return PostProcess, self._key()
+        if self.gaussian is None:
+            return PostProcess, self._key()
+        return _postprocess_from, ({k: getattr(self, k) for k in self.__slots__},)
+
+
+def _postprocess_from(settings):
+    return PostProcess(**settings)
 
 
 def postprocess_maps(sqerr, pp, real=None, roi=None):
@@ -549,7 +678,8 @@ def postprocess_maps(sqerr, pp, real=None, roi=None):
     of interest.  The region is `roi` (a 0 / 1 tensor) when given, else `real > pp.roi_level` when `pp.roi_level` is set, else
     everything; it has the shape of one plane (shared by all maps), one segment or sqerr, and is eroded `pp.erode` times in ONE
     launch before the ONE median launch applies it.  Returns a device tensor shaped like sqerr, no host synchronisation.  With
-    `pp.median` None the region is applied by an elementwise product."""
+    `pp.median` None the region is applied by an elementwise product.  `pp.gaussian` runs first: the median and the region see
+    the smoothed maps (ONE more launch)."""
     if not isinstance(pp, PostProcess):
         raise TypeError("postprocess_maps: pp must be a PostProcess")
     level = 0.0
@@ -559,11 +689,14 @@ def postprocess_maps(sqerr, pp, real=None, roi=None):
         roi, level = real, pp.roi_level
     if roi is not None:
         roi = erode_mask(roi, pp.erode, level) if pp.erode else (_f32c(roi, "postprocess_maps(roi)") > level).float()
+    smoothed = pp.gaussian is not None
+    if smoothed:
+        sqerr = gaussian_filter(sqerr, pp.gaussian)
     if pp.median is not None:
         return median_filter(sqerr, pp.median, roi=roi)
     out = _f32c(sqerr, "postprocess_maps(sqerr)")
     if roi is None:
-        return out.clone()
+        return out if smoothed else out.clone()
     S, C, H, W = _planes(out, _is_batched(out, None), "postprocess_maps")
     if roi.numel() not in (H * W, C * H * W, S * C * H * W):
         raise ValueError(f"postprocess_maps: roi {tuple(roi.shape)} does not match sqerr {tuple(sqerr.shape)}")
@@ -727,7 +860,8 @@ def _valid_mean(values, status):
     return torch.where(n > 0, total / n.clamp(min=1), torch.full_like(total, float("nan"))), n
 
 
-def score_maps(real, mean, sqerr, pred, mask, postprocess=None, roi=None, pro_limit=None, surface=False, threshold=0.5, pred_pp=False):
+def score_maps(real, mean, sqerr, pred, mask, postprocess=None, roi=None, pro_limit=None, surface=False, threshold=0.5, pred_pp=False,
+               image_top=None):
     """Every score of R stacks of anomaly maps, one launch per step whatever R is.  real: [B, C, H, W]; mean (the averaged
     reconstructions), sqerr and pred: [R, B, C, H, W], `pred > 0` being the thresholded map (the 0 / 1 `pred` and the -1 / 1
     `thr_img` of `anomaly_maps` both do); mask: like real, or None.  Setting r pools its B images into one curve, as
@@ -744,7 +878,10 @@ def score_maps(real, mean, sqerr, pred, mask, postprocess=None, roi=None, pro_li
     `aupro_status` [R] of the raw maps -- one component run on the mask and one PRO launch.
     With `surface` and a mask: `hd`, `hd95`, `assd` (and their `_pp` forms) [R]: `surface_distance` of every plane of pred (and
     pred_pp) against its mask plane in one call (a mask of one plane is shared), each the mean over the setting's planes whose
-    status is 0, NaN when there is none; `surface_status` [R, B * C], the planes' status words for pred."""
+    status is 0, NaN when there is none; `surface_status` [R, B * C], the planes' status words for pred.
+    With `image_top` (`image_scores`' `top`; no mask needed): `image_max`, `image_mean`, `image_topk` (and their `_pp` forms) [R, B],
+    the scores of every image's sqerr (all its channels pooled), and `image_status` [R, B] of the raw maps -- ONE launch over all
+    R * B images (2 R B with `postprocess`)."""
     R, have_mask = sqerr.shape[0], mask is not None
     out, stacks = {}, [("", sqerr)]
 
@@ -768,6 +905,13 @@ def score_maps(real, mean, sqerr, pred, mask, postprocess=None, roi=None, pro_li
         out["aupro_regions"], out["aupro_status"] = o["counts"][:R, 0], o["status"][:R]
         for (sfx, _), val in zip(stacks, _nan_where_status(o, "aupro").reshape(-1, R)):
             out["aupro" + sfx] = val
+    if image_top is not None:
+        B = sqerr.shape[1]
+        o, status = image_scores(torch.cat([sq for _, sq in stacks]).reshape(len(stacks) * R * B, -1), image_top, batched=True, return_status=True)
+        out["image_status"] = status[:R * B].reshape(R, B)
+        for k in ("max", "mean", "topk"):
+            for (sfx, _), val in zip(stacks, o[k].reshape(-1, R, B)):
+                out["image_" + k + sfx] = val
     preds = [pred]
     if postprocess is not None and (pred_pp or (surface and have_mask)):
         out["pred_pp"] = _small_components(out["sqerr_pp"], float(threshold), postprocess.min_size, postprocess.connectivity)[0]
@@ -793,7 +937,11 @@ _METRIC_KEYS = (("AUC", "auc", NAN, ()), ("AP", "ap", NAN, ()), ("best_dice", "b
                 ("AUPRO", "aupro", NAN, ("pro",)), ("AUPRO_regions", "aupro_regions", 0, ("pro",)), ("AUPRO_status", "aupro_status", 0, ("pro",)),
                 ("AUPRO_pp", "aupro_pp", NAN, ("pro", "pp")),
                 ("HD", "hd", NAN, ("surface",)), ("HD95", "hd95", NAN, ("surface",)), ("ASSD", "assd", NAN, ("surface",)),
-                ("HD_pp", "hd_pp", NAN, ("surface", "pp")), ("HD95_pp", "hd95_pp", NAN, ("surface", "pp")), ("ASSD_pp", "assd_pp", NAN, ("surface", "pp")))
+                ("HD_pp", "hd_pp", NAN, ("surface", "pp")), ("HD95_pp", "hd95_pp", NAN, ("surface", "pp")), ("ASSD_pp", "assd_pp", NAN, ("surface", "pp")),
+                ("image_max", "image_max", [], ("image",)), ("image_mean", "image_mean", [], ("image",)), ("image_topk", "image_topk", [], ("image",)),
+                ("image_status", "image_status", [], ("image",)),
+                ("image_max_pp", "image_max_pp", [], ("image", "pp")), ("image_mean_pp", "image_mean_pp", [], ("image", "pp")),
+                ("image_topk_pp", "image_topk_pp", [], ("image", "pp")))               # a list: one entry per image of the batch
 
 
 def _to_host(tensors):
@@ -803,12 +951,12 @@ def _to_host(tensors):
     return {k: p.reshape(t.shape) for (k, t), p in zip(tensors.items(), parts)}
 
 
-def _metrics(real, recon, mask, threshold, postprocess, roi, pro_limit=None, surface=False):
+def _metrics(real, recon, mask, threshold, postprocess, roi, pro_limit=None, surface=False, image_top=None):
     """`anomaly_metrics`, `anomaly_metrics_pro` and `anomaly_metrics_surface`: `anomaly_maps`, `score_maps` of the one stack, one
     copy of every number to the host, `_METRIC_KEYS`."""
     maps, counts = anomaly_maps(real, recon, mask, threshold)
     o = score_maps(real, maps["mean"][None], maps["sqerr"][None], maps["pred"][None], mask, postprocess=postprocess, roi=roi,
-                   pro_limit=pro_limit, surface=surface, threshold=threshold, pred_pp=True)
+                   pro_limit=pro_limit, surface=surface, threshold=threshold, pred_pp=True, image_top=image_top)
     dev = {src: o[src][0] for _, src, _, _ in _METRIC_KEYS if src in o}
     dev["counts"] = counts
     if "ssim" in o:
@@ -824,10 +972,13 @@ def _metrics(real, recon, mask, threshold, postprocess, roi, pro_limit=None, sur
     mse = float(c[:, 9].sum()) / real.numel()
     r["mse"] = mse
     r["PSNR"] = float(20.0 * torch.log10(torch.tensor(float(c[:, 10].max())) / torch.sqrt(torch.tensor(mse)))) if mse > 0 else float("inf")
-    on = {"pp": postprocess is not None, "pro": pro_limit is not None, "surface": surface}
+    on = {"pp": postprocess is not None, "pro": pro_limit is not None, "surface": surface, "image": image_top is not None}
     for key, src, absent, options in _METRIC_KEYS:
         if all(on[k] for k in options):
-            r[key] = type(absent)(h[src]) if src in h else absent
+            if isinstance(absent, list):
+                r[key] = [int(v) if key.endswith("status") else v for v in h[src].tolist()] if src in h else []
+            else:
+                r[key] = type(absent)(h[src]) if src in h else absent
     for sfx in ("", "_pp") if on["pp"] else ("",):
         if r["best_dice" + sfx] != r["best_dice" + sfx]:
             r["best_threshold" + sfx] = NAN                          # no positive: no threshold is better than another
@@ -880,6 +1031,15 @@ def anomaly_metrics_surface(real, recon, mask, threshold=0.5, postprocess=None, 
     words; with `postprocess` also `HD_pp`, `HD95_pp`, `ASSD_pp` from `maps["pred_pp"]`, from the same launch.  Without a mask:
     NaN, 0, 0.  The inputs must be `[..., H, W]` images."""
     return _metrics(real, recon, mask, threshold, postprocess, roi, surface=True)
+
+
+def anomaly_metrics_image(real, recon, mask, threshold=0.5, postprocess=None, roi=None, image_top=0.01):
+    """`anomaly_metrics` with the image-level scores beside its results -- a function of its own, as `anomaly_metrics_pro` is, so
+    that `anomaly_metrics` keeps its signature, its keys and its launches.  `image_top` (`image_scores`' `top`: an int k or a
+    fraction in (0, 1]) ADDS `image_max`, `image_mean`, `image_topk` -- lists of B Python floats, the scores of every image's
+    squared-error map, NaN where `image_status` (B ints) is non-zero -- and with `postprocess` their `_pp` forms on the filtered
+    map, all from one launch.  `image_top=None`: exactly `anomaly_metrics(...)`, no key and no launch more."""
+    return _metrics(real, recon, mask, threshold, postprocess, roi, image_top=image_top)
 
 
 # ---------------------------------------------------------------------------------- evaluation.py surface

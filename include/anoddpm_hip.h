@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 32
+#define ANODDPM_ABI_VERSION 33
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -902,6 +902,62 @@ int anoddpm_median2d(const anoddpm_median_args *a, void *stream);
 int anoddpm_erode2d(const anoddpm_erode_args *a, void *stream);
 int anoddpm_small_components(const anoddpm_components_args *a, void *stream);
 int64_t anoddpm_small_components_workspace_bytes(int32_t S, int32_t H, int32_t W);  /* HOST function; -1 for an extent < 1 or S*H*W >= 2^31 */
+
+/* ------------------------------------------------------------------ Gaussian smoothing and image-level scores of anomaly maps
+ * The two steps the texture protocol (Bergmann et al., MVTec AD) puts between an anomaly map and its scores; the reference has
+ * no counterpart.
+ *
+ * anoddpm_gauss2d replaces scipy.ndimage.gaussian_filter(plane, sigma, truncate=truncate) with scipy's defaults (order 0,
+ *   mode="reflect": d c b a | a b c d | d c b a, the same sigma on both axes, fp32 in, fp32 out) on S planes of H x W fp32, plane p
+ *   at src + p * src_stride (src_stride >= H*W); dst is contiguous [S][H][W].  Bit for bit scipy's for finite inputs:
+ *     w       [dev] radius + 1 fp64 weights, w[0] the outermost tap and w[radius] the centre: with r = int(truncate * sigma + 0.5),
+ *             x = -r ... 0:  exp(-0.5 / sigma^2 * x^2) / (sum over all 2 r + 1 taps), as numpy computes them in fp64.  The kernel
+ *             only reads them.
+ *     axis 0  (along H) first:  acc = v[i] * w[r];  for j = -r ... -1 in that order:  acc += (v[i+j] + v[i-j]) * w[r+j];  v is the
+ *             line as fp64, no fused multiply-add; the result is ROUNDED TO fp32.  Axis 1 the same on that result.
+ *     border  index i of a line of n:  m = i mod 2n (non-negative);  m >= n -> 2n - 1 - m.  A plane narrower than the radius
+ *             reflects several times; min(H, W) > radius is NOT required.
+ *   Preconditions: 1 <= radius <= ANODDPM_GAUSS_MAX_RADIUS, S, H, W >= 1, S * tiles below 2^31, dst does not overlap src.  A
+ *   non-finite input propagates by IEEE rules within its radius (no status word); no other plane is touched.
+ *   One launch: a workgroup of 256 threads stages a 32 x 32 tile and its radius halo in LDS with the border resolved, runs the
+ *   axis-0 pass into an fp32 LDS buffer (that buffer is the rounding between the axes) and the axis-1 pass from it; the grid is
+ *   tiles x planes.  LDS: ((32 + 2r)^2 + 32 (32 + 2r)) * 4 + 264 bytes, 49416 at radius 32.
+ *
+ * anoddpm_map_scores: one score per image.  S segments of n contiguous fp32 values (one image, all its channels pooled) at
+ *   src + s * src_stride, and 1 <= k <= n:
+ *     max[s]        fp32, the largest value
+ *     mean[s]       fp64, sum / n
+ *     topk_mean[s]  fp64, the mean of the k largest values as a multiset:  v_k, the k-th largest, is SELECTED on the bit pattern
+ *                   (radix select, integer atomics only);  (sum over v > v_k of v  +  (k - #{v > v_k}) * v_k) / k
+ *     status[s]     precondition as anoddpm_roc_auc: values finite and >= 0 (-0.0 counts as +0.0); a segment that breaks it sets
+ *                   ANODDPM_ROC_NAN / _INF / _NEGATIVE and its other outputs are unspecified; no other segment is touched.
+ *   Both sums are fp64 in a fixed order: thread t of 1024 adds the elements t, t + 1024, ... in that order, a halving tree folds
+ *   the 64 partials of a wave (lane i + lane i+32, then +16, ... +1) and then the 16 wave sums the same way -- the same input
+ *   gives the same bits.  One launch, one workgroup per segment: n <= ANODDPM_MAP_SCORES_MAX_N (64 maps of 512 x 512), above it
+ *   the call is refused.
+ * No allocation and no host synchronisation in either. */
+#define ANODDPM_GAUSS_MAX_RADIUS 32
+#define ANODDPM_MAP_SCORES_MAX_N 16777216
+typedef struct anoddpm_gauss_args {
+    const float *src;               /* [dev] */
+    float *dst;                     /* [dev] [S][H][W] */
+    const double *w;                /* [dev] [radius + 1] */
+    int64_t src_stride;
+    int32_t S, H, W, radius;
+} anoddpm_gauss_args;
+
+typedef struct anoddpm_map_scores_args {
+    const float *src;               /* [dev] */
+    float *max;                     /* [dev] [S] */
+    double *mean;                   /* [dev] [S] */
+    double *topk_mean;              /* [dev] [S] */
+    int32_t *status;                /* [dev] [S] */
+    int64_t src_stride, n, k;
+    int32_t S;
+} anoddpm_map_scores_args;
+
+int anoddpm_gauss2d(const anoddpm_gauss_args *a, void *stream);
+int anoddpm_map_scores(const anoddpm_map_scores_args *a, void *stream);
 
 /* Variational-bound terms of one reverse step (GaussianDiffusion.py:384-397 calc_vlb_xt, and the two MSE curves of
  * calc_total_vlb :445-478): per sample b
