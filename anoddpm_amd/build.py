@@ -33,6 +33,7 @@ SOURCES = {
     "optim.hip": [],
     "metrics.hip": ["-ffp-contract=off"],
     "roc.hip": ["-ffp-contract=off"],
+    "roc_wide.hip": ["-ffp-contract=off"],
     "pro.hip": ["-ffp-contract=off"],
     "surface.hip": ["-ffp-contract=off"],
     "ssim.hip": ["-ffp-contract=off"],

@@ -22,67 +22,13 @@
 //        3 * 2^31); ties go to the higher score.  That order is total, so the reduction's shape does not matter
 // All counters are integers: the result is deterministic.  Compiled with -ffp-contract=off like the other metric kernels.
 #include "common.h"
+#include "roc_shared.h"                                          // what this file shares with roc_wide.hip
 
 namespace {
 
+using namespace anoddpm::roc;
+
 constexpr int THREADS = 1024, WAVES = THREADS / 64, RADIX = 256, UNROLL = 4;
-
-__device__ __forceinline__ void wave_sync()
-{
-    // same-wave LDS hand-off (one lane writes what other lanes of the wave read): the hardware runs a wave's LDS operations in
-    // order; this only keeps the compiler from moving them across the point or into divergent branches
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// exclusive prefix of v over the workgroup in thread order (two barriers; wsum: WAVES words of LDS)
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *wsum)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    __syncthreads();
-    return base + incl - v;
-}
-
-// sum of the per-wave totals below `wave`, and of all of them
-__device__ __forceinline__ void wave_carry(const uint32_t *wtot, int wave, uint32_t &below, uint32_t &total)
-{
-    below = 0;
-    total = 0;
-    for (int w = 0; w < WAVES; ++w) {
-        const uint32_t t = wtot[w];
-        if (w < wave) below += t;
-        total += t;
-    }
-}
-
-// run r (ascending score) of the compacted run list: does sklearn's drop_intermediate keep its curve point?
-__device__ __forceinline__ bool keep_point(const uint32_t *runpos, const uint32_t *runtp, uint32_t r, uint32_t R)
-{
-    if (r == 0 || r == R - 1) return true;                       // last / first point of the curve
-    const uint32_t rsm = runpos[r - 1], rs = runpos[r], rs1 = runpos[r + 1];
-    const uint32_t tpm = runtp[r - 1], tp = runtp[r], tp1 = runtp[r + 1];
-    // second difference at this point = counts of the next lower run minus the counts of this run
-    return (tp1 - tp) != (tp - tpm) || (rs1 - rs) != (rs - rsm);
-}
-
-// candidate (tps, cnt, r) of the best Dice: is a better than b?  den = cnt + P
-__device__ __forceinline__ bool dice_better(uint32_t tpa, uint32_t ca, uint32_t ra, uint32_t tpb, uint32_t cb, uint32_t rb, uint32_t P)
-{
-    const unsigned long long x = (unsigned long long)tpa * ((unsigned long long)cb + P);
-    const unsigned long long y = (unsigned long long)tpb * ((unsigned long long)ca + P);
-    return x > y || (x == y && ra > rb);
-}
 
 template <bool EXTRA>
 __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, int64_t seg_words)
@@ -110,12 +56,7 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
     {
         uint32_t st = 0;
         for (uint32_t i = tid; i < n; i += THREADS) {
-            const float s = score[i], m = mask[i];
-            if (s != s) st |= ANODDPM_ROC_NAN;
-            else if (s == INFINITY || s == -INFINITY) st |= ANODDPM_ROC_INF;
-            if (s < 0.0f) st |= ANODDPM_ROC_NEGATIVE;
-            if (!(m == 0.0f || m == 1.0f)) st |= ANODDPM_ROC_BAD_MASK;
-            src[i] = (__float_as_uint(s + 0.0f) << 1) | (m != 0.0f ? 1u : 0u);     // -0.0 + 0.0 = +0.0
+            src[i] = make_key(score[i], mask[i], st);
         }
         if (st) atomicOr(&s_status, st);
     }
@@ -140,7 +81,8 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
             dt += __shfl_xor(dt, 1);
             dt += __shfl_xor(dt, 2);
             if (dt == n && (tid & 3) == 0) s_skip = 1;           // every key has this digit: the pass would move nothing
-            uint32_t ex = block_exclusive_scan(sum, wsum);
+            uint32_t all;
+            uint32_t ex = block_exclusive_scan<WAVES>(sum, wsum, all);
 #pragma unroll
             for (int k = 0; k < 4; ++k) { hist[(w0 + k) * RADIX + d] = ex; ex += h[k]; }
         }
@@ -160,13 +102,7 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
                 for (int u = 0; u < UNROLL; ++u) {
                     if (base + u * 64 >= c1) break;              // wave-uniform
                     const uint32_t dg = (key[u] >> shift) & 255u;
-                    uint64_t m = __ballot(valid[u]);
-#pragma unroll
-                    for (int b = 0; b < 8; ++b) {
-                        const bool bit = (dg >> b) & 1u;
-                        const uint64_t bal = __ballot(valid[u] && bit);
-                        m &= bit ? bal : ~bal;
-                    }                                            // m: the valid lanes of this group with my digit
+                    const uint64_t m = digit_peers(dg, valid[u]);    // the valid lanes of this group with my digit
                     const uint32_t rank = __popcll(m & lt), cnt = __popcll(m);
                     uint32_t pos = 0;
                     if (valid[u]) pos = wh[dg] + rank;
@@ -198,8 +134,8 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
         if (lane == 0) { wtot_p[wave] = cp; wtot_b[wave] = cb; }
         __syncthreads();
         uint32_t carry_p, carry_b;
-        wave_carry(wtot_p, wave, carry_p, P);
-        wave_carry(wtot_b, wave, carry_b, R);
+        wave_carry<WAVES>(wtot_p, wave, carry_p, P);
+        wave_carry<WAVES>(wtot_b, wave, carry_b, R);
         for (uint32_t base = c0; base < c1; base += 64) {
             const uint32_t i = base + lane;
             const bool valid = i < c1;
@@ -233,7 +169,7 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
         }
         if (lane == 0) wtot_p[wave] = ck;                        // free since the barrier that ended step 3
         __syncthreads();
-        wave_carry(wtot_p, wave, carry_k, K);
+        wave_carry<WAVES>(wtot_p, wave, carry_k, K);
     }
     unsigned long long acc = 0;
     for (uint32_t base = q0; base < q1; base += 64) {
@@ -295,12 +231,8 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
             if (want_ap && pr != 0) part += ((double)pr / dP) * ((double)tps / (double)cnt);
             if (dice_better(tps, cnt, r, btp, bc, br, P)) { btp = tps; bc = cnt; br = r; }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            part += __shfl_xor(part, off);
-            const uint32_t otp = __shfl_xor(btp, off), oc = __shfl_xor(bc, off), orr = __shfl_xor(br, off);
-            if (dice_better(otp, oc, orr, btp, bc, br, P)) { btp = otp; bc = oc; br = orr; }
-        }
+        part = tree_add<64>(part);
+        tree_dice<64>(btp, bc, br, P);
         if (lane == 0) { wap[wave] = part; wbt[wave] = btp; wbc[wave] = bc; wbr[wave] = br; }
         __syncthreads();
         if (wave == 0) {
@@ -308,12 +240,8 @@ __global__ __launch_bounds__(THREADS) void roc_auc_kernel(anoddpm_roc_args a, in
             btp = lane < WAVES ? wbt[lane] : 0u;
             bc = lane < WAVES ? wbc[lane] : 1u;
             br = lane < WAVES ? wbr[lane] : 0u;
-#pragma unroll
-            for (int off = WAVES / 2; off > 0; off >>= 1) {
-                part += __shfl_xor(part, off);
-                const uint32_t otp = __shfl_xor(btp, off), oc = __shfl_xor(bc, off), orr = __shfl_xor(br, off);
-                if (dice_better(otp, oc, orr, btp, bc, br, P)) { btp = otp; bc = oc; br = orr; }
-            }
+            part = tree_add<WAVES>(part);
+            tree_dice<WAVES>(btp, bc, br, P);
             if (lane == 0) {
                 if (want_ap) a.ap[seg] = P == 0 ? (double)NAN : (P == n ? 1.0 : part);
                 if (want_best) {

@@ -32,6 +32,15 @@ ties to the highest threshold -- with that threshold and its `tp` / `fp`, both w
 point of the curve as integer counts, `PR_curve` on device tensors sklearn's `(precision, recall, thresholds)` triple bit for bit.
 A segment without positives has AP = NaN and best Dice = NaN (sklearn: AP 0.0 after a warning); one without negatives has AP = 1.0.
 
+One curve pooled over a whole test set (detection.py:538-643 `roc_data`: mask and squared error of every scored slice, one
+`ROC_AUC` call on the lot; 22 volumes x 4 slices x 256^2 = 5 767 168 pixels with `iterateKnown_restricted`).  One workgroup per
+segment is the right shape for the maps of a sweep and leaves all but one compute unit idle on such a segment:
+`anoddpm_roc_auc_wide` (csrc/roc_wide.hip) sorts and walks ONE segment with the whole chip, as 16 to 18 launches with one workgroup
+per tile of keys, and writes the same bits.  `_roc_launch` takes it for a single segment of at least `ROC_WIDE_MIN_N` elements
+(environment `ANODDPM_ROC_WIDE_MIN_N`), so nothing the functions above return changes.  `PooledCurves` collects the maps of a
+run in two preallocated device buffers without a host synchronisation and scores the pooled segment; `ROC_AUC` and `PR_curve`
+also take a list of device tensors on each side, meaning the pooled segment of all of them.
+
 Post-processing (the reference has none: it scores the raw squared error).  Published brain-MRI anomaly-segmentation pipelines
 median-filter the residual, restrict it to an eroded brain mask and drop tiny components from the binary prediction before they
 report AP and Dice.  `median_filter` (scipy.ndimage.median_filter, windows 3 / 5 / 7, reflect border), `erode_mask`
@@ -71,6 +80,7 @@ settings of a sweep and puts row j into record j as device tensors (None where t
 The individual functions accept the reference's arguments; they use the fused pass when handed device tensors of
 the shapes the reference passes and raise `AnoddpmError` otherwise (no CPU path)."""
 import ctypes
+import os
 
 import torch
 
@@ -78,7 +88,7 @@ from . import _lib
 from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs, ErodeArgs, GaussArgs, MapScoresArgs, MedianArgs, ProArgs, RocArgs, SsimArgs,
                    SurfaceArgs, check, current_stream, lib)
 
-__all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "ssim", "median_filter", "erode_mask",
+__all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "PooledCurves", "ssim", "median_filter", "erode_mask",
            "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "aupro", "pro_points", "AUPRO", "distance_transform",
            "surface_distance", "HD95", "anomaly_metrics_surface", "gaussian_filter", "image_scores", "image_auc", "anomaly_metrics_image", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
@@ -207,11 +217,20 @@ def _segments(x, S, name):
     return x, n, x.stride(0)
 
 
-def _roc_launch(mask, score, batched, curve, pr=False):
+_ROC_WIDE_NEVER = 1 << 31                                            # no segment is that long
+# A single segment of at least this many elements is scored by the whole chip (anoddpm_roc_auc_wide); the outputs have the same
+# bits.  65536 is the smallest measured power of two from which, at every larger measured size, the slowest wide repetition was
+# below the fastest one-workgroup repetition (profiles/roc_wide_ab.txt); 2147483648 switches the path off.
+ROC_WIDE_MIN_N = int(os.environ.get("ANODDPM_ROC_WIDE_MIN_N", "") or 65536)
+
+
+def _roc_launch(mask, score, batched, curve, pr=False, wide=None, tile=None):
     """One `anoddpm_roc_auc` launch.  score: [S, ...] when batched, else one segment; mask: like score, or the shape of one
     segment (one mask shared by every segment).  `pr` adds the average precision and the best Dice (`ap`, `best_dice`,
     `best_threshold`, `best_counts`) and makes `curve` every run of equal score instead of the points sklearn's roc_curve keeps.
-    Returns a dict of device tensors; nothing is copied to the host."""
+    `wide`: score the segments one after another with the whole chip (`anoddpm_roc_auc_wide`, `tile` keys per workgroup; None:
+    the library's choice); None takes that path for one segment of at least `ROC_WIDE_MIN_N` elements.  Both paths write the same
+    bits; `path` says which one ran ("wide" / "workgroup").  Returns a dict of device tensors; nothing is copied to the host."""
     if not isinstance(score, torch.Tensor) or not isinstance(mask, torch.Tensor):
         raise TypeError("roc: mask and score must be device tensors")
     S = score.shape[0] if batched else 1
@@ -228,9 +247,11 @@ def _roc_launch(mask, score, batched, curve, pr=False):
     if mk.device != sc.device:
         raise ValueError("roc: mask and score are on different devices")
     dev = sc.device
+    if wide is None:
+        wide = S == 1 and n >= ROC_WIDE_MIN_N
     out = {"auc": torch.empty((S,), dtype=torch.float64, device=dev),
            "counts": torch.empty((S, 4), dtype=torch.int64, device=dev),
-           "status": torch.empty((S,), dtype=torch.int32, device=dev), "n": n}
+           "status": torch.empty((S,), dtype=torch.int32, device=dev), "n": n, "path": "wide" if wide else "workgroup"}
     a = RocArgs()
     a.score, a.mask = sc.data_ptr(), mk.data_ptr()
     a.auc, a.counts, a.status = out["auc"].data_ptr(), out["counts"].data_ptr(), out["status"].data_ptr()
@@ -245,6 +266,17 @@ def _roc_launch(mask, score, batched, curve, pr=False):
         out["best_counts"] = torch.empty((S, 2), dtype=torch.int64, device=dev)
         a.ap, a.best_dice = out["ap"].data_ptr(), out["best_dice"].data_ptr()
         a.best_thr, a.best_counts = out["best_threshold"].data_ptr(), out["best_counts"].data_ptr()
+    if wide:
+        tile = 0 if tile is None else int(tile)
+        nbytes = lib().anoddpm_roc_wide_workspace_bytes(S, n, tile)
+        if nbytes < 0:
+            raise ValueError(f"roc: segment length {n} is outside [1, 2^31), or tile {tile} is not a multiple of 256 that cuts it into "
+                             f"at most {_lib.ROC_WIDE_MAX_TILES} tiles")
+        ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+        with torch.cuda.device(dev):
+            check(lib().anoddpm_roc_auc_wide(ctypes.byref(a), tile, current_stream()), "roc_auc_wide")
+        return out
     _launch("roc_auc", a, dev, (lib().anoddpm_roc_workspace_bytes(S, n), torch.int32, f"roc: segment length {n} is outside [1, 2^31)"))
     return out
 
@@ -1121,10 +1153,83 @@ def FPR(real_mask, recon_mask):
     return (c[4] / (c[4] + c[6] + 1e-6)).float()
 
 
+def _pooled(real_mask, square_error, what):
+    """Lists / tuples of device tensors on both sides -> the pooled segment of all of them (mask, score), else None."""
+    if not isinstance(real_mask, (list, tuple)) and not isinstance(square_error, (list, tuple)):
+        return None
+    if not (isinstance(real_mask, (list, tuple)) and isinstance(square_error, (list, tuple))) or len(real_mask) != len(square_error) or not real_mask:
+        raise TypeError(f"{what}: a pooled call takes two non-empty lists of device tensors of the same length")
+    for x in (*real_mask, *square_error):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise TypeError(f"{what}: a pooled call takes device tensors only")
+    pool = PooledCurves(sum(s.numel() for s in square_error), device=square_error[0].device)
+    for m, s in zip(real_mask, square_error):
+        pool.add(m, s)
+    return pool._mask, pool._score
+
+
+class PooledCurves:
+    """The masks and scores of a run collected into ONE segment -- the curve pooled over a whole test set (detection.py:538-643
+    `roc_data`) -- in two preallocated fp32 device buffers of `capacity` pixels.  `add(mask, score)` appends device tensors of
+    equal `numel`, or one mask plane shared by several score planes (the mask is written out once per plane), without a host
+    synchronisation; it raises ValueError, from the count kept on the host, when the buffers would overflow.  `len()` is the
+    number of pixels held, `reset()` empties the pool.  `scores()` is the dict `curve_scores` returns for the pooled segment
+    (S = 1, device tensors, no synchronisation), `roc_curve()` / `pr_curve()` what `ROC_AUC` / `PR_curve` return for it."""
+
+    def __init__(self, capacity, device=None):
+        capacity = int(capacity)
+        if capacity < 1 or capacity >= _ROC_WIDE_NEVER:
+            raise ValueError(f"PooledCurves: capacity must be in [1, 2^31), got {capacity}")
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("PooledCurves: the buffers live on the device")
+        self._mask = torch.empty((capacity,), dtype=torch.float32, device=device)
+        self._score = torch.empty((capacity,), dtype=torch.float32, device=device)
+        self._n = 0
+
+    capacity = property(lambda self: self._mask.numel())
+
+    def __len__(self):
+        return self._n
+
+    def reset(self):
+        self._n = 0
+
+    def add(self, mask, score):
+        if not isinstance(mask, torch.Tensor) or not isinstance(score, torch.Tensor) or not mask.is_cuda or not score.is_cuda:
+            raise TypeError("PooledCurves.add: mask and score must be device tensors")
+        k, km = score.numel(), mask.numel()
+        if k == 0 or km == 0 or k % km != 0:
+            raise ValueError(f"PooledCurves.add: mask of {km} elements does not match score {tuple(score.shape)}")
+        if self._n + k > self.capacity:
+            raise ValueError(f"PooledCurves.add: {self._n} + {k} pixels exceed the capacity {self.capacity}")
+        self._score[self._n:self._n + k].copy_(score.reshape(-1))
+        self._mask[self._n:self._n + k].view(k // km, km).copy_(mask.reshape(1, km).expand(k // km, km))
+        self._n += k
+
+    def _segment(self, what):
+        if self._n == 0:
+            raise ValueError(f"PooledCurves.{what}: the pool is empty")
+        return self._mask[:self._n], self._score[:self._n]
+
+    def scores(self):
+        return curve_scores(*self._segment("scores"), batched=False)
+
+    def roc_curve(self):
+        return ROC_AUC(*self._segment("roc_curve"))
+
+    def pr_curve(self):
+        return PR_curve(*self._segment("pr_curve"))
+
+
 def ROC_AUC(real_mask, square_error):
     """evaluation.py:78-82.  Device tensors: the native sort (`roc_points` of the flattened inputs); the host prepends the
     `(0, 0, inf)` point and divides the integer counts in fp64, which gives sklearn's `(fpr, tpr, thresholds)` bit for bit
-    (NaN arrays when a class is empty).  Host inputs (numpy arrays, CPU tensors): sklearn, as upstream."""
+    (NaN arrays when a class is empty).  A list or tuple of device tensors on each side is the pooled segment of all of them.
+    Host inputs (numpy arrays, CPU tensors): sklearn, as upstream."""
+    pooled = _pooled(real_mask, square_error, "ROC_AUC")
+    if pooled is not None:
+        real_mask, square_error = pooled
     if isinstance(real_mask, torch.Tensor) and isinstance(square_error, torch.Tensor) and real_mask.is_cuda and square_error.is_cuda:
         import numpy as np
         p = roc_points(real_mask, square_error, batched=False)[0]
@@ -1144,8 +1249,11 @@ def PR_curve(real_mask, square_error):
     """sklearn's `precision_recall_curve(real_mask.flatten(), square_error.flatten())`: `(precision, recall, thresholds)` in
     ascending threshold order with the final `(1, 0)` point appended.  Device tensors: the native sort (`pr_points` of the
     flattened inputs); the host divides the integer counts in fp64, which gives sklearn's arrays bit for bit.  Recall is all
-    ones when the mask has no positive, as sklearn's is; its warning is not re-issued.  Host inputs (numpy arrays, CPU
-    tensors): sklearn."""
+    ones when the mask has no positive, as sklearn's is; its warning is not re-issued.  A list or tuple of device tensors on
+    each side is the pooled segment of all of them.  Host inputs (numpy arrays, CPU tensors): sklearn."""
+    pooled = _pooled(real_mask, square_error, "PR_curve")
+    if pooled is not None:
+        real_mask, square_error = pooled
     if isinstance(real_mask, torch.Tensor) and isinstance(square_error, torch.Tensor) and real_mask.is_cuda and square_error.is_cuda:
         import numpy as np
         p = pr_points(real_mask, square_error, batched=False)[0]

@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 33
+#define ANODDPM_ABI_VERSION 34
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -662,6 +662,23 @@ typedef struct anoddpm_roc_args {
 
 int anoddpm_roc_auc(const anoddpm_roc_args *a, void *stream);
 int64_t anoddpm_roc_workspace_bytes(int32_t S, int64_t n);   /* HOST function; -1 for S < 1, n < 1 or n >= 2^31 */
+
+/* The same scores with every segment sorted by the whole chip (csrc/roc_wide.hip): for one long segment -- the curve pooled over a
+ * whole test set, detection.py:538-643 roc_data -- where anoddpm_roc_auc keeps 255 of 256 compute units idle.  Same argument
+ * struct, every field with the meaning above (strides, shared mask, all optional outputs); the S segments are processed one after
+ * another on `stream`, each as a sequence of 16 to 18 launches with one workgroup per tile of `tile` keys, and share ONE segment's
+ * workspace.  A launch boundary is the only ordering between workgroups.
+ *   tile       keys per workgroup: a multiple of 256 from 256 up, or 0 for the library's choice.  One workgroup scans the
+ *              [256][tiles] counter table of a sort pass, so n may be cut into at most ANODDPM_ROC_WIDE_MAX_TILES tiles: an
+ *              explicit tile that needs more is refused; tile 0 is 4096 keys and grows with n so that every n < 2^31 is accepted
+ *   workspace  [dev] anoddpm_roc_wide_workspace_bytes(S, n, tile) bytes, 16-byte aligned; about 20 n bytes (keys, run records and
+ *              one fp64 average-precision term per run) whatever S is; never smaller for a larger n at the same tile
+ * For every accepted input every output has the bits anoddpm_roc_auc writes for the same arguments, the status word of a segment
+ * that breaks the precondition included (its other outputs stay not meaningful).  Argument checks as anoddpm_roc_auc, made before
+ * anything is launched. */
+#define ANODDPM_ROC_WIDE_MAX_TILES 2048
+int anoddpm_roc_auc_wide(const anoddpm_roc_args *a, int32_t tile, void *stream);
+int64_t anoddpm_roc_wide_workspace_bytes(int32_t S, int64_t n, int32_t tile);   /* HOST function; -1 where the call would be refused */
 
 /* ------------------------------------------------------------------ mean structural similarity (SSIM) of image pairs
  * Replaces skimage.metrics.structural_similarity as the reference calls it (evaluation.py:46-47 SSIM; detection.py:241-246,
