@@ -113,6 +113,92 @@ __global__ __launch_bounds__(256) void resample_pass_kernel(const float *__restr
     }
 }
 
+// AnomalousMRIDataset's per-slice work (dataset.py:646-790) fused: plane gather, CenterCrop((crop_h, crop_w)) with its zero
+// padding, both passes of PIL's resample, Normalize and the mask's `> 0` -- the arithmetic of resample_pass_kernel, tap for tap.
+// grid: x = output tile (ANO_TH rows x ANO_TW columns), y = item, z = 0 image / 1 mask.  A workgroup walks the cropped rows its
+// tile's vertical taps reach in chunks of ANO_CH: the horizontal pass of a chunk goes to LDS as fp32 (the rounding PIL's
+// intermediate image has), then every thread adds the chunk's share of its ANO_RPT output rows' vertical taps into fp64 registers.
+// Chunks ascend and the taps inside one ascend, so each sum runs in the order of resample_pass_kernel whatever the scale -- a
+// 1 x 1 output streams the whole plane through the same 8 KB.  Reads of the plane are bounds-checked by the crop itself.
+constexpr int ANO_TW = 64, ANO_TH = 16, ANO_CH = 32, ANO_RPT = ANO_TH / 4;
+
+__global__ __launch_bounds__(256) void ano_slices_kernel(const anoddpm_ano_slices_args a)
+{
+    __shared__ float hrow[ANO_CH * ANO_TW];
+    const int item = blockIdx.y;
+    const bool is_mask = blockIdx.z != 0;
+    const float *vol = is_mask ? a.masks[item] : a.vols[item];
+    const float *plane = vol ? vol + (long long)a.slice_idx[item] * a.R * a.C : nullptr;
+    const int tiles_x = (a.out_w + ANO_TW - 1) / ANO_TW;
+    const int ox0 = (int)(blockIdx.x % tiles_x) * ANO_TW, oy0 = (int)(blockIdx.x / tiles_x) * ANO_TH;
+    const int tw = min(ANO_TW, a.out_w - ox0), th = min(ANO_TH, a.out_h - oy0);
+    const int c = threadIdx.x % ANO_TW;
+    const int g = __builtin_amdgcn_readfirstlane(threadIdx.x / ANO_TW);  // a wave is one g: said so, the ky reads below are scalar loads
+
+    int rbeg = a.crop_h, rend = 0;                                       // cropped rows the tile's vertical taps reach
+#pragma unroll
+    for (int j = 0; j < ANO_TH; ++j) {                                   // (rows past the tile repeat its last one: no branch, loads batched)
+        const int o = min(oy0 + j, a.out_h - 1);
+        const int k0 = a.ky_min[o];
+        rbeg = min(rbeg, k0);
+        rend = max(rend, k0 + a.ky_n[o]);
+    }
+    rbeg = max(rbeg, 0);
+    rend = min(rend, a.crop_h);
+
+    int k0y[ANO_RPT], k1y[ANO_RPT];
+    double acc[ANO_RPT];
+#pragma unroll
+    for (int j = 0; j < ANO_RPT; ++j) {
+        const int o = oy0 + g + 4 * j;
+        const bool live = g + 4 * j < th;
+        k0y[j] = live ? a.ky_min[o] : 0;
+        k1y[j] = live ? k0y[j] + a.ky_n[o] : 0;
+        acc[j] = 0.0;
+    }
+
+    for (int r0 = rbeg; r0 < rend; r0 += ANO_CH) {
+        const int cnt = min(ANO_CH, rend - r0);
+        for (int i = threadIdx.x; i < cnt * tw; i += 256) {              // horizontal pass of rows [r0, r0 + cnt), columns of the tile
+            const int rr = i / tw, cc = i - rr * tw;
+            const int o = ox0 + cc;
+            const int k0 = a.kx_min[o], kn = a.kx_n[o];
+            const double *k = a.kx + (long long)o * a.kmax_x;
+            const int sy = r0 + rr + a.crop_top;
+            const bool row_in = plane && sy >= 0 && sy < a.R;
+            const float *src = plane + (long long)sy * a.C;
+            double ss = 0.0;
+            for (int t = 0; t < kn; ++t) {
+                const int sx = k0 + t + a.crop_left;
+                const float p = (row_in && sx >= 0 && sx < a.C) ? src[sx] : 0.f;
+                ss += (double)p * k[t];
+            }
+            hrow[rr * ANO_TW + cc] = (float)ss;
+        }
+        __syncthreads();
+        if (c < tw) {
+#pragma unroll
+            for (int j = 0; j < ANO_RPT; ++j) {
+                const int lo = max(k0y[j], r0), hi = min(k1y[j], r0 + cnt);
+                const double *k = a.ky + (long long)(oy0 + g + 4 * j) * a.kmax_y - k0y[j];
+                for (int r = lo; r < hi; ++r) acc[j] += (double)hrow[(r - r0) * ANO_TW + c] * k[r];
+            }
+        }
+        __syncthreads();
+    }
+
+    if (c < tw) {
+        float *out = (is_mask ? a.mask : a.img) + ((long long)item * a.out_h + oy0) * a.out_w + ox0 + c;
+#pragma unroll
+        for (int j = 0; j < ANO_RPT; ++j) {
+            if (g + 4 * j >= th) continue;
+            float v = ((float)acc[j] - a.mean) / a.std;
+            if (is_mask) v = v > 0.f ? 1.f : 0.f;
+            out[(long long)(g + 4 * j) * a.out_w] = v;
+        }
+    }
+}
+
 }  // namespace
 
 using namespace anoddpm;
@@ -157,4 +243,18 @@ extern "C" int anoddpm_resize_bilinear_pil(const anoddpm_resize_args *a, void *s
         hipLaunchKernelGGL((resample_pass_kernel<true, false>), dim3((n2 + 255) / 256, a->B), dim3(256), 0, s, a->tmp, a->out, a->ky, a->ky_min, a->ky_n,
                            a->kmax_y, a->in_h, a->out_w, a->out_h, a->out_w, 0.f, 1.f);
     return check_launch("resize_bilinear_pil");
+}
+
+extern "C" int anoddpm_ano_slices(const anoddpm_ano_slices_args *a, void *stream)
+{
+    ANODDPM_REQUIRE(a && a->vols && a->slice_idx && a->img && a->kx && a->kx_min && a->kx_n && a->ky && a->ky_min && a->ky_n, "ano_slices: null pointer");
+    ANODDPM_REQUIRE(!a->masks || a->mask, "ano_slices: mask volumes given without a mask output");
+    ANODDPM_REQUIRE(a->n >= 1 && a->n <= 65535, "ano_slices: need 1 <= n <= 65535");
+    ANODDPM_REQUIRE(a->R >= 1 && a->C >= 1 && a->crop_h >= 1 && a->crop_w >= 1 && a->out_h >= 1 && a->out_w >= 1 && a->kmax_x >= 1 && a->kmax_y >= 1,
+                    "ano_slices: bad sizes");
+    ANODDPM_REQUIRE(a->std != 0.0f, "ano_slices: std must be non-zero");
+    const long long tiles = (long long)((a->out_w + ANO_TW - 1) / ANO_TW) * ((a->out_h + ANO_TH - 1) / ANO_TH);
+    ANODDPM_REQUIRE(tiles <= 2147483647LL, "ano_slices: output too large");
+    hipLaunchKernelGGL(ano_slices_kernel, dim3((unsigned)tiles, a->n, a->masks ? 2 : 1), dim3(256), 0, as_stream(stream), *a);
+    return check_launch("ano_slices");
 }

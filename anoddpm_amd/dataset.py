@@ -10,6 +10,9 @@ MI355X-first: every volume is uploaded ONCE and stays resident in HBM (a normali
 set is ~5 GB of the 288 GB), a slice never touches the host again, and a whole batch costs three launches (`get_batch`).
 A user-supplied `transform` callable is honoured the reference's way (it receives the numpy slice on the host).
 NIfTI input needs nibabel exactly like upstream; without it only the `.npy` cache path works.
+
+`AnomalousMRIDataset` -- the reference's test-set loader (dataset.py:646-790) the same way: volumes and masks resident, one launch
+per sample for all its slices, image and mask (anoddpm_ano_slices); the slice table comes from the caller or `slices.json`.
 """
 import ctypes
 import os
@@ -19,10 +22,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MriSliceArgs, ResizeArgs, check, current_stream, lib
+from ._lib import AnoSlicesArgs, MriSliceArgs, ResizeArgs, check, current_stream, lib
 
-__all__ = ["MRIDataset", "normalise_volume", "resize_coeffs", "center_crop_geometry", "affine_fixed_coeffs", "cycle",
-           "init_dataset_loader"]
+__all__ = ["MRIDataset", "AnomalousMRIDataset", "normalise_volume", "resize_coeffs", "center_crop_geometry", "center_crop_geometry_hw",
+           "affine_fixed_coeffs", "cycle", "init_dataset_loader"]
 
 CROP = 235
 
@@ -61,6 +64,18 @@ def center_crop_geometry(h, w, crop):
     pad_bottom = (crop - h + 1) // 2 if crop > h else 0
     H, W = h + pad_top + pad_bottom, w + pad_left + pad_right
     return pad_left, pad_top, int(round((H - crop) / 2.0)), int(round((W - crop) / 2.0))
+
+
+def center_crop_geometry_hw(h, w, crop_h, crop_w):
+    """torchvision center_crop to a (crop_h, crop_w) window: (pad_left, pad_top, crop_top, crop_left).  Zero padding of
+    (c - s) // 2 before and (c - s + 1) // 2 after where the image is smaller, then the window at int(round((S - c) / 2.0)) of the
+    padded size S: Python's round, half to even (a difference of 1 gives 0, of 3 gives 2)."""
+    pad_left = (crop_w - w) // 2 if crop_w > w else 0
+    pad_top = (crop_h - h) // 2 if crop_h > h else 0
+    pad_right = (crop_w - w + 1) // 2 if crop_w > w else 0
+    pad_bottom = (crop_h - h + 1) // 2 if crop_h > h else 0
+    H, W = h + pad_top + pad_bottom, w + pad_left + pad_right
+    return pad_left, pad_top, int(round((H - crop_h) / 2.0)), int(round((W - crop_w) / 2.0))
 
 
 def affine_fixed_coeffs(w, h, angle, translate):
@@ -217,6 +232,219 @@ class MRIDataset(torch.utils.data.Dataset):
             return {"image": self.transform(image), "filenames": name}
         out, names = self.get_batch([idx])
         return {"image": out[0], "filenames": names[0]}
+
+
+ANO_CROP = (175, 240)
+SLICE_SELECTIONS = ("random", "iterateKnown", "iterateKnown_restricted", "iterateUnknown")
+
+
+def _slice_table(ROOT_DIR, slices):
+    """id -> range from the caller's mapping or {ROOT_DIR}/slices.json; values are ranges or (start, stop) pairs."""
+    if slices is None:
+        path = os.path.join(ROOT_DIR, "slices.json")
+        if not os.path.exists(path):
+            raise _lib.AnoddpmError(
+                f"AnomalousMRIDataset needs the tumour slice range of every volume: pass slices={{id: range(start, stop)}} (or "
+                f"(start, stop) pairs), or put them into {path} as {{\"id\": [start, stop]}}; upstream's table is at dataset.py:675-682")
+        import json
+        with open(path) as f:
+            slices = json.load(f)
+    if not hasattr(slices, "items") or len(slices) == 0:
+        raise _lib.AnoddpmError("AnomalousMRIDataset: slices must be a non-empty mapping id -> range or (start, stop)")
+    table = {}
+    for name, r in slices.items():
+        if not isinstance(r, range):
+            try:
+                start, stop = (int(v) for v in r)
+            except (TypeError, ValueError) as e:
+                raise _lib.AnoddpmError(f"AnomalousMRIDataset: slices[{name!r}] = {r!r} is neither a range nor (start, stop)") from e
+            r = range(start, stop)
+        if r.step != 1 or r.start < 0 or r.stop < r.start:
+            raise _lib.AnoddpmError(f"AnomalousMRIDataset: slices[{name!r}] = {r!r} is not an ascending unit-step range")
+        table[str(name)] = r
+    return table
+
+
+class AnomalousMRIDataset(torch.utils.data.Dataset):
+    """Anomalous MRI dataset (dataset.py:646-790): tumour volumes `{ROOT}/raw_cleaned/{id}.npy` (`raw/` with cleaned=False) and
+    masks `{ROOT}/mask/{id}.npy`, sliced along axis 0, through CenterCrop((175, 240)) -> Resize(img_size, BILINEAR) -> ToTensor ->
+    Normalize(0.5, 0.5); the mask goes through the same transform and is then `> 0`.
+
+    Kept from the reference: the file layout (`-resized.npy` variants with resized=True where they exist), `filenames`, `slices`,
+    `img_size`, `slice_selection`, `__len__`, the four modes with their index rules and the sample dict (`"slices"` has upstream's
+    type per mode).  Not kept: the slice table itself -- it comes from `slices=` or `{ROOT}/slices.json` -- and the NIfTI branch
+    (upstream's names always end in .npy, so its nib.load cannot succeed): a missing file raises AnoddpmError naming the path.
+
+    MI355X-first: every volume and mask is uploaded once (astype(float32)) and stays in HBM; one `__getitem__` of any mode costs one
+    upload of its pointers and slice indices and ONE launch (anoddpm_ano_slices) for all slices, image and mask.  `image` / `mask`
+    are [n, H, W] device tensors ([1, H, W] for "random").  A user `transform` is honoured upstream's way (numpy slice in, host)."""
+
+    def __init__(self, ROOT_DIR, transform=None, img_size=(32, 32), slice_selection="random", resized=False, cleaned=True, device=None,
+                 slices=None):
+        if slice_selection not in SLICE_SELECTIONS:
+            raise ValueError(f"slice_selection {slice_selection!r} is none of {SLICE_SELECTIONS}")
+        self.transform = transform
+        self.img_size = tuple(int(v) for v in img_size)
+        self.resized = resized
+        self.slices = _slice_table(ROOT_DIR, slices)
+        self._ids = list(self.slices)
+        self.filenames = [f"{ROOT_DIR}/{'raw_cleaned' if cleaned else 'raw'}/{name}.npy" for name in self._ids]
+        self.ROOT_DIR = ROOT_DIR
+        self.slice_selection = slice_selection
+        if device is None:                                                   # as MRIDataset: the calling process's current device
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cuda:0")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self._vols = {}
+        self._coef = {}
+
+    def __len__(self):
+        return len(self.filenames)
+
+    # ---- volumes and masks: one upload each, resident afterwards
+    def _resident(self, path):
+        v = self._vols.get(path)
+        if v is None:
+            if not os.path.exists(path):
+                raise _lib.AnoddpmError(f"{path} is missing (AnomalousMRIDataset reads .npy volumes only)")
+            v = torch.from_numpy(np.ascontiguousarray(np.load(path), dtype=np.float32)).to(self.device)
+            if v.dim() != 3:
+                raise ValueError(f"{path}: expected a 3-D volume, got shape {tuple(v.shape)}")
+            self._vols[path] = v
+        return v
+
+    def _volume(self, idx):
+        path = self.filenames[idx]
+        alt = f"{path[:-4]}-resized.npy"
+        return self._resident(alt if self.resized and os.path.exists(alt) else path)
+
+    def _mask(self, idx):
+        path = f"{self.ROOT_DIR}/mask/{self._ids[idx]}.npy"
+        alt = f"{path[:-4]}-resized.npy"
+        m = self._resident(alt if self.resized and os.path.exists(alt) else path)
+        if m.shape != self._volume(idx).shape:
+            raise ValueError(f"{path}: mask shape {tuple(m.shape)} is not the volume's {tuple(self._volume(idx).shape)}")
+        return m
+
+    def _tables(self):
+        key = self.img_size
+        t = self._coef.get(key)
+        if t is None:
+            kx, xmin, xn = resize_coeffs(ANO_CROP[1], self.img_size[1])
+            ky, ymin, yn = resize_coeffs(ANO_CROP[0], self.img_size[0])
+            up = lambda a: torch.from_numpy(a).to(self.device)
+            t = self._coef[key] = (up(kx), up(xmin), up(xn), kx.shape[1], up(ky), up(ymin), up(yn), ky.shape[1])
+        return t
+
+    def _launch(self, vols, masks, slice_idx):
+        """One upload (pointers and slice indices in one buffer) and one launch: vols / masks are lists of resident volumes of one
+        plane shape, masks may be None.  -> (img [n,H,W], mask [n,H,W] or None)."""
+        n = len(vols)
+        R, C = int(vols[0].shape[1]), int(vols[0].shape[2])
+        for v in vols:
+            _lib.require_cuda(v, "AnomalousMRIDataset")
+        host = np.zeros(2 * n + (n + 1) // 2, dtype=np.int64)
+        host[:n] = [v.data_ptr() for v in vols]
+        if masks is not None:
+            host[n:2 * n] = [m.data_ptr() for m in masks]
+        host[2 * n:].view(np.int32)[:n] = slice_idx
+        with torch.cuda.device(self.device):                                 # launches go to THIS dataset's device and its stream
+            buf = torch.from_numpy(host).to(self.device)
+            kx, xmin, xn, kmx, ky, ymin, yn, kmy = self._tables()
+            H, W = self.img_size
+            img = torch.empty((n, H, W), dtype=torch.float32, device=self.device)
+            mask = torch.empty((n, H, W), dtype=torch.float32, device=self.device) if masks is not None else None
+            pl, pt, ct, cl = center_crop_geometry_hw(R, C, *ANO_CROP)
+            a = AnoSlicesArgs()
+            a.vols, a.masks, a.slice_idx = buf.data_ptr(), (buf.data_ptr() + 8 * n if masks is not None else None), buf.data_ptr() + 16 * n
+            a.img, a.mask = img.data_ptr(), (mask.data_ptr() if mask is not None else None)
+            a.kx, a.kx_min, a.kx_n, a.ky, a.ky_min, a.ky_n = kx.data_ptr(), xmin.data_ptr(), xn.data_ptr(), ky.data_ptr(), ymin.data_ptr(), yn.data_ptr()
+            a.n, a.R, a.C, a.crop_h, a.crop_w, a.crop_top, a.crop_left = n, R, C, ANO_CROP[0], ANO_CROP[1], ct - pt, cl - pl
+            a.out_h, a.out_w, a.kmax_x, a.kmax_y, a.mean, a.std = H, W, kmx, kmy, 0.5, 0.5
+            check(lib().anoddpm_ano_slices(ctypes.byref(a), current_stream()), "ano_slices")
+        return img, mask
+
+    def _items(self, pairs, with_mask):
+        """pairs: (volume index, slice index).  Checks the indices, then one launch."""
+        if len(pairs) == 0:
+            raise ValueError("AnomalousMRIDataset: no slices asked for")
+        vol_of = {i: self._volume(i) for i in dict.fromkeys(i for i, _ in pairs)}        # each volume looked up once, not once per slice
+        vols = [vol_of[i] for i, _ in pairs]
+        for (i, s), v in zip(pairs, vols):
+            if not 0 <= s < v.shape[0]:
+                raise IndexError(f"slice {s} is outside volume {self.filenames[i]} with {v.shape[0]} slices")
+        if any(v.shape[1:] != vols[0].shape[1:] for v in vol_of.values()):
+            raise ValueError("volumes of one batch must share their plane shape")
+        masks = None
+        if with_mask:
+            mask_of = {i: self._mask(i) for i in vol_of}
+            masks = [mask_of[i] for i, _ in pairs]
+        return self._launch(vols, masks, np.array([s for _, s in pairs], dtype=np.int32))
+
+    def _host_slices(self, idx, slice_indices, with_mask):
+        """The reference's loop for a user transform: the numpy slice goes in on the host, the results fill torch.empty(n, *img_size)."""
+        vol = self._volume(idx).cpu().numpy()
+        msk = self._mask(idx).cpu().numpy() if with_mask else None
+        out = torch.empty(len(slice_indices), *self.img_size)
+        out_mask = torch.empty(len(slice_indices), *self.img_size) if with_mask else None
+        for k, s in enumerate(slice_indices):
+            if not 0 <= s < vol.shape[0]:
+                raise IndexError(f"slice {s} is outside volume {self.filenames[idx]} with {vol.shape[0]} slices")
+            out[k, ...] = torch.as_tensor(self.transform(vol[s]))
+            if with_mask:
+                out_mask[k, ...] = torch.as_tensor(self.transform(msk[s]))
+        return out, ((out_mask > 0).float() if with_mask else None)
+
+    def get_slices(self, idx, slice_indices, with_mask=True):
+        """(image [n,H,W], mask [n,H,W] of 0/1 or None) of the listed slices of volume idx: the primitive of every mode."""
+        if torch.is_tensor(idx):
+            idx = idx.tolist()
+        slice_indices = [int(s) for s in slice_indices]
+        if self.transform is not None:
+            return self._host_slices(idx, slice_indices, with_mask)
+        return self._items([(idx, s) for s in slice_indices], with_mask)
+
+    def get_batch(self, indices):
+        """"random" over several volumes (which must share R and C) in one launch: {"image": [B,1,H,W], "slices": [B ints],
+        "filenames": [B names]}; one random.randint per index, in order."""
+        indices = [i.tolist() if torch.is_tensor(i) else i for i in indices]
+        draws = [random.randint(self.slices[self._ids[i]].start, self.slices[self._ids[i]].stop) for i in indices]
+        if self.transform is not None:
+            image = torch.stack([self._host_slices(i, [s], False)[0] for i, s in zip(indices, draws)])
+        else:
+            image = self._items(list(zip(indices, draws)), False)[0][:, None]
+        return {"image": image, "slices": draws, "filenames": [self.filenames[i] for i in indices]}
+
+    def __getitem__(self, idx):
+        if torch.is_tensor(idx):
+            idx = idx.tolist()
+        temp_range = self.slices[self._ids[idx]]
+        sample = {}
+        if self.slice_selection == "random":
+            slice_idx = random.randint(temp_range.start, temp_range.stop)    # :732, the stop is inclusive
+            if self.transform is not None:                                   # :733-735, the transform's result as it is
+                vol = self._volume(idx)
+                if not 0 <= slice_idx < vol.shape[0]:
+                    raise IndexError(f"slice {slice_idx} is outside volume {self.filenames[idx]} with {vol.shape[0]} slices")
+                image = self.transform(vol[slice_idx].cpu().numpy())
+            else:
+                image = self.get_slices(idx, [slice_idx], with_mask=False)[0]
+            sample["slices"] = slice_idx
+        elif self.slice_selection == "iterateKnown":
+            image, sample["mask"] = self.get_slices(idx, temp_range)
+            sample["slices"] = temp_range
+        elif self.slice_selection == "iterateKnown_restricted":
+            slices = np.linspace(temp_range.start + 5, temp_range.stop - 5, 4).astype(np.int32)      # :761
+            image, sample["mask"] = self.get_slices(idx, slices)
+            sample["slices"] = slices
+        else:                                                                # "iterateUnknown": the whole volume, no mask
+            n = int(self._volume(idx).shape[0])
+            image = self.get_slices(idx, range(n), with_mask=False)[0]
+            sample["slices"] = n
+        sample["image"] = image
+        sample["filenames"] = self.filenames[idx]
+        return sample
 
 
 def cycle(iterable):

@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 34
+#define ANODDPM_ABI_VERSION 35
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -1310,6 +1310,32 @@ typedef struct anoddpm_resize_args {
 } anoddpm_resize_args;
 
 int anoddpm_resize_bilinear_pil(const anoddpm_resize_args *a, void *stream);
+
+/* Anomalous test-set slices and their masks (AnomalousMRIDataset.__getitem__, dataset.py:646-790) in ONE launch: per item the plane
+ * vols[i][slice_idx[i]] of a resident fp32 volume [S_i][R][C] (axis 0 is sliced, planes are contiguous), torchvision
+ * CenterCrop((crop_h, crop_w)) with its zero padding, PIL Image.resize(BILINEAR) -- horizontal pass, then vertical pass, fp64
+ * sums in ascending tap order, an fp32 rounding after each pass, exactly as anoddpm_resize_bilinear_pil -- and Normalize:
+ *   img[i][oy][ox]  = (v - mean) / std
+ *   mask[i][oy][ox] = ((m - mean) / std > 0) ? 1.f : 0.f      the mask plane through the same transform, then `> 0` (:748-754)
+ * The cropped image is crop[y][x] = plane[y + crop_top][x + crop_left] where that lies inside the plane and 0 elsewhere; both
+ * offsets are signed (negative where the plane is smaller than the crop and torchvision pads).  Coefficient tables as in
+ * anoddpm_resize_args, for crop_w -> out_w (kx) and crop_h -> out_h (ky).  No intermediate goes to global memory.
+ * The caller guarantees 0 <= slice_idx[i] < S_i; a NULL entry of masks[] reads as a plane of zeros. */
+typedef struct anoddpm_ano_slices_args {
+    const float *const *vols;       /* [dev] n pointers to resident fp32 volumes [S_i][R][C] */
+    const float *const *masks;      /* [dev] n pointers to mask volumes of the same shapes, or NULL: no mask output */
+    const int32_t *slice_idx;       /* [dev] n */
+    float *img;                     /* [n][out_h][out_w] */
+    float *mask;                    /* [n][out_h][out_w]; required when masks is given, else unused */
+    const double *kx;               /* [out_w][kmax_x] */
+    const int32_t *kx_min, *kx_n;
+    const double *ky;               /* [out_h][kmax_y] */
+    const int32_t *ky_min, *ky_n;
+    int32_t n, R, C, crop_h, crop_w, crop_top, crop_left, out_h, out_w, kmax_x, kmax_y;
+    float mean, std;
+} anoddpm_ano_slices_args;
+
+int anoddpm_ano_slices(const anoddpm_ano_slices_args *a, void *stream);
 
 #ifdef __cplusplus
 }
