@@ -5,8 +5,36 @@
 
 namespace anoddpm {
 
+// a0 b0 + a1 b1 + a2 b2 in ONE evaluation order, whatever kernel the caller is compiled into.  With the sixths of the F(4x4,3x3)
+// matrix roughly one U in a hundred is, in exact arithmetic, a tie between two fp32 neighbours (a sum of three fp32 weights that is divisible
+// by 3, over 24), and the side the fp64 value falls on is decided by its last bit: left to the compiler's contraction the stand-alone
+// kernel, the batched kernel and the bf16 packer rounded some of these to different neighbours (18 of 73 728 values of a 64 x 32
+// weight differed between anoddpm_pack_weights and anoddpm_pack_batch).
+__device__ __forceinline__ double dot3(double a0, double b0, double a1, double b1, double a2, double b2)
+{
+    return __builtin_fma(a2, b2, __builtin_fma(a1, b1, a0 * b0));
+}
+
+// Row u of U = G g G^T of Winograd F(4x4,3x3) (the 6x3 G of interpolation points 0, +-1, +-2, inf) for the four input channels of a
+// quad: f[v][e], fp64 transform, rounded once to fp32.  The one statement of the transform: the fp32 layout (mode 2 below) and the
+// bf16 planes (winograd43b.hip) hold the same values.
+__device__ __forceinline__ void wino43_u_row(const double (&g)[4][3][3], int u, float (&f)[6][4])
+{
+    const double G6[6][3] = {{1.0 / 4, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                             {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
+    double t1[4][3];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int b2 = 0; b2 < 3; ++b2) t1[e][b2] = dot3(G6[u][0], g[e][0][b2], G6[u][1], g[e][1][b2], G6[u][2], g[e][2][b2]);
+#pragma unroll
+    for (int v = 0; v < 6; ++v)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[v][e] = (float)dot3(t1[e][0], G6[v][0], t1[e][1], G6[v][1], t1[e][2], G6[v][2]);
+}
+
 // OIHW 3x3 -> mode 0: direct [9][I/4][O][4]; mode 1: Winograd F(2x2,3x3) U = G g G^T [16][I/4][O][4]; mode 2: F(4x4,3x3)
-// [36][I/4][O][4] (fp64 like the host versions, unet.py:_pack_conv / _pack_wino / _pack_wino43).  bwd != 0 packs the data-gradient
+// [36][I/4][O][4] (fp64 like the host versions, tests/hipops.py:_pack_conv / _pack_wino / _pack_wino43).  bwd != 0 packs the data-gradient
 // weights W'[o=k][i=n][a][b] = w[n][k][2-a][2-b].  idx = one (o, input-channel quad).
 __device__ __forceinline__ void pack_conv3x3_item(const float *__restrict__ w, float *__restrict__ out, int N, int K, int mode, int bwd, int64_t idx)
 {
@@ -42,25 +70,13 @@ __device__ __forceinline__ void pack_conv3x3_item(const float *__restrict__ w, f
     float4 *dst = reinterpret_cast<float4 *>(out) + (int64_t)i4 * O + o;
     const int64_t plane = (int64_t)I4 * O;                           // float4 slots per position
     if (mode == 2) {
-        // Winograd F(4x4,3x3): U = G g G^T with the 6x3 G of interpolation points 0, +-1, +-2, inf; [36 xi = 6u+v][I/4][O][4]
-        const double G6[6][3] = {{1.0 / 4, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                 {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
+        // Winograd F(4x4,3x3): [36 xi = 6u+v][I/4][O][4]
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
-            double t1[4][3];
+            float f[6][4];
+            wino43_u_row(g, u, f);
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int b2 = 0; b2 < 3; ++b2) t1[e][b2] = G6[u][0] * g[e][0][b2] + G6[u][1] * g[e][1][b2] + G6[u][2] * g[e][2][b2];
-#pragma unroll
-            for (int v = 0; v < 6; ++v) {
-                float4 o4;
-                o4.x = (float)(t1[0][0] * G6[v][0] + t1[0][1] * G6[v][1] + t1[0][2] * G6[v][2]);
-                o4.y = (float)(t1[1][0] * G6[v][0] + t1[1][1] * G6[v][1] + t1[1][2] * G6[v][2]);
-                o4.z = (float)(t1[2][0] * G6[v][0] + t1[2][1] * G6[v][1] + t1[2][2] * G6[v][2]);
-                o4.w = (float)(t1[3][0] * G6[v][0] + t1[3][1] * G6[v][1] + t1[3][2] * G6[v][2]);
-                dst[(u * 6 + v) * plane] = o4;
-            }
+            for (int v = 0; v < 6; ++v) dst[(u * 6 + v) * plane] = make_float4(f[v][0], f[v][1], f[v][2], f[v][3]);
         }
     } else {
         const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};

@@ -278,8 +278,8 @@ __global__ __launch_bounds__(256) void wgrad_fold_tile_kernel(const anoddpm_wgra
 }
 
 // Weight packing for the 3x3 kernels on the device (training re-packs after every optimizer step): OIHW ->
-//   mode 0: direct layout  [9 taps][I/4][O][4]                    (unet.py:_pack_conv)
-//   mode 1: Winograd       [16 xi = 4u+v][I/4][O][4], U = G g G^T  (unet.py:_pack_wino; fp64 like the host version)
+//   mode 0: direct layout  [9 taps][I/4][O][4]                    (tests/hipops.py:_pack_conv)
+//   mode 1: Winograd       [16 xi = 4u+v][I/4][O][4], U = G g G^T  (tests/hipops.py:_pack_wino; fp64 like the host version)
 // bwd != 0 packs the data-gradient weights W'[o=k][i=n][a][b] = w[n][k][2-a][2-b].  Thread = (o, i).
 __global__ __launch_bounds__(256) void pack_conv3x3_kernel(const float *__restrict__ w, float *__restrict__ out,
                                                            int N, int K, int mode, int bwd)

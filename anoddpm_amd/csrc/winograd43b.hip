@@ -20,6 +20,7 @@
 // 36 x 6 MFMAs per wave | barrier; the raw patch of the next iteration is requested before the MFMA phase.  Weights: three bf16
 // planes [piece][pos][K/8][N][8] (pack kind 6), one 16-byte load per piece and position per lane through a register ring.
 #include "f43.h"
+#include "pack_items.h"
 
 using namespace anoddpm;
 
@@ -281,21 +282,14 @@ __global__ __launch_bounds__(256) void pack_wino43b_kernel(const float *__restri
 #pragma unroll
         for (int t = 0; t < 9; ++t) g[e][t / 3][t % 3] = (double)src[t];
     }
-    const double G6[6][3] = {{1.0 / 4, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                             {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
     const int64_t plane = (int64_t)36 * (K >> 3) * N * 8;           // bf16 elements per piece
 #pragma unroll
     for (int u = 0; u < 6; ++u) {
-        double t1[4][3];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int b2 = 0; b2 < 3; ++b2) t1[e][b2] = G6[u][0] * g[e][0][b2] + G6[u][1] * g[e][1][b2] + G6[u][2] * g[e][2][b2];
+        float fu[6][4];
+        anoddpm::wino43_u_row(g, u, fu);                            // the fp32 values of anoddpm_pack_weights kind 5, bit for bit
 #pragma unroll
         for (int v = 0; v < 6; ++v) {
-            float f[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) f[e] = (float)(t1[e][0] * G6[v][0] + t1[e][1] * G6[v][1] + t1[e][2] * G6[v][2]);
+            const float *f = fu[v];
             unsigned h01, m01, l01, h23, m23, l23;
             split3(f32x2{f[0], f[1]}, h01, m01, l01);
             split3(f32x2{f[2], f[3]}, h23, m23, l23);

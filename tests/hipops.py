@@ -436,7 +436,7 @@ def gn_silu_backward(srcs, da, gamma, beta, mean, rstd, *, act=1, a_mode=0, acc_
     Returns (dx list, dgamma, dbeta)."""
     from anoddpm_amd._lib import GnBwdArgs
     dev = srcs[0].device
-    da = da.clone()                 # the kernel may use da as scratch (act != 0, a_mode == 0): keep the caller's tensor intact
+    da = da.clone()                 # a copy, though the kernel takes da const and leaves it bit-identical (test_gpu_gn_bwd_elements.py)
     B, Hs, Ws, c0 = srcs[0].shape
     c1 = srcs[1].shape[3] if len(srcs) > 1 else 0
     C, P = c0 + c1, Hs * Ws
