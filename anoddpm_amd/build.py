@@ -35,6 +35,7 @@ SOURCES = {
     "roc.hip": ["-ffp-contract=off"],
     "roc_wide.hip": ["-ffp-contract=off"],
     "pro.hip": ["-ffp-contract=off"],
+    "pro_wide.hip": ["-ffp-contract=off"],
     "surface.hip": ["-ffp-contract=off"],
     "ssim.hip": ["-ffp-contract=off"],
     "postproc.hip": [],

@@ -20,9 +20,14 @@
 //      t, t + 1024, ... in that order, a halving tree folds the 64 partials of a wave and then the 16 wave sums (the order of
 //      roc.hip's average precision); AUPRO = sum / limit.
 // K is folded from the per-plane region counts at the start of the launch.  Compiled with -ffp-contract=off.
+// The key, the element of the walk with its weight, the group scan, the PRO value and the trapezoid term are the functions of
+// pro_shared.h, which csrc/pro_wide.hip (one segment over the whole chip, the same bits) includes too.
 #include "common.h"
+#include "pro_shared.h"
 
 namespace {
+
+using namespace anoddpm::pro;                                    // make_key, group_scan, elem_of, pro_value, term_of: shared with pro_wide.hip
 
 constexpr int THREADS = 1024, WAVES = THREADS / 64, RADIX = 256, UNROLL = 4;
 
@@ -65,37 +70,6 @@ __device__ __forceinline__ void wave_carry(const uint32_t *wtot, int wave, uint3
     }
 }
 
-// inclusive fp64 scan over the 64 lanes of a wave, Hillis-Steele: the order of the additions is the same everywhere it is used
-__device__ __forceinline__ double group_scan(double v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
-// element j of the descending order (sorted index n - 1 - j) of a wave's walk
-struct Elem { bool valid, pos, end; uint32_t key; double w; };
-
-__device__ __forceinline__ Elem elem_of(const uint32_t *__restrict__ key, const int32_t *__restrict__ area, uint32_t j, uint32_t c1, uint32_t n)
-{
-    Elem e;
-    e.valid = j < c1;
-    e.key = 0;
-    e.pos = e.end = false;
-    e.w = 0.0;
-    if (e.valid) {
-        const uint32_t i = n - 1 - j;
-        e.key = key[i];
-        e.pos = (e.key & 1u) != 0;
-        e.end = i == 0 || (key[i - 1] >> 1) != (e.key >> 1);
-        if (e.pos) e.w = 1.0 / (double)area[i];
-    }
-    return e;
-}
-
 __global__ __launch_bounds__(THREADS) void pro_auc_kernel(anoddpm_pro_args a, int64_t seg_words)
 {
     __shared__ uint32_t hist[WAVES * RADIX];                     // wave-private rows: digit counts, then scatter offsets
@@ -130,14 +104,7 @@ __global__ __launch_bounds__(THREADS) void pro_auc_kernel(anoddpm_pro_args a, in
         for (uint32_t i = tid; i < n; i += THREADS) {
             const float s = score[i];
             const int32_t ar = area[i];
-            if (s != s) st |= ANODDPM_ROC_NAN;
-            else if (s == INFINITY || s == -INFINITY) st |= ANODDPM_ROC_INF;
-            if (s < 0.0f) st |= ANODDPM_ROC_NEGATIVE;
-            if (mask) {
-                const float m = mask[i];
-                if (!(m == 0.0f || m == 1.0f)) st |= ANODDPM_ROC_BAD_MASK;
-            }
-            src[i] = (__float_as_uint(s + 0.0f) << 1) | (ar != 0 ? 1u : 0u);       // -0.0 + 0.0 = +0.0
+            src[i] = make_key(s, ar, mask != nullptr, mask ? mask[i] : 0.0f, st);
             psrc[i] = ar;
         }
         if (st) atomicOr(&s_status, st);
@@ -241,7 +208,6 @@ __global__ __launch_bounds__(THREADS) void pro_auc_kernel(anoddpm_pro_args a, in
         double carry_w = 0.0;
         for (int w = 0; w < wave; ++w) carry_w += wtot_w[w];
         const bool want_curve = a.curve_fps != nullptr;
-        const double dK = (double)K;
         for (uint32_t base = c0; base < c1; base += 64) {
             const uint32_t j = base + lane;
             const Elem e = elem_of(src, psrc, j, c1, n);
@@ -250,7 +216,7 @@ __global__ __launch_bounds__(THREADS) void pro_auc_kernel(anoddpm_pro_args a, in
             if (e.end) {
                 const uint32_t q = carry_e + __popcll(be & lt);
                 const uint32_t fps = (j + 1) - (carry_p + __popcll(bp & lt) + (e.pos ? 1u : 0u));
-                const double pro = K == 0 ? (double)NAN : fmin((carry_w + incl) / dK, 1.0);
+                const double pro = pro_value(carry_w, incl, K);
                 runfps[q] = fps;                                 // q < R <= n
                 runpro[q] = pro;
                 if (want_curve && (int64_t)q < a.curve_cap) {
@@ -274,17 +240,7 @@ __global__ __launch_bounds__(THREADS) void pro_auc_kernel(anoddpm_pro_args a, in
         double part = 0.0;
         if (K != 0 && N != 0) {
             for (uint32_t q = tid; q < R; q += THREADS) {
-                const double x1 = (double)runfps[q] / dN, y1 = runpro[q];
-                const double x0 = q ? (double)runfps[q - 1] / dN : 0.0, y0 = q ? runpro[q - 1] : 0.0;
-                double term = 0.0;
-                if (x0 < limit) {
-                    if (x1 <= limit) term = (x1 - x0) * (y1 + y0) * 0.5;
-                    else {
-                        const double yl = y0 + (y1 - y0) * ((limit - x0) / (x1 - x0));
-                        term = (limit - x0) * (yl + y0) * 0.5;
-                    }
-                }
-                part += term;
+                part += term_of(runfps, runpro, q, dN, limit);
             }
         }
 #pragma unroll

@@ -3,37 +3,27 @@
 // the whole test set).  A launch boundary is the only ordering between workgroups: no kernel below waits for another workgroup,
 // and none reads, within a launch, what another workgroup wrote in that launch.  Every loop is bounded by n or by the tile count.
 //   keys        key as roc.hip (roc_shared.h), the tile's precondition bits, and the tile histogram of the first pass
-//   4 x         scan     one workgroup: exclusive scan of the [256][tiles] counter table in (digit, tile) order; a pass in which
-//                        the WHOLE segment has one digit sets the pass's skip flag
-//               scatter  per tile: its waves own contiguous chunks, rank among equal digits from ballots (stable); a skipped pass
-//                        copies the tile, so the sorted keys always end in the first buffer
-//               hist     per tile: the histogram of the next pass's digit (LDS integer atomics)
+//   4 x         scan, scatter (its key-only instantiation), hist of the next pass's digit: the sort pass of wide_shared.h
 //   run_count   per tile: run starts (a tile's first key compares against the previous tile's last key) and positives
 //   run_write   per tile: its carry is the sum of the counts of the tiles below; runpos / runtp compacted, with the sentinel
 //   run_terms   per tile of runs, from the highest score down: its part of twoU (uint64), its number of kept curve points, its
 //               best-Dice candidate, and the average-precision terms into an fp64 array
 //   curve_write per tile of runs: the kept points, compactly, from the carry of the tiles above       (only with curve outputs)
-//   ap_lanes    16 workgroups, one per wave of roc.hip's step 6: virtual lane t of 1024 adds the terms t, t + 1024, ... in that
-//               order (the other waves of the workgroup only stage the terms in LDS), then the 64-lane tree       (only with ap)
+//   lanes       16 workgroups, one per wave of roc.hip's step 6 (wide_shared.h): virtual lane t of 1024 adds the terms t,
+//               t + 1024, ... in that order, then the 64-lane tree                                                (only with ap)
 //   finish      one workgroup: folds the per-tile integers, the 16-wave tree, writes the outputs of the segment
 // 16 launches per segment without curve and ap, 18 with both.  Every output has the bits anoddpm_roc_auc writes.
 // Compiled with -ffp-contract=off.  There is no floating-point atomic in this file.
 #include "common.h"
 #include "roc_shared.h"
+#include "wide_shared.h"
 
 namespace {
 
 using namespace anoddpm::roc;
+using namespace anoddpm::wide;                                   // geometry, hist / scan / scatter<payload> and lanes: shared with pro_wide.hip
 
-constexpr int WT = 256, WW = WT / 64, RADIX = 256, UNROLL = 4;   // workgroup of a tile: one thread per digit
-constexpr int ST = 1024, SW = ST / 64;                           // workgroup of the table scan and of ap_lanes
-constexpr int AP_LANES = 1024, AP_WAVES = AP_LANES / 64;         // the workgroup of roc.hip whose summation order ap keeps
-constexpr int AP_STAGE = 64;                                     // rows of 64 terms staged per round
-constexpr int32_t MAX_TILES = ANODDPM_ROC_WIDE_MAX_TILES, DEFAULT_TILE = 4096;
 enum { H_SKIP = 0, H_R = 4, H_P = 5, H_WORDS = 64 };
-
-static_assert(2 * ST == MAX_TILES, "scan_kernel: one thread owns two rows of the counter table");
-static_assert(AP_WAVES == 16 && SW == 16, "the trees of roc_shared.h are instantiated for 16 waves");
 
 struct wide_ws {                 // one segment's workspace
     double *terms;               // [W] average-precision term of run r
@@ -45,26 +35,7 @@ struct wide_ws {                 // one segment's workspace
     uint32_t *hdr;               // H_WORDS
 };
 
-struct wide_geom { uint32_t n, tile, T; };
-
 int64_t seg_words_of(int64_t n) { return (n + 1 + 63) / 64 * 64; }
-
-int32_t default_tile(int64_t n)
-{
-    const int64_t per = (n + MAX_TILES - 1) / MAX_TILES;
-    const int64_t t = (per + 255) / 256 * 256;
-    return (int32_t)(t > DEFAULT_TILE ? t : DEFAULT_TILE);
-}
-
-// tiles the workspace is sized for: with the default tile a count that never shrinks as n grows
-int64_t alloc_tiles(int64_t n, int32_t tile)
-{
-    if (tile == 0) {
-        const int64_t t = (n + DEFAULT_TILE - 1) / DEFAULT_TILE;
-        return t < MAX_TILES ? t : MAX_TILES;
-    }
-    return (n + tile - 1) / tile;
-}
 
 int64_t carve(wide_ws *w, void *base, int64_t n, int64_t Ta)
 {
@@ -108,123 +79,6 @@ __global__ __launch_bounds__(WT) void keys_kernel(const float *__restrict__ scor
     __syncthreads();
     w.table[tid * g.T + b] = hist[tid];                          // digit-major
     if (tid == 0) w.tile_st[b] = s_status;
-}
-
-__global__ __launch_bounds__(WT) void hist_kernel(const uint32_t *__restrict__ src, uint32_t *__restrict__ table, wide_geom g, int shift)
-{
-    __shared__ uint32_t hist[RADIX];
-    const uint32_t b = blockIdx.x, tid = threadIdx.x;
-    hist[tid] = 0;
-    __syncthreads();
-    const uint32_t i0 = b * g.tile, i1 = min(i0 + g.tile, g.n);
-    for (uint32_t i = i0 + tid; i < i1; i += WT) atomicAdd(&hist[(src[i] >> shift) & 255u], 1u);
-    __syncthreads();
-    table[tid * g.T + b] = hist[tid];
-}
-
-// one workgroup: table[0 .. 256 T) -> its exclusive prefix, in place; *skip = the whole segment has one digit in this pass.
-// The table is T rows of 256 words, one 16-byte load per lane: a wave sums its rows, the row totals are scanned in LDS, and a
-// second sweep writes each row's prefix -- five barriers however long the table is.
-__global__ __launch_bounds__(ST) void scan_kernel(uint32_t *table, uint32_t *skip, wide_geom g)
-{
-    __shared__ uint32_t rowsum[MAX_TILES];
-    __shared__ uint32_t wsum[SW];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, T = g.T;     // T <= MAX_TILES rows
-    uint4 *rows = reinterpret_cast<uint4 *>(table);
-    if (tid == 0) *skip = 0;
-#pragma unroll 4
-    for (uint32_t row = wave; row < T; row += SW) {
-        const uint4 v = rows[row * 64 + lane];
-        uint32_t sum = v.x + v.y + v.z + v.w;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-        if (lane == 0) rowsum[row] = sum;
-    }
-    __syncthreads();
-    {
-        const uint32_t r0 = 2 * tid;                             // 2 * ST = MAX_TILES: every row has an owner
-        const uint32_t a = r0 < T ? rowsum[r0] : 0u, b = r0 + 1 < T ? rowsum[r0 + 1] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_exclusive_scan<SW>(a + b, wsum, total);
-        if (r0 < T) rowsum[r0] = ex;
-        if (r0 + 1 < T) rowsum[r0 + 1] = ex + a;
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (uint32_t row = wave; row < T; row += SW) {
-        const uint4 v = rows[row * 64 + lane];
-        const uint32_t sum = v.x + v.y + v.z + v.w;
-        uint32_t incl = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
-        uint4 o;
-        o.x = rowsum[row] + incl - sum;
-        o.y = o.x + v.x;
-        o.z = o.y + v.y;
-        o.w = o.z + v.z;
-        rows[row * 64 + lane] = o;
-    }
-    __syncthreads();                                             // this workgroup's own stores, read back below
-    if (tid < RADIX) {
-        const uint32_t end = tid == RADIX - 1 ? g.n : table[(tid + 1) * T];
-        if (end - table[tid * T] == g.n) *skip = 1;              // at most one digit can hold every key
-    }
-}
-
-__global__ __launch_bounds__(WT) void scatter_kernel(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, const uint32_t *__restrict__ table,
-                                                     const uint32_t *__restrict__ skip, wide_geom g, int shift)
-{
-    __shared__ uint32_t hist[WW * RADIX];                        // wave-private rows: digit counts, then scatter offsets
-    const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = g.n;
-    const uint32_t i0 = b * g.tile, i1 = min(i0 + g.tile, n);
-    if (*skip != 0) {                                            // written by the scan launch: uniform over the grid
-        for (uint32_t i = i0 + tid; i < i1; i += WT) dst[i] = src[i];
-        return;
-    }
-    const uint64_t lt = (1ull << lane) - 1ull;
-    const uint32_t chunk = g.tile / WW;                          // a multiple of 64
-    const uint32_t c0 = min(i0 + wave * chunk, i1), c1 = min(c0 + chunk, i1);
-    for (int i = tid; i < WW * RADIX; i += WT) hist[i] = 0;
-    __syncthreads();
-    uint32_t *wh = hist + wave * RADIX;
-    for (uint32_t i = c0 + lane; i < c1; i += 64) atomicAdd(&wh[(src[i] >> shift) & 255u], 1u);
-    __syncthreads();
-    {
-        uint32_t ex = table[tid * g.T + b];                      // thread = digit: where this tile's keys of the digit begin
-#pragma unroll
-        for (int k = 0; k < WW; ++k) {
-            const uint32_t h = hist[k * RADIX + tid];
-            hist[k * RADIX + tid] = ex;
-            ex += h;
-        }
-    }
-    __syncthreads();
-    for (uint32_t base = c0; base < c1; base += 64 * UNROLL) {
-        uint32_t key[UNROLL];
-        bool valid[UNROLL];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            const uint32_t i = base + u * 64 + lane;
-            valid[u] = i < c1;
-            key[u] = valid[u] ? src[i] : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            if (base + u * 64 >= c1) break;                      // wave-uniform
-            const uint32_t dg = (key[u] >> shift) & 255u;
-            const uint64_t m = digit_peers(dg, valid[u]);
-            const uint32_t rank = __popcll(m & lt), cnt = __popcll(m);
-            uint32_t pos = 0;
-            if (valid[u]) pos = wh[dg] + rank;
-            wave_sync();
-            if (valid[u] && rank == cnt - 1) wh[dg] = pos + 1;
-            wave_sync();
-            if (valid[u] && pos < n) dst[pos] = key[u];          // pos < n always; the guard keeps a bad offset inside the buffer
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ runs
@@ -420,40 +274,6 @@ __global__ __launch_bounds__(WT) void curve_write_kernel(const uint32_t *__restr
     }
 }
 
-// workgroup v = wave v of roc.hip's step 6.  Lane l of it is virtual lane t = 64 v + l and adds the terms t, t + 1024, ... in that
-// order; the sixteen waves here only fetch AP_STAGE rows of those terms into LDS, wave 0 adds them row by row.
-__global__ __launch_bounds__(ST) void ap_lanes_kernel(wide_ws w, wide_geom g)
-{
-    __shared__ double stage[AP_STAGE * 64];
-    const uint32_t v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, sub = tid >> 6;
-    const uint32_t R = min(w.hdr[H_R], g.n);
-    const uint32_t rows = (R + AP_LANES - 1) / AP_LANES;         // <= 2^21
-    constexpr int PER = AP_STAGE / SW;
-    double part = 0.0, next[PER];
-    auto fetch = [&](uint32_t k0) {                              // the rows of the next round, in flight while wave 0 adds this one
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const uint32_t k = k0 + sub * PER + u;
-            const uint32_t r = k * AP_LANES + v * 64 + lane;     // < 2^31 + 2^18
-            next[u] = (k < rows && r < R) ? w.terms[r] : 0.0;    // + 0.0 leaves a non-negative partial alone
-        }
-    };
-    fetch(0);
-    for (uint32_t k0 = 0; k0 < rows; k0 += AP_STAGE) {
-#pragma unroll
-        for (int u = 0; u < PER; ++u) stage[(sub * PER + u) * 64 + lane] = next[u];
-        __syncthreads();
-        if (k0 + AP_STAGE < rows) fetch(k0 + AP_STAGE);
-        if (sub == 0)
-            for (int k = 0; k < AP_STAGE; ++k) part += stage[k * 64 + lane];
-        __syncthreads();
-    }
-    if (sub == 0) {
-        part = tree_add<64>(part);
-        if (lane == 0) w.wavesum[v] = part;
-    }
-}
-
 struct wide_out {                // the outputs of this segment
     double *auc; int64_t *counts; int32_t *status; int32_t *curve_len; int64_t curve_cap;
     double *ap; double *best_dice; float *best_thr; int64_t *best_counts;
@@ -513,16 +333,6 @@ __global__ __launch_bounds__(WT) void finish_kernel(const uint32_t *__restrict__
     }
 }
 
-int check_tile(int64_t n, int32_t tile, int32_t *used, const char *who)
-{
-    using namespace anoddpm;
-    ANODDPM_REQUIRE(tile >= 0 && tile % WT == 0, "%s: tile must be a multiple of 256, or 0 for the default", who);
-    const int32_t t = tile == 0 ? default_tile(n) : tile;
-    ANODDPM_REQUIRE((n + t - 1) / t <= MAX_TILES, "%s: tile %d cuts n into more than %d tiles", who, (int)tile, (int)MAX_TILES);
-    *used = t;
-    return ANODDPM_OK;
-}
-
 }  // namespace
 
 extern "C" int64_t anoddpm_roc_wide_workspace_bytes(int32_t S, int64_t n, int32_t tile)
@@ -578,7 +388,7 @@ extern "C" int anoddpm_roc_auc_wide(const anoddpm_roc_args *a, int32_t tile, voi
         for (int pass = 0; pass < 4; ++pass) {
             if (pass > 0) hipLaunchKernelGGL(hist_kernel, tiles, wt, 0, s, src, w.table, g, pass * 8);
             hipLaunchKernelGGL(scan_kernel, one, st, 0, s, w.table, w.hdr + H_SKIP + pass, g);
-            hipLaunchKernelGGL(scatter_kernel, tiles, wt, 0, s, src, dst, w.table, w.hdr + H_SKIP + pass, g, pass * 8);
+            hipLaunchKernelGGL(scatter_kernel<false>, tiles, wt, 0, s, src, dst, (const int32_t *)nullptr, (int32_t *)nullptr, w.table, w.hdr + H_SKIP + pass, g, pass * 8);
             uint32_t *t = src;
             src = dst;
             dst = t;
@@ -595,7 +405,7 @@ extern "C" int anoddpm_roc_auc_wide(const anoddpm_roc_args *a, int32_t tile, voi
             c.cap = a->curve_cap;
             hipLaunchKernelGGL(curve_write_kernel, tiles, wt, 0, s, src, runpos, runtp, w, g, want, c);
         }
-        if (want.ap) hipLaunchKernelGGL(ap_lanes_kernel, dim3(AP_WAVES), st, 0, s, w, g);
+        if (want.ap) hipLaunchKernelGGL(lanes_kernel, dim3(AP_WAVES), st, 0, s, (const double *)w.terms, (const uint32_t *)(w.hdr + H_R), w.wavesum, g.n);
         wide_out o;
         o.auc = a->auc + seg;
         o.counts = a->counts + (int64_t)seg * 4;

@@ -40,6 +40,11 @@ per tile of keys, and writes the same bits.  `_roc_launch` takes it for a single
 (environment `ANODDPM_ROC_WIDE_MIN_N`), so nothing the functions above return changes.  `PooledCurves` collects the maps of a
 run in two preallocated device buffers without a host synchronisation and scores the pooled segment; `ROC_AUC` and `PR_curve`
 also take a list of device tensors on each side, meaning the pooled segment of all of them.
+The per-region overlap score pools the same way and is a data-set score by definition: `anoddpm_pro_auc_wide` (csrc/pro_wide.hip)
+sorts (key, area) pairs and walks ONE segment with the whole chip, as 18 launches, and writes the bits of `anoddpm_pro_auc`;
+`_pro_launch` takes it for a single segment of at least `PRO_WIDE_MIN_N` elements (environment `ANODDPM_PRO_WIDE_MIN_N`).
+`PooledRegionCurves` is a `PooledCurves` that also keeps the region areas, so one pool yields AUPRO beside AUROC, AP and best
+Dice; `AUPRO` takes a list of device tensors on each side too.
 
 Post-processing (the reference has none: it scores the raw squared error).  Published brain-MRI anomaly-segmentation pipelines
 median-filter the residual, restrict it to an eroded brain mask and drop tiny components from the binary prediction before they
@@ -88,7 +93,7 @@ from . import _lib
 from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs, ErodeArgs, GaussArgs, MapScoresArgs, MedianArgs, ProArgs, RocArgs, SsimArgs,
                    SurfaceArgs, check, current_stream, lib)
 
-__all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "PooledCurves", "ssim", "median_filter", "erode_mask",
+__all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "PooledCurves", "PooledRegionCurves", "ssim", "median_filter", "erode_mask",
            "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "aupro", "pro_points", "AUPRO", "distance_transform",
            "surface_distance", "HD95", "anomaly_metrics_surface", "gaussian_filter", "image_scores", "image_auc", "anomaly_metrics_image", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
@@ -760,10 +765,38 @@ def component_areas(mask, connectivity=2, level=0.0, batched=None):
     return areas, counts
 
 
-def _pro_launch(mask, score, limit, connectivity, batched, curve):
+# A single segment of at least this many elements is sorted and walked by the whole chip (anoddpm_pro_auc_wide); the outputs have
+# the same bits.  65536 is the smallest measured power of two from which, at every larger measured size, the slowest wide repetition
+# was below the fastest one-workgroup repetition (profiles/pro_wide_ab.txt); 2147483648 switches the path off.
+PRO_WIDE_MIN_N = int(os.environ.get("ANODDPM_PRO_WIDE_MIN_N", "") or 65536)
+
+
+def _pro_call(a, out, S, n, dev, wide, tile):
+    """The launch of a filled `ProArgs`: `anoddpm_pro_auc_wide` (`tile` elements per workgroup; None: the library's choice) or
+    `anoddpm_pro_auc`, with the workspace of either.  Sets `out["path"]`."""
+    out["path"] = "wide" if wide else "workgroup"
+    if wide:
+        tile = 0 if tile is None else int(tile)
+        nbytes = lib().anoddpm_pro_wide_workspace_bytes(S, n, tile)
+        if nbytes < 0:
+            raise ValueError(f"pro: segment length {n} is outside [1, 2^31), or tile {tile} is not a multiple of 256 that cuts it into "
+                             f"at most {_lib.ROC_WIDE_MAX_TILES} tiles")
+        ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+        with torch.cuda.device(dev):
+            check(lib().anoddpm_pro_auc_wide(ctypes.byref(a), tile, current_stream()), "pro_auc_wide")
+        return out
+    _launch("pro_auc", a, dev, (lib().anoddpm_pro_workspace_bytes(S, n), torch.float64, f"pro: segment length {n} is outside [1, 2^31)"))
+    return out
+
+
+def _pro_launch(mask, score, limit, connectivity, batched, curve, wide=None, tile=None):
     """One `anoddpm_component_areas` run on the mask and one `anoddpm_pro_auc` launch.  score: [S, ..., H, W] when batched, else
     one segment [..., H, W]; every plane of `score[s]` belongs to segment s.  mask: like score, or the shape of one segment (its
-    areas are computed once and shared).  Returns a dict of device tensors; nothing is copied to the host."""
+    areas are computed once and shared).  `wide`: sort and walk the segments one after another with the whole chip
+    (`anoddpm_pro_auc_wide`, `tile` elements per workgroup; None: the library's choice); None takes that path for one segment of
+    at least `PRO_WIDE_MIN_N` elements.  Both paths write the same bits; `path` says which one ran ("wide" / "workgroup").
+    Returns a dict of device tensors; nothing is copied to the host."""
     if not isinstance(score, torch.Tensor) or not isinstance(mask, torch.Tensor):
         raise TypeError("pro: mask and score must be device tensors")
     if isinstance(limit, bool) or not 0.0 < float(limit) <= 1.0:
@@ -790,8 +823,9 @@ def _pro_launch(mask, score, limit, connectivity, batched, curve):
     a.limit, a.S, a.planes_per_segment, a.H, a.W = float(limit), S, C, H, W
     if curve:                                                        # a segment has at most n distinct scores
         a.curve_fps, a.curve_pro, a.curve_thr, a.curve_len, a.curve_cap = _curve_buffers(out, "pro", torch.float64, S, n, dev)
-    _launch("pro_auc", a, dev, (lib().anoddpm_pro_workspace_bytes(S, n), torch.float64, f"pro: segment length {n} is outside [1, 2^31)"))
-    return out
+    if wide is None:
+        wide = S == 1 and n >= PRO_WIDE_MIN_N
+    return _pro_call(a, out, S, n, dev, wide, tile)
 
 
 def aupro(mask, score, limit=0.3, connectivity=2, batched=None, return_status=False):
@@ -813,7 +847,11 @@ def pro_points(mask, score, limit=0.3, connectivity=2, batched=None):
     threshold down and without the `(0, 0)` point in front.  A list of dicts with `fps` (int64 counts; `FPR = fps / N`), `pro`
     (fp64), `thresholds` (fp32), `K` (regions), `N`, `P` (pixels outside / inside the regions) and `aupro` (Python numbers).
     Copies to the host; raises ValueError for inputs outside the precondition."""
-    o = _pro_launch(mask, score, limit, connectivity, _is_batched(score, batched), curve=True)
+    return _pro_points_of(_pro_launch(mask, score, limit, connectivity, _is_batched(score, batched), curve=True))
+
+
+def _pro_points_of(o):
+    """The host form of a `_pro_launch` dict with curve outputs: the list `pro_points` returns."""
     status, lens, counts, val = o["status"].cpu(), o["len"].cpu(), o["counts"].cpu(), o["aupro"].cpu()
     _raise_on_status("pro", status)
     return [dict(_curve_arrays(o, ("fps", "pro", "thresholds"), s, L), K=int(counts[s, 0]), N=int(counts[s, 1]),
@@ -1222,6 +1260,71 @@ class PooledCurves:
         return PR_curve(*self._segment("pr_curve"))
 
 
+class PooledRegionCurves(PooledCurves):
+    """`PooledCurves` that also keeps what the per-region overlap score needs, so that one pool yields every pooled score of a
+    run: beside mask and score the int32 area of every pixel's connected ground-truth region (`component_areas`, `connectivity`
+    2: 8 neighbours) and, in a one-element int64 device accumulator, the number of regions.  `add(mask, score)`: mask
+    `[..., H, W]`, score of the same shape or k stacked copies' worth of planes for the one mask; planes of different adds may
+    differ in H x W.  One component run per `add` on the mask planes, no host synchronisation.  Every (mask plane, score plane)
+    pair is an image of the set, so a mask shared by k score planes counts its regions k times.  Overflow raises ValueError from
+    the count kept on the host, as `PooledCurves.add` does.  `aupro(limit)` is a `[1]` fp64 device tensor without a
+    synchronisation (NaN under the status rule of `metrics.aupro`; `return_status=True` also returns the status word),
+    `pro_curve(limit)` the dict `pro_points` returns for the pooled segment.  `scores()` / `roc_curve()` / `pr_curve()` are
+    inherited.  The pooled segment goes to the kernels as one plane of 1 x n: they read the plane shape only through n, and the
+    region counts only through their sum."""
+
+    def __init__(self, capacity, connectivity=2, device=None):
+        _check_connectivity(connectivity, "PooledRegionCurves")
+        super().__init__(capacity, device=device)
+        self._connectivity = int(connectivity)
+        self._area = torch.empty((self.capacity,), dtype=torch.int32, device=self._mask.device)
+        self._regions = torch.zeros((1,), dtype=torch.int64, device=self._mask.device)
+
+    def reset(self):
+        super().reset()
+        self._regions.zero_()
+
+    def add(self, mask, score):
+        if not isinstance(mask, torch.Tensor) or not isinstance(score, torch.Tensor) or not mask.is_cuda or not score.is_cuda:
+            raise TypeError("PooledRegionCurves.add: mask and score must be device tensors")
+        k, km = score.numel(), mask.numel()
+        if mask.dim() < 2 or score.dim() < 2 or k == 0 or km == 0 or k % km != 0 or tuple(score.shape[-2:]) != tuple(mask.shape[-2:]):
+            raise ValueError(f"PooledRegionCurves.add: mask {tuple(mask.shape)} does not match score {tuple(score.shape)}")
+        if self._n + k > self.capacity:
+            raise ValueError(f"PooledRegionCurves.add: {self._n} + {k} pixels exceed the capacity {self.capacity}")
+        H, W = mask.shape[-2:]
+        areas, regions = component_areas(mask.reshape(-1, H, W), self._connectivity, batched=True)
+        n0 = self._n
+        super().add(mask, score)
+        self._area[n0:n0 + k].view(k // km, km).copy_(areas.reshape(1, km).expand(k // km, km))
+        self._regions += regions.sum() * (k // km)
+
+    def _pro(self, limit, curve, what):
+        if isinstance(limit, bool) or not 0.0 < float(limit) <= 1.0:
+            raise ValueError(f"pro: limit must be in (0, 1], got {limit!r}")
+        mk, sc = self._segment(what)
+        n, dev = self._n, sc.device
+        out = {"aupro": torch.empty((1,), dtype=torch.float64, device=dev),
+               "counts": torch.empty((1, 4), dtype=torch.int64, device=dev),
+               "status": torch.empty((1,), dtype=torch.int32, device=dev), "n": n}
+        a = ProArgs()
+        a.score, a.area, a.region_counts, a.mask = sc.data_ptr(), self._area.data_ptr(), self._regions.data_ptr(), mk.data_ptr()
+        a.aupro, a.counts, a.status = out["aupro"].data_ptr(), out["counts"].data_ptr(), out["status"].data_ptr()
+        a.score_stride, a.area_stride, a.mask_stride = n, n, n
+        a.limit, a.S, a.planes_per_segment, a.H, a.W = float(limit), 1, 1, 1, n
+        if curve:
+            a.curve_fps, a.curve_pro, a.curve_thr, a.curve_len, a.curve_cap = _curve_buffers(out, "pro", torch.float64, 1, n, dev)
+        return _pro_call(a, out, 1, n, dev, n >= PRO_WIDE_MIN_N, None)
+
+    def aupro(self, limit=0.3, return_status=False):
+        o = self._pro(limit, False, "aupro")
+        val = _nan_where_status(o, "aupro")
+        return (val, o["status"]) if return_status else val
+
+    def pro_curve(self, limit=0.3):
+        return _pro_points_of(self._pro(limit, True, "pro_curve"))[0]
+
+
 def ROC_AUC(real_mask, square_error):
     """evaluation.py:78-82.  Device tensors: the native sort (`roc_points` of the flattened inputs); the host prepends the
     `(0, 0, inf)` point and divides the integer counts in fp64, which gives sklearn's `(fpr, tpr, thresholds)` bit for bit
@@ -1271,7 +1374,18 @@ def AUPRO(real_mask, square_error, limit=0.3):
     """Area under the per-region overlap curve of the mask's connected regions (8 neighbours) up to the false-positive rate
     `limit`, normalised to [0, 1] (Bergmann et al., IJCV 2021), as a Python float: `aupro` with all planes of the inputs pooled
     into one curve.  NaN without a region or without background; ValueError for inputs outside the precondition of `ROC_AUC`.
-    Device tensors only: the reference has no host implementation to fall back to."""
+    A list or tuple of device tensors on each side is the pooled curve of all of them, `[..., H, W]` each, planes of mixed
+    shapes allowed (`PooledRegionCurves`).  Device tensors only: the reference has no host implementation to fall back to."""
+    if isinstance(real_mask, (list, tuple)) or isinstance(square_error, (list, tuple)):
+        if not (isinstance(real_mask, (list, tuple)) and isinstance(square_error, (list, tuple))) or len(real_mask) != len(square_error) or not real_mask:
+            raise TypeError("AUPRO: a pooled call takes two non-empty lists of device tensors of the same length")
+        for x in (*real_mask, *square_error):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda:
+                raise TypeError("AUPRO: a pooled call takes device tensors only")
+        pool = PooledRegionCurves(sum(x.numel() for x in square_error), device=square_error[0].device)
+        for m, x in zip(real_mask, square_error):
+            pool.add(m, x)
+        return pool.pro_curve(limit)["aupro"]
     return pro_points(real_mask, square_error, limit=limit, batched=False)[0]["aupro"]
 
 

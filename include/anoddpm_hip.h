@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 35
+#define ANODDPM_ABI_VERSION 36
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -789,6 +789,30 @@ typedef struct anoddpm_pro_args {
 int anoddpm_component_areas(const anoddpm_component_areas_args *a, void *stream);
 int anoddpm_pro_auc(const anoddpm_pro_args *a, void *stream);
 int64_t anoddpm_pro_workspace_bytes(int32_t S, int64_t n);   /* HOST function; -1 for S < 1, n < 1 or n >= 2^31 */
+
+/* The same curve and AUPRO with every segment sorted and walked by the whole chip (csrc/pro_wide.hip): for one long segment -- a
+ * whole test set pooled into one curve, which is how the score is defined -- where anoddpm_pro_auc keeps all but one compute unit
+ * idle.  Like anoddpm_pro_auc it replaces no call of the reference, which has no counterpart.  Same argument struct, every field
+ * with the meaning above (strides, shared mask, optional mask check, optional curve outputs); the S segments are processed one
+ * after another on `stream`, each as a sequence of 18 launches with one workgroup per tile of `tile` elements, and share ONE
+ * segment's workspace.  A launch boundary is the only ordering between workgroups; nothing allocates or synchronises, so the call
+ * is capturable in a hipGraph.
+ *   tile       elements per workgroup: a multiple of 256 from 256 up, or 0 for the library's choice, with the rules of
+ *              anoddpm_roc_auc_wide: at most ANODDPM_ROC_WIDE_MAX_TILES tiles, an explicit tile that needs more is refused, tile
+ *              0 is 4096 and grows with n so that every n < 2^31 is accepted
+ *   workspace  [dev] anoddpm_pro_wide_workspace_bytes(S, n, tile) bytes, 16-byte aligned, whatever S is: with W = n rounded up
+ *              to 64, 28 W bytes (keys and areas twice, the false-positive count and the fp64 PRO of every curve point; the fp64
+ *              trapezoid terms lie in the key and area buffers the sort left free) + W / 4 bytes (two fp64 words per group of 64
+ *              elements) + 1044 bytes per tile (the 256 counters of a sort pass and five words) + less than 1 KB; never
+ *              smaller for a larger n at the same tile
+ * H, W and planes_per_segment are read only through n = planes_per_segment * H * W, and region_counts only through the sum of
+ * the segment's planes_per_segment entries: a caller that pools planes of several shapes passes planes_per_segment = 1, H = 1,
+ * W = n and one entry that holds the number of regions.
+ * For every accepted input every output has the bits anoddpm_pro_auc writes for the same arguments: aupro, counts, status,
+ * curve_fps / curve_pro / curve_thr / curve_len, ANODDPM_ROC_CURVE_TRUNCATED, and the status word of a segment that breaks the
+ * precondition (its other outputs stay not meaningful).  Argument checks as anoddpm_pro_auc, made before anything is launched. */
+int anoddpm_pro_auc_wide(const anoddpm_pro_args *a, int32_t tile, void *stream);
+int64_t anoddpm_pro_wide_workspace_bytes(int32_t S, int64_t n, int32_t tile);   /* HOST function; -1 where the call would be refused */
 
 /* ------------------------------------------------------------------ distance transform and boundary distances of anomaly maps
  * The Hausdorff distance, its 95th-percentile form (HD95) and the average symmetric surface distance (ASSD): how far the
