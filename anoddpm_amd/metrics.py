@@ -161,7 +161,7 @@ def anomaly_maps(real, recon, mask=None, threshold=0.5, want=("mean", "sqerr", "
             raise ValueError("mask size mismatch")
     dev = real.device
     maps = {k: torch.empty_like(real) for k in want}
-    counts = torch.empty((B, NC), dtype=torch.float64, device=dev)
+    counts = torch.zeros((B, NC), dtype=torch.float64, device=dev)       # the pass leaves the reserved column 11 alone: 0
     ws = torch.empty((_lib.ANOMALY_BLOCKS * B * NC,), dtype=torch.float64, device=dev)
     a = AnomalyArgs()
     a.recon, a.real, a.mask = recon.data_ptr(), real.data_ptr(), (mask.data_ptr() if mask is not None else None)
@@ -1121,15 +1121,20 @@ def heatmap(real, recon, mask, filename, save=True):
 
 
 def dice_coeff(real, recon, real_mask, smooth=0.000001, mse=None):
-    """evaluation.py:26-36.  `mse`, when given, is the already thresholded map (detection.py:232)."""
+    """evaluation.py:26-36.  `mse`, when given, is used as it is, like upstream (evaluation.py:34-35: `sum(mse * real_mask)` and
+    `sum(mse) + sum(real_mask)` per image): the thresholded map of detection.py:232, or any real-valued map -- the three sums are
+    then plain fp64 reductions on the device (no threshold pass, no host synchronisation), so the value is the reference's for
+    every `mse`, not only for a {0,1} one."""
     if mse is None:
         _, counts = anomaly_maps(real, recon, real_mask, threshold=0.5, want=())
+        d = (2.0 * counts[:, 2] + smooth) / (counts[:, 0] + counts[:, 1] + smooth)
     else:
-        # thresholded map supplied: pred = (mse > 0.5) reproduces it for a {0,1} map; run the same pass on it
-        zeros = torch.zeros_like(_f32c(mse, "dice_coeff(mse)"))
-        sq = _f32c(mse, "dice_coeff(mse)").sqrt()                    # (sqrt(m) - 0)^2 = m for m in {0,1}
-        _, counts = anomaly_maps(zeros, sq, real_mask, threshold=0.5, want=())
-    d = (2.0 * counts[:, 2] + smooth) / (counts[:, 0] + counts[:, 1] + smooth)
+        m = _f32c(mse, "dice_coeff(mse)")
+        k = _f32c(real_mask, "dice_coeff(real_mask)")
+        if m.dim() < 1 or k.numel() != m.numel():
+            raise ValueError(f"dice_coeff: mse shape {tuple(m.shape)} does not match real_mask {tuple(k.shape)}")
+        m, k = m.reshape(m.shape[0], -1).double(), k.reshape(m.shape[0], -1).double()
+        d = (2.0 * (m * k).sum(dim=1) + smooth) / (m.sum(dim=1) + k.sum(dim=1) + smooth)
     return d.mean(dim=0).float()
 
 

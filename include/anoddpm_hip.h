@@ -584,7 +584,10 @@ int anoddpm_sumsq(const float *g, int64_t n, float *out, double *workspace, floa
  * and the sums behind dice_coeff / IoU / precision / recall / FPR / PSNR (evaluation.py:26-76) as
  * counts[b][ANODDPM_ANOMALY_NCOUNTS] (fp64):
  *   0 sum(pred)  1 sum(mask)  2 sum(pred*mask)  3 #(mask==1&pred==1)  4 #(mask==1&pred==0)  5 #(mask==0&pred==1)
- *   6 #(mask==0&pred==0)  7 #(mask!=0 & pred!=0)  8 #(mask!=0 | pred!=0)  9 sum(sqerr)  10 max(real)  11 reserved
+ *   6 #(mask==0&pred==0)  7 #(mask!=0 & pred!=0)  8 #(mask!=0 | pred!=0)  9 sum(sqerr)  10 max(real)  11 reserved (never written)
+ * The mean is the sequential fp32 sum in chain order followed by one division: within navg * 2^-24 * mean_k|recon_k| of the exact
+ * mean always, and equal to CPU ATen's torch.mean(dim=0) for the sizes tests/test_anomaly_reference.py found (navg <= 16 on slices
+ * of a multiple of 64 floats).  max(real) is NaN when the image holds a NaN, like torch.max; sum(sqerr) likewise.
  * recon: [navg] slices of n floats per image, slice stride recon_as, image stride recon_bs (elements).
  * Any of mean / sqerr / mse_img / thr_img / pred may be NULL.  mask may be NULL (treated as all zero).
  * workspace: ANODDPM_ANOMALY_BLOCKS * B * NCOUNTS doubles [dev].  Deterministic (fixed-order fold). */

@@ -12,14 +12,27 @@ import numpy as np
 NCOUNTS = 12
 
 
+def strided_recon(buf, navg, B, n, recon_as, recon_bs):
+    """The [navg,B,n] view the C ABI describes over a flat fp32 buffer: chain k of image b starts at k * recon_as + b * recon_bs
+    (elements).  Elements between the slices are not part of the view."""
+    buf = np.asarray(buf, np.float32).ravel()
+    assert navg >= 1 and (navg - 1) * recon_as + (B - 1) * recon_bs + n <= buf.size
+    return np.lib.stride_tricks.as_strided(buf, (navg, B, n), (4 * recon_as, 4 * recon_bs, 4), writeable=False)
+
+
 def anomaly_maps(real, recon, mask=None, threshold=0.5):
     """real [B,...] fp32; recon [navg,B,...] fp32; mask like real or None.
-    Returns dict(mean, sqerr, mse_img, thr_img, pred) and counts [B,12] float64 (layout of include/anoddpm_hip.h)."""
+    Returns dict(mean, sqerr, mse_img, thr_img, pred) and counts [B,12] float64 (layout of include/anoddpm_hip.h).
+    The mean is the kernel's own statement: the fp32 running sum in chain order, then one division.  That is within
+    navg * 2^-24 * mean_k|recon_k| of the exact mean always, and equal to CPU ATen's torch.mean(dim=0) only for the sizes
+    tests/test_anomaly_reference.py found (navg <= 16 on slices of a multiple of 64 floats; ATen sums larger navg, and slices
+    with a vector tail, in another order).  A NaN compares false, so pred is 0 and thr_img -1 there; max(real) and sum(sqerr)
+    keep it, like torch.max and torch.sum."""
     real = np.asarray(real, np.float32)
     recon = np.asarray(recon, np.float32)
     navg = recon.shape[0]
     s = recon[0].copy()
-    for k in range(1, navg):                      # torch.mean(dim=0): fp32 running sum in index order, then / N
+    for k in range(1, navg):                      # fp32 running sum in chain order, then / navg
         s = (s + recon[k]).astype(np.float32)
     mean = (s / np.float32(navg)).astype(np.float32) if navg > 1 else s
     d = (mean - real).astype(np.float32)
