@@ -40,6 +40,7 @@ SOURCES = {
     "ssim.hip": ["-ffp-contract=off"],
     "postproc.hip": [],
     "smooth.hip": ["-ffp-contract=off"],
+    "select_wide.hip": ["-ffp-contract=off"],
     "wgrad.hip": [],
     "wgrad43.hip": [],
     "gn_backward.hip": [],

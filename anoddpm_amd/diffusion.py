@@ -639,6 +639,9 @@ class GaussianDiffusionModel:
     # opt-in image-level scores of the detection records (metrics.image_scores' `top`: an int k or a fraction in (0, 1]): the maximum
     # and the top-k mean of every image's squared-error map; see _score_settings.  A plain attribute like `pro_limit`.
     image_top = None
+    # opt-in scores at calibrated operating thresholds (an fp32 device tensor [T], e.g. metrics.HealthyPool.thresholds; never read on
+    # the host): `dice_at`, `precision_at`, `recall_at`, `fpr_at` in every detection record; see _score_settings.
+    operating_thresholds = None
     # opt-in strided reverse sampler (StridedSampler; None: the reference's ancestral sampler, and none of the strided code runs).
     # Read by ReverseChain / reverse_chain / forward_backward and the detection loops unless they are handed `sampler=`; also set at
     # construction from ANODDPM_SAMPLER="<stride>[,<eta>]".  A plain attribute like `postprocess`.
@@ -1305,7 +1308,10 @@ class GaussianDiffusionModel:
         never synchronises).  `auc` ... `ssim` stay None where nothing fills them (no mask, images below the SSIM window); the opt-in
         `self.postprocess` (with `self.postprocess_roi`) and `self.pro_limit` add their keys, None without a mask;
         `self.surface_metrics` adds `hd`, `hd95`, `assd` (and `_pp`) only with a mask; `self.image_top` adds `image_max` and
-        `image_topk` (and `_pp`), [B] per record, mask or not.  All unset: exactly the first six."""
+        `image_topk` (and `_pp`), [B] per record, mask or not.  All unset: exactly the first six.
+        `self.operating_thresholds` ([T], on the device) adds `dice_at`, `precision_at`, `recall_at`, `fpr_at`, fp64 [T] per record:
+        `metrics.scores_at` of every setting's squared-error map (its B images pooled, as `auc` pools them) from ONE
+        `anoddpm_threshold_counts` call for the whole sweep; without a mask every pixel is a negative and only `fpr_at` is a number."""
         from . import metrics
         self.last_detection, stacks = [], {"mean": [], "sqerr": [], "thr_img": []}
         for j, extra in enumerate(settings):
@@ -1325,6 +1331,11 @@ class GaussianDiffusionModel:
                     rec[key] = scores[key][j]
                 elif options is not None and all(getattr(self, o) is not None for o in options):
                     rec[key] = None
+        if self.operating_thresholds is not None:
+            sq = torch.stack(stacks["sqerr"]).reshape(len(settings), -1)
+            at = metrics.scores_at(mask if mask is not None else torch.zeros_like(sq[0]), sq, self.operating_thresholds.reshape(-1), batched=True)
+            for j, rec in enumerate(self.last_detection):
+                rec.update({k + "_at": at[k][j] for k in ("dice", "precision", "recall", "fpr")})
 
     def detection_A(self, model, x_0, args, file, mask, total_avg=2):
         """GaussianDiffusion.py:480-529: simplex frequencies 2^7..2^1 x t_distance 50..0.6T step 50, `total_avg` chains each -- all

@@ -75,6 +75,14 @@ mean and top-k mean of every image from ONE launch (`anoddpm_map_scores`: the k-
 the sums are fp64 in a fixed order), `image_auc` the AUROC of N such scores against N image labels (`roc_auc` of one segment).
 `PostProcess(gaussian=sigma)` puts the filter in front of the median; `score_maps(..., image_top=)` adds the image scores.
 
+Operating thresholds (the reference cuts every map at 0.5; `best_dice` needs the ground truth).  Unsupervised pipelines calibrate on
+healthy data: the operating threshold is the value that a chosen share of the pixels of a healthy validation set exceeds.
+`HealthyPool` collects those maps on the device, `HealthyPool.thresholds(fpr)` selects the values with the whole chip
+(`anoddpm_select_wide`, csrc/select_wide.hip: up to 16 order statistics of one segment of up to 2^31 - 1 values, integer counts only
+between workgroups, the fp64 sums in `image_scores`' order; `order_stats` is the primitive), and `counts_at` / `scores_at` /
+`anomaly_metrics_at` score maps at thresholds that stay on the device (`anoddpm_threshold_counts`: exact tp / fp for up to 16
+thresholds from one pass).  No result is copied to the host, and no threshold is read there.
+
 `score_maps` states the scoring pipeline once: R stacks of maps in, one launch per step whatever R is -- curve scores, SSIM, and
 opt-in the post-processing with its own curve scores, AUPRO and the boundary distances -- a dict of device tensors with a leading
 R axis out, without a host synchronisation; a score that cannot be computed has no key.  Its callers only say how a result
@@ -90,12 +98,13 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs, ErodeArgs, GaussArgs, MapScoresArgs, MedianArgs, ProArgs, RocArgs, SsimArgs,
-                   SurfaceArgs, check, current_stream, lib)
+from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs, ErodeArgs, GaussArgs, MapScoresArgs, MedianArgs, ProArgs, RocArgs, SelectArgs,
+                   SsimArgs, SurfaceArgs, ThresholdCountsArgs, check, current_stream, lib)
 
 __all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "PooledCurves", "PooledRegionCurves", "ssim", "median_filter", "erode_mask",
            "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "aupro", "pro_points", "AUPRO", "distance_transform",
-           "surface_distance", "HD95", "anomaly_metrics_surface", "gaussian_filter", "image_scores", "image_auc", "anomaly_metrics_image", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
+           "surface_distance", "HD95", "anomaly_metrics_surface", "gaussian_filter", "image_scores", "image_auc", "anomaly_metrics_image", "order_stats", "counts_at", "scores_at",
+           "anomaly_metrics_at", "HealthyPool", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
 
 NC = _lib.ANOMALY_NCOUNTS
@@ -642,6 +651,136 @@ def image_auc(labels, scores, return_status=False):
     return roc_auc(labels.reshape(-1), scores.reshape(-1), batched=False, return_status=return_status)
 
 
+# ---------------------------------------------------------------------------------- operating thresholds
+def _rank_table(ranks, n, dev, what):
+    """-> (int32 device tensor [Q] whose bits are the uint32 ranks, ctypes host copy or None).  A list (or a host tensor) is checked
+    here; a device tensor is never read on the host."""
+    if isinstance(ranks, torch.Tensor) and ranks.is_cuda:
+        if ranks.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8, torch.int8):
+            raise TypeError(f"{what}: a rank tensor holds integers, got {ranks.dtype}")
+        Q = ranks.numel()
+        if not 1 <= Q <= _lib.SELECT_MAX_RANKS:
+            raise ValueError(f"{what}: 1 ... {_lib.SELECT_MAX_RANKS} ranks per call, got {Q}")
+        if ranks.device != dev:
+            raise ValueError(f"{what}: ranks and score are on different devices")
+        # a rank outside [0, 2^31) becomes a pattern that is >= n: the kernel sets SELECT_BAD_RANK
+        return ranks.reshape(-1).to(torch.int64).clamp(min=-1, max=0x7fffffff).to(torch.int32).contiguous(), None
+    if isinstance(ranks, torch.Tensor):
+        ranks = ranks.reshape(-1).tolist()
+    ranks = [ranks] if isinstance(ranks, int) and not isinstance(ranks, bool) else list(ranks)
+    if not 1 <= len(ranks) <= _lib.SELECT_MAX_RANKS:
+        raise ValueError(f"{what}: 1 ... {_lib.SELECT_MAX_RANKS} ranks per call, got {len(ranks)}")
+    for r in ranks:
+        if isinstance(r, bool) or not isinstance(r, int) or not 0 <= r < n:
+            raise ValueError(f"{what}: rank {r!r} is outside 0 ... n - 1 = {n - 1}")
+    return torch.tensor(ranks, dtype=torch.int32, device=dev), (ctypes.c_uint32 * len(ranks))(*ranks)
+
+
+def order_stats(score, ranks, batched=None, tile=None, return_status=False):
+    """Order statistics of every segment, each selected by the whole chip (`anoddpm_select_wide`, csrc/select_wide.hip): score
+    [S, ...] (`batched`; the default is `roc_auc`'s), every value of `score[s]` pooled into segment s, 1 <= n < 2^31.  `ranks`: up
+    to 16 0-based positions from the top (0 is the maximum, k - 1 the k-th largest value), one table for all segments -- a list
+    of ints, checked here (ValueError for a rank outside 0 ... n - 1), or an integer device tensor, which is never read on the
+    host (a rank outside sets the status bit `SELECT_BAD_RANK`).  Returns a dict of device tensors, no host synchronisation, the
+    same bits every run: `value` [S, Q] fp32 (selected on the bit pattern; -0.0 counts as +0.0), `above` / `equal` [S, Q] int64
+    (`#{v > value}`, `#{v == value}`; `above <= rank < above + equal`), `topk` [S, Q] fp64 (the mean of the rank + 1 largest
+    values as a multiset), `max` [S] fp32, `mean` [S] fp64.  Sums in `image_scores`' order: up to 2^24 values and for one rank,
+    `topk`, `max` and `mean` have the bits `image_scores` returns for k = rank + 1.  Values must be finite and >= 0: the float
+    entries of a segment that breaks this are NaN and its status word is non-zero (`return_status=True` returns `(dict, status)`,
+    int32 [S]).  `tile`: values per workgroup, a multiple of 256 (None: the library's choice).  With a device `ranks` the call
+    only allocates and launches (graph-capture-safe)."""
+    if not isinstance(score, torch.Tensor):
+        raise TypeError("order_stats: score must be a device tensor")
+    S = score.shape[0] if _is_batched(score, batched) else 1
+    if score.numel() == 0 or S < 1:
+        raise ValueError("order_stats: empty score")
+    sc, n, s_stride = _segments(score, S, "order_stats(score)")
+    dev = sc.device
+    table, host = _rank_table(ranks, n, dev, "order_stats")
+    Q = table.numel()
+    tile = 0 if tile is None else int(tile)
+    nbytes = lib().anoddpm_select_wide_workspace_bytes(n, Q, tile)
+    if nbytes < 0:
+        raise ValueError(f"order_stats: segment length {n} is outside [1, 2^31), or tile {tile} is not a multiple of 256")
+    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    out = {"value": torch.empty((S, Q), dtype=torch.float32, device=dev), "above": torch.empty((S, Q), dtype=torch.int64, device=dev),
+           "equal": torch.empty((S, Q), dtype=torch.int64, device=dev), "topk": torch.empty((S, Q), dtype=torch.float64, device=dev),
+           "max": torch.empty((S,), dtype=torch.float32, device=dev), "mean": torch.empty((S,), dtype=torch.float64, device=dev)}
+    status = torch.empty((S,), dtype=torch.int32, device=dev)
+    a = SelectArgs()
+    a.src, a.ranks, a.ranks_host = sc.data_ptr(), table.data_ptr(), (ctypes.addressof(host) if host is not None else None)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    a.value, a.above, a.equal, a.topk_mean = out["value"].data_ptr(), out["above"].data_ptr(), out["equal"].data_ptr(), out["topk"].data_ptr()
+    a.max, a.mean, a.status = out["max"].data_ptr(), out["mean"].data_ptr(), status.data_ptr()
+    a.src_stride, a.n, a.S, a.Q = s_stride, n, S, Q
+    with torch.cuda.device(dev):
+        check(lib().anoddpm_select_wide(ctypes.byref(a), tile, current_stream()), "select_wide")
+    for key in ("value", "topk", "max", "mean"):
+        bad = (status != 0).reshape((S,) + (1,) * (out[key].dim() - 1))
+        out[key] = torch.where(bad, torch.full_like(out[key], float("nan")), out[key])
+    return (out, status) if return_status else out
+
+
+def counts_at(mask, score, thresholds, batched=None):
+    """True and false positives of the predictions `score > thresholds[j]` -- strict, as the reference's `sqerr > 0.5` -- for up
+    to 16 thresholds that live on the DEVICE, from one pass over the data (`anoddpm_threshold_counts`): score [S, ...] (`batched`
+    as `roc_auc`), mask of the same shape or of one segment's shape (shared), `thresholds` an fp32 device tensor [T] (one table
+    for all segments) or [S, T]; it is never read on the host.  Returns a dict of device tensors without a host synchronisation:
+    `tp`, `fp` [S, T] and `P`, `N` [S] (the mask's positives and negatives), int64 and exact, and `status` [S] int32
+    (`ROC_BAD_MASK`, `ROC_NAN`; a NaN score is never predicted)."""
+    if not isinstance(score, torch.Tensor) or not isinstance(mask, torch.Tensor) or not isinstance(thresholds, torch.Tensor):
+        raise TypeError("counts_at: mask, score and thresholds must be device tensors")
+    S = score.shape[0] if _is_batched(score, batched) else 1
+    if score.numel() == 0 or S < 1:
+        raise ValueError("counts_at: empty score")
+    sc, n, s_stride = _segments(score, S, "counts_at(score)")
+    if mask.numel() == S * n:
+        mk, _, m_stride = _segments(mask, S, "counts_at(mask)")
+    elif mask.numel() == n:
+        mk, _, _ = _segments(mask, 1, "counts_at(mask)")
+        m_stride = 0
+    else:
+        raise ValueError(f"counts_at: mask of {mask.numel()} elements does not match score {tuple(score.shape)}")
+    th = _f32c(thresholds, "counts_at(thresholds)")
+    if th.dim() == 2 and th.shape[0] == S and S > 1:
+        T, t_stride = th.shape[1], th.shape[1]
+    elif th.dim() <= 1 or (th.dim() == 2 and th.shape[0] == 1):
+        th = th.reshape(-1)
+        T, t_stride = th.numel(), 0
+    else:
+        raise ValueError(f"counts_at: thresholds {tuple(thresholds.shape)} are neither [T] nor [S, T] for S = {S}")
+    if not 1 <= T <= _lib.THRESHOLD_COUNTS_MAX:
+        raise ValueError(f"counts_at: 1 ... {_lib.THRESHOLD_COUNTS_MAX} thresholds per call, got {T}")
+    if mk.device != sc.device or th.device != sc.device:
+        raise ValueError("counts_at: mask, score and thresholds are on different devices")
+    dev = sc.device
+    counts = torch.empty((S, T, 2), dtype=torch.int64, device=dev)
+    totals = torch.empty((S, 2), dtype=torch.int64, device=dev)
+    status = torch.empty((S,), dtype=torch.int32, device=dev)
+    a = ThresholdCountsArgs()
+    a.score, a.mask, a.thr = sc.data_ptr(), mk.data_ptr(), th.data_ptr()
+    a.counts, a.totals, a.status = counts.data_ptr(), totals.data_ptr(), status.data_ptr()
+    a.n, a.score_stride, a.mask_stride, a.thr_stride, a.S, a.T = n, s_stride, m_stride, t_stride, S, T
+    _launch("threshold_counts", a, dev)
+    return {"tp": counts[:, :, 0], "fp": counts[:, :, 1], "P": totals[:, 0], "N": totals[:, 1], "status": status}
+
+
+def scores_at(mask, score, thresholds, batched=None):
+    """`counts_at` and the scores that follow from its counts, as fp64 device tensors [S, T] without a host synchronisation:
+    `dice` = 2 tp / (tp + fp + P) (`best_dice`'s definition, so never above it; NaN when P = 0), `precision` = tp / (tp + fp) (NaN
+    when nothing is predicted), `recall` = tp / P and `fpr` = fp / N (NaN for an empty class).  All four are NaN in a segment
+    whose status word is non-zero."""
+    o = counts_at(mask, score, thresholds, batched)
+    tp, fp = o["tp"].double(), o["fp"].double()
+    P, N = o["P"].double()[:, None], o["N"].double()[:, None]
+    nan = torch.full_like(tp, float("nan"))
+    bad = (o["status"] != 0)[:, None]
+    ratios = {"dice": ((2 * o["tp"]).double() / (o["tp"] + o["fp"] + o["P"][:, None]).double(), P == 0),
+              "precision": (tp / (tp + fp), (tp + fp) == 0), "recall": (tp / P, P == 0), "fpr": (fp / N, N == 0)}
+    o.update({k: torch.where(empty | bad, nan, v) for k, (v, empty) in ratios.items()})
+    return o
+
+
 class _PostProcessType(type):
     """`PostProcess(..., gaussian=sigma)`: the trailing keyword is taken here, by the call of the class, and `__init__` keeps the
     five positional settings and the signature it has had since it was written (callers and tests read it with `inspect`)."""
@@ -1112,6 +1251,26 @@ def anomaly_metrics_image(real, recon, mask, threshold=0.5, postprocess=None, ro
     return _metrics(real, recon, mask, threshold, postprocess, roi, image_top=image_top)
 
 
+_AT_KEYS = ("dice", "precision", "recall", "fpr")
+
+
+def anomaly_metrics_at(real, recon, mask, thresholds, postprocess=None, roi=None):
+    """`anomaly_metrics` with the scores at calibrated operating thresholds beside its results -- a function of its own, as
+    `anomaly_metrics_pro` is.  `thresholds`: an fp32 device tensor [T] (`HealthyPool.thresholds`), never read on the host.  ADDS
+    `dice_at`, `precision_at`, `recall_at`, `fpr_at` -- fp64 device tensors [T], `scores_at` of `maps["sqerr"]` with the whole
+    batch pooled into one segment, as `AUC` pools it -- and `tp_at`, `fp_at` (int64 [T]), the counts behind them; with
+    `postprocess` also their `_pp` forms on `maps["sqerr_pp"]` (the filtered map cut at every threshold; small components are not
+    removed, that step takes one host threshold).  Without a mask every pixel is a negative: only `fpr_at` is a number."""
+    r = _metrics(real, recon, mask, 0.5, postprocess, roi)
+    for sfx in ("", "_pp") if postprocess is not None else ("",):
+        sq = r["maps"]["sqerr" + sfx]
+        mk = mask if mask is not None else torch.zeros_like(sq)
+        o = scores_at(mk.reshape(1, -1), sq.reshape(1, -1), thresholds.reshape(-1), batched=True)
+        for k in _AT_KEYS + ("tp", "fp"):
+            r[k + "_at" + sfx] = o[k][0]
+    return r
+
+
 # ---------------------------------------------------------------------------------- evaluation.py surface
 def heatmap(real, recon, mask, filename, save=True):
     """evaluation.py:12-22 computes the squared-error / threshold images, plots them and returns None.  The images come from the
@@ -1328,6 +1487,69 @@ class PooledRegionCurves(PooledCurves):
 
     def pro_curve(self, limit=0.3):
         return _pro_points_of(self._pro(limit, True, "pro_curve"))[0]
+
+
+class HealthyPool:
+    """The score maps of a HEALTHY validation run collected into one segment, to calibrate operating thresholds without ground
+    truth: an fp32 device buffer of `capacity` pixels (`PooledCurves`' buffer handling, without a mask).  `add(score)` appends a
+    device tensor of any shape without a host synchronisation and raises ValueError, from the count kept on the host, when the
+    buffer would overflow; `len()` is the number of pixels held, `reset()` empties the pool.
+    `thresholds(fpr, negatives=None)`: for every requested false-positive rate (a number or up to 16 of them) the operating
+    threshold as a [Q] fp32 device tensor -- with `k = floor(fpr * negatives)` in Python floats (`negatives` defaults to
+    `len(pool)`), the pooled value of descending rank k: the smallest pooled value that at most k pooled values exceed, so the
+    prediction `score > threshold` marks at most that share of the healthy pixels.  `fpr = 0` gives the pool's maximum; a rate
+    whose k reaches `len(pool)` is a ValueError.  Pass the number of region-of-interest pixels as `negatives` when the maps were
+    zeroed outside it: the zeros sit at the bottom and do not move the k-th largest value.  `order_stats(ranks)` is the primitive
+    underneath: `metrics.order_stats` of the pooled segment."""
+
+    def __init__(self, capacity, device=None):
+        capacity = int(capacity)
+        if capacity < 1 or capacity >= _ROC_WIDE_NEVER:
+            raise ValueError(f"HealthyPool: capacity must be in [1, 2^31), got {capacity}")
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("HealthyPool: the buffer lives on the device")
+        self._score = torch.empty((capacity,), dtype=torch.float32, device=device)
+        self._n = 0
+
+    capacity = property(lambda self: self._score.numel())
+
+    def __len__(self):
+        return self._n
+
+    def reset(self):
+        self._n = 0
+
+    def add(self, score):
+        if not isinstance(score, torch.Tensor) or not score.is_cuda:
+            raise TypeError("HealthyPool.add: score must be a device tensor")
+        k = score.numel()
+        if k == 0:
+            raise ValueError("HealthyPool.add: empty score")
+        if self._n + k > self.capacity:
+            raise ValueError(f"HealthyPool.add: {self._n} + {k} pixels exceed the capacity {self.capacity}")
+        self._score[self._n:self._n + k].copy_(score.reshape(-1))
+        self._n += k
+
+    def order_stats(self, ranks, tile=None, return_status=False):
+        if self._n == 0:
+            raise ValueError("HealthyPool.order_stats: the pool is empty")
+        return order_stats(self._score[:self._n], ranks, batched=False, tile=tile, return_status=return_status)
+
+    def thresholds(self, fpr, negatives=None):
+        rates = [fpr] if isinstance(fpr, (int, float)) else list(fpr)
+        negatives = self._n if negatives is None else negatives
+        if isinstance(negatives, bool) or not isinstance(negatives, int) or negatives < 1:
+            raise ValueError(f"HealthyPool.thresholds: negatives must be a positive int, got {negatives!r}")
+        ranks = []
+        for f in rates:
+            if isinstance(f, bool) or not isinstance(f, (int, float)) or not 0.0 <= float(f) <= 1.0:
+                raise ValueError(f"HealthyPool.thresholds: a false-positive rate is a number in [0, 1], got {f!r}")
+            k = int(float(f) * float(negatives))
+            if k >= self._n:
+                raise ValueError(f"HealthyPool.thresholds: rate {f!r} of {negatives} pixels is rank {k}, the pool holds {self._n}")
+            ranks.append(k)
+        return self.order_stats(ranks)["value"][0]
 
 
 def ROC_AUC(real_mask, square_error):

@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 36
+#define ANODDPM_ABI_VERSION 37
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -1002,6 +1002,85 @@ typedef struct anoddpm_map_scores_args {
 
 int anoddpm_gauss2d(const anoddpm_gauss_args *a, void *stream);
 int anoddpm_map_scores(const anoddpm_map_scores_args *a, void *stream);
+
+/* ------------------------------------------------------------------ operating thresholds from a pooled segment, scores at them
+ * The evaluation protocol of unsupervised anomaly segmentation (the reference has no counterpart: it cuts every map at 0.5): the
+ * operating threshold is the value that a chosen share of the pixels of a HEALTHY validation set exceeds, and the test maps are
+ * scored at it.  csrc/select_wide.hip.
+ *
+ * anoddpm_select_wide: order statistics of S segments of n contiguous fp32 values at src + s * src_stride, 1 <= n < 2^31, each
+ *   selected by the whole chip; the S segments are processed one after another on `stream` and share ONE segment's workspace.
+ *     ranks       [dev] Q uint32 ranks, 1 <= Q <= ANODDPM_SELECT_MAX_RANKS, one table for all segments; the kernels only read it.
+ *                 Rank r is the 0-based position from the top: 0 is the maximum, k - 1 is anoddpm_map_scores' v_k.  Ranks may
+ *                 repeat.  Every rank must be below n:
+ *     ranks_host  [host] the same Q ranks, or NULL.  Given, a rank >= n is refused before anything is launched.  NULL, such a
+ *                 rank sets ANODDPM_SELECT_BAD_RANK in status[s] and leaves value / above / equal / topk_mean of THAT rank
+ *                 unspecified; nothing is read or written outside the buffers either way.
+ *     value[s][q]      fp32, the value of descending rank r_q, SELECTED on the 31-bit pattern (sign dropped: -0.0 is +0.0)
+ *     above[s][q]      int64, #{v > value};  equal[s][q]  int64, #{v == value}.   above <= r_q < above + equal
+ *     topk_mean[s][q]  fp64, with k = r_q + 1:  (sum over v > value of v  +  (k - above) * value) / k
+ *     max[s]  fp32,  mean[s]  fp64 sum / n,  status[s]: ANODDPM_ROC_NAN / _INF / _NEGATIVE as anoddpm_map_scores (the other
+ *                 outputs of such a segment are unspecified; no other segment is touched), and ANODDPM_SELECT_BAD_RANK
+ *   Order of additions: anoddpm_map_scores', continued beyond its limit -- virtual thread t of 1024 adds the elements t, t + 1024,
+ *   ... in that order, a halving tree folds the 64 partials of a wave and then the 16 wave sums.  So for n <=
+ *   ANODDPM_MAP_SCORES_MAX_N and Q = 1 every output shared with anoddpm_map_scores has the bits it writes for k = r + 1.
+ *   Launches, 11 per segment whatever Q is: a clear; four times a histogram launch with one workgroup per tile (for every rank the
+ *   256 bins of the pass's byte among the values that match the rank's prefix, LDS integer atomics, then integer adds into a
+ *   [Q][256] table) and a one-workgroup launch that picks every rank's bin; the sums, 16 workgroups that are the 16 waves of the
+ *   order above and read the segment in place; a one-workgroup finish.  Counts, status bits and the maximum cross workgroups as
+ *   integers only; a launch boundary is the only ordering between workgroups.
+ *     tile        values per workgroup of the histogram launches: any multiple of 256, or 0 for the library's choice -- n / 2048
+ *                 rounded up to a multiple of 256, at least 1024 and at most 16384.  There is no cap on the tile count (at most
+ *                 2^23 workgroups), so every n < 2^31 is accepted at every tile.
+ *     workspace   [dev] anoddpm_select_wide_workspace_bytes(n, Q, tile) bytes, 16-byte aligned: four [Q][256] counter tables,
+ *                 Q state records and (Q + 1) x 16 wave sums -- 4240 Q + 144 bytes, whatever n and S are.
+ *   Refused before anything is launched: null pointers, S < 1, n outside 1 ... 2^31 - 1, Q outside 1 ... 16, a tile that is
+ *   negative or no multiple of 256, src_stride < n with S > 1, a workspace too small or misaligned, a rank >= n in ranks_host.
+ *
+ * anoddpm_threshold_counts: S score segments of n fp32 values (score_stride) against a 0 / 1 fp32 mask (mask_stride, 0 = one
+ *   mask for every segment) at T thresholds read from DEVICE memory, 1 <= T <= ANODDPM_THRESHOLD_COUNTS_MAX: thr + s * thr_stride,
+ *   thr_stride 0 = one table for every segment, else >= T.  The prediction at threshold j is score > thr[j] -- strict, as
+ *   detection.py:232: a score equal to the threshold is not predicted, nor is a NaN score.
+ *     counts[s][j]  int64 {tp, fp}: predicted pixels with mask != 0 / with mask == 0
+ *     totals[s]     int64 {P, N}: pixels with mask != 0 / with mask == 0
+ *     status[s]     ANODDPM_ROC_BAD_MASK (a mask value other than 0 and 1), ANODDPM_ROC_NAN (a NaN score)
+ *   All counts are exact.  Two launches: a clear of the outputs, then ONE pass over the data whatever T is, grid segments x tiles
+ *   of 4096 values; counts are reduced per wave and per workgroup and added to the outputs as integers.  1 <= n < 2^31, S * tiles
+ *   below 2^31.
+ * No allocation and no host synchronisation in either: both are legal inside stream capture. */
+#define ANODDPM_SELECT_MAX_RANKS 16
+#define ANODDPM_SELECT_BAD_RANK 32
+#define ANODDPM_THRESHOLD_COUNTS_MAX 16
+typedef struct anoddpm_select_args {
+    const float *src;               /* [dev] */
+    const uint32_t *ranks;          /* [dev] [Q] */
+    const uint32_t *ranks_host;     /* [host] [Q] or NULL */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    float *value;                   /* [dev] [S][Q] */
+    int64_t *above, *equal;         /* [dev] [S][Q] */
+    double *topk_mean;              /* [dev] [S][Q] */
+    float *max;                     /* [dev] [S] */
+    double *mean;                   /* [dev] [S] */
+    int32_t *status;                /* [dev] [S] */
+    int64_t src_stride, n;
+    int32_t S, Q;
+} anoddpm_select_args;
+
+typedef struct anoddpm_threshold_counts_args {
+    const float *score;             /* [dev] */
+    const float *mask;              /* [dev] */
+    const float *thr;               /* [dev] [T], or [S] tables thr_stride apart */
+    int64_t *counts;                /* [dev] [S][T][2] */
+    int64_t *totals;                /* [dev] [S][2] */
+    int32_t *status;                /* [dev] [S] */
+    int64_t n, score_stride, mask_stride, thr_stride;
+    int32_t S, T;
+} anoddpm_threshold_counts_args;
+
+int anoddpm_select_wide(const anoddpm_select_args *a, int32_t tile, void *stream);
+int64_t anoddpm_select_wide_workspace_bytes(int64_t n, int32_t Q, int32_t tile);   /* HOST function; -1 where the call would be refused */
+int anoddpm_threshold_counts(const anoddpm_threshold_counts_args *a, void *stream);
 
 /* Variational-bound terms of one reverse step (GaussianDiffusion.py:384-397 calc_vlb_xt, and the two MSE curves of
  * calc_total_vlb :445-478): per sample b
