@@ -31,7 +31,7 @@ class AnoddpmError(RuntimeError):
 # ---- a reader of the restricted C the header is written in: whatever it does not recognise is an error, never skipped
 _SCALARS = {"int": c_int, "int16_t": c_int16, "int32_t": c_int32, "int64_t": c_int64, "uint32_t": c_uint32, "uint64_t": c_uint64,
             "float": c_float, "double": c_double}
-_POINTEES = set(_SCALARS) | {"void", "char", "long long"}      # what a pointer may point to, besides the header's own structs
+_POINTEES = set(_SCALARS) | {"void", "char", "long long", "uint8_t"}      # what a pointer may point to, besides the header's own structs
 
 
 def _int(text):
@@ -122,7 +122,7 @@ _STRUCTS = [globals()[_py] for _py in _PYNAME.values()]
 SYMBOLS = list(_PROTOS)
 
 # limits and selectors the header states in prose only
-PHILOX_REVERSE, PHILOX_FORWARD, PHILOX_FILL = 0, 1, 2                                   # the `domain` word of the philox counter
+PHILOX_REVERSE, PHILOX_FORWARD, PHILOX_FILL, PHILOX_KNOWN = 0, 1, 2, 3                                # the `domain` word of the philox counter
 SSIM_MAX_WIN = 15
 MEDIAN_SIZES = (3, 5, 7)                                                                # anoddpm_median_args.k
 ERODE_MAX = 8                                                                           # anoddpm_erode_args.n

@@ -254,18 +254,16 @@ __device__ __forceinline__ void reverse_store1(const anoddpm_p_update_args &a, c
     if (a.mean_out) a.mean_out[i] = mu;
 }
 
-// GAUSS: a.noise is NULL; the step noise comes from `key` at (stream of sample b, step = normalised t[b]).  It is generated at
-// t == 0 too, where sigma is 0: mean + 0 * nz keeps the sign-of-zero behaviour of the unfused pair.
-// STRIDED: the coefficients come from `sa` (thread 0 forms them in fp64, once per workgroup) instead of c_coef1 / c_coef2 /
-// c_sigma; where sigma is 0 the noise is neither read nor generated.
-template <int VEC, bool GAUSS, bool STRIDED>
-__global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a, PhiloxKey key, StridedArgs sa)
+// The prologue of every update kernel: sample b's timestep normalised (`ti`; 0 where it was out of range, `bad`) and the step's
+// coefficients.  STRIDED: they come from `sa` (thread 0 forms them in fp64, once per workgroup) instead of c_coef1 / c_coef2 /
+// c_sigma.
+template <bool STRIDED>
+__device__ __forceinline__ StepCoef step_coef(const anoddpm_p_update_args &a, const StridedArgs &sa, int b, long long &ti, bool &bad)
 {
-    const int b = blockIdx.y;
-    long long ti = a.t[b];
+    ti = a.t[b];
     const bool nonzero = (ti != 0);
     ti = ti < 0 ? ti + a.T : ti;
-    const bool bad = ti < 0 || ti >= a.T;            // out of range: no out-of-bounds read, NaN result (see q_sample_kernel)
+    bad = ti < 0 || ti >= a.T;                       // out of range: no out-of-bounds read, NaN result (see q_sample_kernel)
     ti = bad ? 0 : ti;
     StepCoef k;
     k.recip = bad ? __builtin_nanf("") : a.c_recip[ti];
@@ -282,6 +280,19 @@ __global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a, 
         k.coef2 = a.c_coef2[ti];
         k.sigma = nonzero ? a.c_sigma[ti] : 0.0f;    // (t != 0).float() * exp(0.5*logvar)
     }
+    return k;
+}
+
+// GAUSS: a.noise is NULL; the step noise comes from `key` at (stream of sample b, step = normalised t[b]).  It is generated at
+// t == 0 too, where sigma is 0: mean + 0 * nz keeps the sign-of-zero behaviour of the unfused pair.
+// STRIDED: the coefficients come from `sa` (step_coef); where sigma is 0 the noise is neither read nor generated.
+template <int VEC, bool GAUSS, bool STRIDED>
+__global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a, PhiloxKey key, StridedArgs sa)
+{
+    const int b = blockIdx.y;
+    long long ti;
+    bool bad;
+    const StepCoef k = step_coef<STRIDED>(a, sa, b, ti, bad);
     const bool noisy = !STRIDED || k.sigma != 0.0f;
     const int64_t base = (int64_t)b * a.n;
     if (GAUSS) {
@@ -307,6 +318,100 @@ __global__ __launch_bounds__(256) void p_update_kernel(anoddpm_p_update_args a, 
             reverse_store4<STRIDED>(a, k, base + i, nv);
         } else {
             reverse_store1<STRIDED>(a, k, base + i, a.noise && noisy ? a.noise[base + i] : 0.0f);
+        }
+    }
+}
+
+// ---------------------------------------------------------------- known-region conditioning
+// RePaint (Lugmayr et al., CVPR 2022, Algorithm 1 / eq. 8) and the "stitch" of AutoDDPM (Bercea et al., 2023) on the reverse update
+// of GaussianDiffusion.py:298-318: the pixels marked "keep" leave the step as the input image noised to the timestep s the step
+// lands on (the q-sample of GaussianDiffusion.py:361-371), every other pixel as the ordinary update.  One sample's share of it:
+struct KnownSample {
+    const float *x0, *noise;     // this sample's planes; noise NULL: not read (s < 0, a poisoned sample, or generated)
+    const uint8_t *keep;
+    float qa, qc;                // ca[s], cb[s]
+    bool exact, poison;          // s < 0: the kept pixels are x0 itself; poison: every element of the sample is NaN
+};
+
+// x_prev of one element: a select, so that a NaN in `u` under a kept pixel, or in `x0` / `kz` under any other, stays where it is
+__device__ __forceinline__ float known_one(float u, float x0, float kz, bool kept, const KnownSample &ks)
+{
+    const float kn = ks.exact ? x0 : ks.qa * x0 + ks.qc * kz;
+    return ks.poison ? __builtin_nanf("") : (kept ? kn : u);
+}
+
+// A sibling of p_update_kernel over the same prologue and reverse_one, one thread per quad in every form.  GAUSS: the step noise is
+// generated as there (domain 0, step ti); the known-region noise is kr.noise, or with GAUSS and kr.noise NULL generated from the same
+// key in domain 3 at step s.
+template <int VEC, bool GAUSS, bool STRIDED>
+__global__ __launch_bounds__(256) void p_update_known_kernel(anoddpm_p_update_args a, anoddpm_known_args kr, PhiloxKey key, StridedArgs sa)
+{
+    const int b = blockIdx.y;
+    long long ti;
+    bool bad;
+    const StepCoef k = step_coef<STRIDED>(a, sa, b, ti, bad);
+    const bool noisy = !STRIDED || k.sigma != 0.0f;
+    long long stride = 1;
+    if constexpr (STRIDED) stride = *sa.stride;
+    KnownSample ks;
+    ks.poison = bad || stride < 1;
+    const long long s = ks.poison ? -1 : ti - stride;          // < a.T: never outside the tables
+    const bool noised = s >= 0;
+    ks.exact = !ks.poison && !noised;
+    ks.qa = noised ? kr.ca[s] : 0.0f;
+    ks.qc = noised ? kr.cb[s] : 0.0f;
+    ks.x0 = kr.x0 + (int64_t)b * kr.x0_stride;
+    ks.keep = kr.keep + (int64_t)b * kr.keep_stride;
+    ks.noise = noised && kr.noise ? kr.noise + (int64_t)b * kr.noise_stride : nullptr;
+    const bool kgen = GAUSS && noised && !kr.noise;
+    PhiloxSample ps = {}, pk = {};
+    if (GAUSS) {
+        ps = philox_sample(key, b, (uint32_t)ti);
+        pk = ps;
+        pk.step = (uint32_t)(noised ? s : 0);
+        pk.domain = 3u;                                          // known-region noise
+    }
+    const float *step_noise = !GAUSS && a.noise && noisy ? a.noise + (int64_t)b * a.n : nullptr;
+    const int64_t base = (int64_t)b * a.n;
+    const int64_t nq = (a.n + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f}, w[4] = {0.f, 0.f, 0.f, 0.f};
+        if (GAUSS && noisy) philox_normals(ps, (uint32_t)q, z);
+        if (kgen) philox_normals(pk, (uint32_t)q, w);
+        const int64_t j = 4 * q, i = base + j;
+        if (VEC == 4) {
+            if (step_noise) {
+                const float4 nv = *reinterpret_cast<const float4 *>(step_noise + j);
+                z[0] = nv.x, z[1] = nv.y, z[2] = nv.z, z[3] = nv.w;
+            }
+            if (ks.noise) {
+                const float4 nv = *reinterpret_cast<const float4 *>(ks.noise + j);
+                w[0] = nv.x, w[1] = nv.y, w[2] = nv.z, w[3] = nv.w;
+            }
+            const float4 xv = *reinterpret_cast<const float4 *>(a.x_t + i);
+            const float4 ev = *reinterpret_cast<const float4 *>(a.eps + i);
+            const float4 cv = *reinterpret_cast<const float4 *>(ks.x0 + j);
+            const uint32_t kb = *reinterpret_cast<const uint32_t *>(ks.keep + j);
+            float4 o, p0, mu;
+            o.x = known_one(reverse_one<STRIDED>(xv.x, ev.x, z[0], k, &p0.x, &mu.x), cv.x, w[0], (kb & 0x000000ffu) != 0, ks);
+            o.y = known_one(reverse_one<STRIDED>(xv.y, ev.y, z[1], k, &p0.y, &mu.y), cv.y, w[1], (kb & 0x0000ff00u) != 0, ks);
+            o.z = known_one(reverse_one<STRIDED>(xv.z, ev.z, z[2], k, &p0.z, &mu.z), cv.z, w[2], (kb & 0x00ff0000u) != 0, ks);
+            o.w = known_one(reverse_one<STRIDED>(xv.w, ev.w, z[3], k, &p0.w, &mu.w), cv.w, w[3], (kb & 0xff000000u) != 0, ks);
+            *reinterpret_cast<float4 *>(a.x_prev + i) = o;
+            if (a.pred_x0) *reinterpret_cast<float4 *>(a.pred_x0 + i) = p0;
+            if (a.mean_out) *reinterpret_cast<float4 *>(a.mean_out + i) = mu;
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                if (j + l < a.n) {
+                    float p0, mu;
+                    const float nz = step_noise ? step_noise[j + l] : z[l];
+                    const float u = reverse_one<STRIDED>(a.x_t[i + l], a.eps[i + l], nz, k, &p0, &mu);
+                    a.x_prev[i + l] = known_one(u, ks.x0[j + l], ks.noise ? ks.noise[j + l] : w[l], ks.keep[j + l] != 0, ks);
+                    if (a.pred_x0) a.pred_x0[i + l] = p0;
+                    if (a.mean_out) a.mean_out[i + l] = mu;
+                }
+            }
         }
     }
 }
@@ -674,13 +779,12 @@ static void p_update_dispatch(bool v4, unsigned gx, const anoddpm_p_update_args 
         hipLaunchKernelGGL((p_update_kernel<1, GAUSS, STRIDED>), dim3(gx, a.B), dim3(256), 0, anoddpm::as_stream(stream), a, key, sa);
 }
 
-// key == nullptr: the noise tensor a->noise (or none); else the step noise is generated in the kernel.  sa == nullptr: the
-// ancestral update from the c_coef1 / c_coef2 / c_sigma tables; else the strided sampler's, which ignores those three.
-static int p_update_launch(const anoddpm_p_update_args *a, const PhiloxKey *key, const StridedArgs *sa, void *stream, const char *who)
+// The argument checks every update launch shares.  -> EINVAL, 1 for an empty batch (nothing to launch), else 0.
+static int p_update_check(const anoddpm_p_update_args *a, const PhiloxKey *key, const StridedArgs *sa, const char *who)
 {
     ANODDPM_REQUIRE(a, "%s: null argument struct", who);
     ANODDPM_REQUIRE(a->B >= 0 && a->n >= 0 && a->T > 0, "%s: bad sizes", who);
-    if (a->B == 0 || a->n == 0) return ANODDPM_OK;
+    if (a->B == 0 || a->n == 0) return 1;
     ANODDPM_REQUIRE(a->x_prev && a->x_t && a->eps && a->t, "%s: null pointer", who);
     ANODDPM_REQUIRE(a->c_recip && a->c_recipm1, "%s: null table", who);
     if (sa)
@@ -688,13 +792,27 @@ static int p_update_launch(const anoddpm_p_update_args *a, const PhiloxKey *key,
     else
         ANODDPM_REQUIRE(a->c_coef1 && a->c_coef2 && a->c_sigma, "%s: null table", who);
     ANODDPM_REQUIRE(a->B <= 65535, "%s: B > 65535", who);
-    const bool v4 = (a->n % 4 == 0) && aligned16(a->x_prev) && aligned16(a->x_t) && aligned16(a->eps) &&
-                    (!a->noise || aligned16(a->noise)) && (!a->pred_x0 || aligned16(a->pred_x0)) &&
-                    (!a->mean_out || aligned16(a->mean_out));
-    const StridedArgs no_stride = {};
     if (key) {
         if (const int rc = philox_key_check(key->seed, a->n, who)) return rc;
         ANODDPM_REQUIRE(!a->noise, "%s: a noise tensor was given as well", who);
+    }
+    return 0;
+}
+
+static bool p_update_v4(const anoddpm_p_update_args *a)
+{
+    return (a->n % 4 == 0) && aligned16(a->x_prev) && aligned16(a->x_t) && aligned16(a->eps) &&
+           (!a->noise || aligned16(a->noise)) && (!a->pred_x0 || aligned16(a->pred_x0)) && (!a->mean_out || aligned16(a->mean_out));
+}
+
+// key == nullptr: the noise tensor a->noise (or none); else the step noise is generated in the kernel.  sa == nullptr: the
+// ancestral update from the c_coef1 / c_coef2 / c_sigma tables; else the strided sampler's, which ignores those three.
+static int p_update_launch(const anoddpm_p_update_args *a, const PhiloxKey *key, const StridedArgs *sa, void *stream, const char *who)
+{
+    if (const int rc = p_update_check(a, key, sa, who)) return rc < 0 ? rc : ANODDPM_OK;
+    const bool v4 = p_update_v4(a);
+    const StridedArgs no_stride = {};
+    if (key) {
         const unsigned gx = grid_x((a->n + 3) / 4);
         if (sa)
             p_update_dispatch<true, true>(v4, gx, *a, *key, *sa, stream);
@@ -730,6 +848,44 @@ extern "C" int anoddpm_strided_update(const anoddpm_p_update_args *a, const doub
     if (!seed) return p_update_launch(a, nullptr, &sa, stream, "strided_update");
     const PhiloxKey key = {seed, streams, stream0, 0u};       // domain 0, as the ancestral update: the keying is the same
     return p_update_launch(a, &key, &sa, stream, "strided_update");
+}
+
+template <bool GAUSS, bool STRIDED>
+static void p_update_known_dispatch(bool v4, unsigned gx, const anoddpm_p_update_args &a, const anoddpm_known_args &k,
+                                    const PhiloxKey &key, const StridedArgs &sa, void *stream)
+{
+    if (v4)
+        hipLaunchKernelGGL((p_update_known_kernel<4, GAUSS, STRIDED>), dim3(gx, a.B), dim3(256), 0, anoddpm::as_stream(stream), a, k, key, sa);
+    else
+        hipLaunchKernelGGL((p_update_known_kernel<1, GAUSS, STRIDED>), dim3(gx, a.B), dim3(256), 0, anoddpm::as_stream(stream), a, k, key, sa);
+}
+
+extern "C" int anoddpm_p_sample_update_known(const anoddpm_p_update_args *a, const anoddpm_known_args *k, const double *alphas_cumprod,
+                                             const int32_t *stride, const float *eta, const uint64_t *seed, const int32_t *streams,
+                                             uint32_t stream0, void *stream)
+{
+    const char *who = "p_sample_update_known";
+    ANODDPM_REQUIRE(k, "%s: null known-region struct", who);
+    const bool strided = alphas_cumprod || stride || eta;
+    ANODDPM_REQUIRE(!strided || (alphas_cumprod && stride && eta), "%s: alphas_cumprod, stride and eta are all set or all NULL", who);
+    ANODDPM_REQUIRE(seed || k->noise, "%s: no known-region noise tensor and no seed to generate it from", who);
+    const StridedArgs sa = {alphas_cumprod, stride, eta};
+    const PhiloxKey key = {seed, streams, stream0, 0u};       // domain 0 for the step noise; the kernel takes domain 3 for the known region's
+    const int rc = p_update_check(a, seed ? &key : nullptr, strided ? &sa : nullptr, who);
+    if (rc < 0) return rc;
+    ANODDPM_REQUIRE(k->x0 && k->keep && k->ca && k->cb, "%s: null x0 / keep / ca / cb", who);
+    for (const int64_t w : {k->x0_stride, k->keep_stride, k->noise_stride})
+        ANODDPM_REQUIRE(w == 0 || w == a->n, "%s: a sample stride of %lld is neither 0 nor n", who, (long long)w);
+    if (rc) return ANODDPM_OK;
+    const bool v4 = p_update_v4(a) && aligned16(k->x0) && (!k->noise || aligned16(k->noise)) && ((uintptr_t)k->keep & 3) == 0;
+    const unsigned gx = grid_x((a->n + 3) / 4);
+    if (seed)
+        strided ? p_update_known_dispatch<true, true>(v4, gx, *a, *k, key, sa, stream)
+                : p_update_known_dispatch<true, false>(v4, gx, *a, *k, key, sa, stream);
+    else
+        strided ? p_update_known_dispatch<false, true>(v4, gx, *a, *k, key, sa, stream)
+                : p_update_known_dispatch<false, false>(v4, gx, *a, *k, key, sa, stream);
+    return anoddpm::check_launch(who);
 }
 
 extern "C" int anoddpm_chain_advance(int64_t *t, int32_t B, int32_t *step, void *stream)

@@ -28,10 +28,10 @@ import numpy as np
 import torch
 
 from . import _lib, philox
-from ._lib import LossArgs, PUpdateArgs, VlbArgs, check, current_stream, lib, ptr
+from ._lib import KnownArgs, LossArgs, PUpdateArgs, VlbArgs, check, current_stream, lib, ptr
 from .simplex import Simplex_CLASS, perm_tables
 
-__all__ = ["SimplexNoiseFn", "GaussNoiseFn", "ReverseChain", "StridedSampler", "get_beta_schedule", "extract", "mean_flat", "normal_kl", "approx_standard_normal_cdf",
+__all__ = ["SimplexNoiseFn", "GaussNoiseFn", "ReverseChain", "StridedSampler", "KnownRegion", "get_beta_schedule", "extract", "mean_flat", "normal_kl", "approx_standard_normal_cdf",
            "discretised_gaussian_log_likelihood", "generate_simplex_noise", "random_noise",
            "GaussianDiffusionModel"]
 
@@ -222,6 +222,66 @@ def _check_sampler(sampler):
     return sampler
 
 
+class KnownRegion:
+    """Opt-in known-region conditioning of the reverse chain (RePaint, Lugmayr et al., CVPR 2022, Algorithm 1 / eq. 8; the
+    "stitch" of AutoDDPM, Bercea et al., 2023); immutable.  At the step from t to s (t - 1, or t - stride) the pixels
+    marked in `keep` leave the step as `x_0` noised to s -- `x_0` itself once s < 0 -- and every other pixel as the ordinary update;
+    both happen in the one fused update launch.
+      x_0    [B or 1, C, H, W], stored as fp32
+      keep   [B or 1, C or 1, H, W], any dtype: stored as bytes `!= 0`, broadcast over the channels here, once
+      noise  "fixed": one plane per sample for the whole chain -- the chain's forward noise (forward_backward hands over the one
+             it noised `x` with; a chain built directly draws `noise_fn(x_0, t_distance - 1)` once);
+             "fresh": a new draw per step, made inside the kernel from the seeded stream (domain 3): seeded owners only;
+             a tensor [B or 1, C, H, W]: that plane, as "fixed".
+    A hard select, no resampling jumps, single chains only (not the slot-batched detection sweeps).  What it does to detection
+    quality has not been measured."""
+    __slots__ = ("x_0", "keep", "noise")
+
+    def __init__(self, x_0, keep, noise="fixed"):
+        if not torch.is_tensor(x_0) or x_0.dim() != 4 or not x_0.is_floating_point():
+            raise ValueError("KnownRegion: x_0 must be a floating-point tensor [B or 1, C, H, W]")
+        C, H, W = x_0.shape[1:]
+        if not torch.is_tensor(keep) or keep.dim() != 4 or tuple(keep.shape[2:]) != (H, W) or keep.shape[1] not in (1, C):
+            raise ValueError(f"KnownRegion: keep must be [B or 1, C or 1, {H}, {W}] for x_0 {tuple(x_0.shape)}, got "
+                             f"{tuple(keep.shape) if torch.is_tensor(keep) else type(keep).__name__}")
+        if torch.is_tensor(noise):
+            if noise.dim() != 4 or tuple(noise.shape[1:]) != (C, H, W):
+                raise ValueError(f"KnownRegion: a noise tensor must be [B or 1, {C}, {H}, {W}], got {tuple(noise.shape)}")
+            noise = noise.detach().to(device=x_0.device, dtype=torch.float32).contiguous()
+        elif noise not in ("fixed", "fresh"):
+            raise ValueError(f"KnownRegion: noise must be 'fixed', 'fresh' or a tensor, got {noise!r}")
+        object.__setattr__(self, "x_0", x_0.detach().float().contiguous())
+        object.__setattr__(self, "keep", (keep.detach().to(x_0.device) != 0).expand(keep.shape[0], C, H, W).to(torch.uint8).contiguous())
+        object.__setattr__(self, "noise", noise)
+
+    @property
+    def mode(self):
+        """"fresh", or "fixed" for everything that is one plane per sample (a tensor included): what a captured step depends on."""
+        return "fresh" if isinstance(self.noise, str) and self.noise == "fresh" else "fixed"
+
+    def check_batch(self, shape):
+        """The planes fit a chain / step of batch shape `shape`: the same image shape, batch 1 or `shape[0]` each."""
+        for name, p in (("x_0", self.x_0), ("keep", self.keep), ("noise", self.noise)):
+            if torch.is_tensor(p) and (tuple(p.shape[1:]) != tuple(shape[1:]) or p.shape[0] not in (1, shape[0])):
+                raise ValueError(f"KnownRegion: {name} {tuple(p.shape)} does not fit a batch of shape {tuple(shape)}")
+
+    def __setattr__(self, name, value):
+        raise AttributeError("KnownRegion is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("KnownRegion is immutable")
+
+    def __repr__(self):
+        noise = self.noise if isinstance(self.noise, str) else f"tensor{tuple(self.noise.shape)}"
+        return f"KnownRegion(x_0={tuple(self.x_0.shape)}, keep={tuple(self.keep.shape)}, noise={noise!r})"
+
+
+def _check_known(known):
+    if known is not None and not isinstance(known, KnownRegion):
+        raise TypeError(f"known must be None or a KnownRegion, got {type(known).__name__}")
+    return known
+
+
 def plan_chain_slots(lengths, slots):
     """Longest-first list schedule of reverse chains on `slots` chain slots (host logic of `_run_chains`).
 
@@ -276,9 +336,11 @@ def slot_events(place, steps, slots):
 class ReverseChain:
     """Device-resident state of the reverse loop (GaussianDiffusion.py:351-357): x, t and a step counter
     live in HBM; one step = model forward + noise + ONE fused update launch + t -= 1.  With a `sampler` (StridedSampler) the
-    update is the strided one, t -= stride (floored at 0), and `remaining` counts ceil(t_distance / stride) steps."""
+    update is the strided one, t -= stride (floored at 0), and `remaining` counts ceil(t_distance / stride) steps.  With `known`
+    (KnownRegion) the update is the conditioned one; the image, the keep bytes and the fixed noise live in static
+    buffers of the chain, so a kept graph follows the `known` of every reset()."""
 
-    def __init__(self, owner, model, x, t_distance, denoise_fn, use_graph=None, stream_base=None, sampler=None):
+    def __init__(self, owner, model, x, t_distance, denoise_fn, use_graph=None, stream_base=None, sampler=None, known=None):
         """Everything a chain allocates, once; `_start` (shared with reset()) then begins the chain itself."""
         _lib.require_cuda(x, "ReverseChain")
         self.owner, self.model, self.denoise_fn = owner, model, denoise_fn
@@ -308,8 +370,16 @@ class ReverseChain:
             self.noise = torch.empty_like(self.x)
             # room for the permutation tables of a full-length chain, so that reset() can start another chain on the same buffers
             self.tables = torch.empty((owner.num_timesteps * fn.in_channels, 512), dtype=torch.int16, device=x.device)
-        self.reuse_key = self._reuse_key_of(owner, denoise_fn, sampler)
+        self.reuse_key = self._reuse_key_of(owner, denoise_fn, sampler, known)
         self.capture_safe = capture_safe
+        # known-region conditioning: static planes, allocated here and copied into by _start, never inside a capture
+        self.known_mode = self._known_mode_of(owner, denoise_fn, known)
+        self.k_x0 = self.k_keep = self.k_noise = None
+        if self.known_mode is not None:
+            self.k_x0 = torch.empty_like(self.x)
+            self.k_keep = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
+            if self.known_mode == "fixed":
+                self.k_noise = torch.empty_like(self.x)
         # A seeded owner's gaussian step noise is generated inside the update kernel: no noise buffer, no ATen launch.
         # The kernel reads the seed and this chain's per-sample stream ids from device memory, so a kept graph follows
         # seed_gauss() and every reset() / slot refill without a recapture.
@@ -317,7 +387,7 @@ class ReverseChain:
         if self._seeded_gauss(owner, fn, capture_safe):
             self.streams = torch.empty((self.B,), dtype=torch.int32, device=x.device)
             owner._gauss_seed_dev(x.device)                         # allocated now, not inside a capture
-        self._start(x, t_distance, stream_base)
+        self._start(x, t_distance, stream_base, known)
         # HIP-graph replay of the step: on by default for the built-in UNetModel (every launch of a step is
         # stream-ordered, allocation-free C-ABI work) with a capture-safe noise source; ANODDPM_NO_GRAPH=1 forces
         # eager launches.  An explicit use_graph=True with an unsafe noise source is refused, not silently wrong.
@@ -365,11 +435,28 @@ class ReverseChain:
         return capture_safe and not isinstance(fn, SimplexNoiseFn) and getattr(owner, "gauss_seed", None) is not None
 
     @staticmethod
-    def _reuse_key_of(owner, denoise_fn, sampler=None):
+    def _known_mode_of(owner, denoise_fn, known):
+        """None, "fixed" or "fresh": which conditioned launch serves `known` for this noise request.  "fresh" is generated inside
+        the kernel from the seeded stream, so it is refused for anything else."""
+        if _check_known(known) is None:
+            return None
+        if known.mode == "fresh":
+            fn, capture_safe = ReverseChain._resolve_noise(owner, denoise_fn)
+            if isinstance(fn, SimplexNoiseFn):
+                raise ValueError("KnownRegion(noise='fresh'): the step noise is a simplex field; a second simplex field per step "
+                                 "for the known region is not provided -- use 'fixed' or a tensor")
+            if not ReverseChain._seeded_gauss(owner, fn, capture_safe):
+                raise ValueError("KnownRegion(noise='fresh'): the per-step draw is made inside the update kernel from the seeded "
+                                 "gaussian stream; this owner is not seeded (seed_gauss) or the noise request is not the gaussian one")
+        return known.mode
+
+    @staticmethod
+    def _reuse_key_of(owner, denoise_fn, sampler=None, known=None):
         """Key under which a graph-replaying chain for this noise request may be restarted with reset() (None: never).  A graph
         captured with torch.randn_like is never replayed for a seeded run, nor the reverse: the keys differ.  Likewise an
         ancestral graph and a strided one (tag "strided"); stride and eta are NOT in the key -- the strided launches read them
-        from device words, so one strided graph serves every stride."""
+        from device words, so one strided graph serves every stride.  A conditioned graph carries ("known", mode): it is never
+        replayed for an unconditioned request, nor the reverse, and "fixed" and "fresh" are different launches."""
         fn, capture_safe = ReverseChain._resolve_noise(owner, denoise_fn)
         if isinstance(fn, SimplexNoiseFn):
             key = ("simplex", id(fn.simplex), fn.octave, fn.persistence, fn.frequency, fn.in_channels)
@@ -377,7 +464,11 @@ class ReverseChain:
             key = ("gauss", "seeded")
         else:
             key = ("gauss",) if capture_safe else None
-        return key + ("strided",) if key is not None and sampler is not None else key
+        if key is not None and sampler is not None:
+            key += ("strided",)
+        if key is not None and known is not None:
+            key += (("known", ReverseChain._known_mode_of(owner, denoise_fn, known)),)
+        return key
 
     def _set_streams(self, stream_base):
         """Sample b of a seeded chain draws from stream `stream_base + b`; None: B fresh ids from the owner's allocator."""
@@ -405,27 +496,36 @@ class ReverseChain:
         self.table_setup_ms = 1000.0 * (time.perf_counter() - t0)
         self.table_setup_steps = nsteps
 
-    def reset(self, x, t_distance, stream_base=None, sampler=None):
+    def reset(self, x, t_distance, stream_base=None, sampler=None, known=None):
         """Start another chain of the same batch shape on this chain's device buffers: the captured HIP graph (and the plan behind
         it) is reused instead of being built again -- the detection loops run hundreds of chains of one shape.  A strided chain
-        may be handed another `sampler` (None: keep its own): the kept graph follows the re-written stride / eta words."""
+        may be handed another `sampler` (None: keep its own): the kept graph follows the re-written stride / eta words.  A
+        conditioned chain may be handed another `known` of its own mode (None: the planes stay as they are)."""
+        if known is not None:
+            if self.known_mode is None:
+                raise ValueError("ReverseChain.reset: an unconditioned chain cannot be restarted as a conditioned one")
+            if self._known_mode_of(self.owner, self.denoise_fn, known) != self.known_mode:
+                raise ValueError(f"ReverseChain.reset: this chain's known-region noise is {self.known_mode!r}, not {known.mode!r}")
         if sampler is not None:
             if self.sampler is None:
                 raise ValueError("ReverseChain.reset: an ancestral chain cannot be restarted as a strided one")
             self.sampler = _check_sampler(sampler)
         if tuple(x.shape) != tuple(self.x.shape) or x.device != self.x.device:
             raise ValueError("ReverseChain.reset: shape / device differ from the chain's buffers")
-        self._start(x, t_distance, stream_base)
+        self._start(x, t_distance, stream_base, known)
         if self.hip_model and self._graph_state == 2:
             # the replayed graph reads the packed weights of the plan it was captured with (NOT whatever _plan_for would pick
             # now -- ANODDPM_ARITH may have changed since): let THAT plan re-pack them if the parameters moved since
             self._plan.refresh_weights()
         return self
 
-    def _start(self, x, t_distance, stream_base):
+    def _start(self, x, t_distance, stream_base, known=None):
         """Begin a chain of `t_distance` timesteps from `x` on this chain's buffers.  The order is fixed: `_draw_tables` consumes
-        the global numpy stream and `_set_streams` the owner's stream allocator.  Never runs inside a capture: the sampler
-        words are allocated and written here."""
+        the global numpy stream and `_set_streams` the owner's stream allocator; a "fixed" known-region noise that the chain
+        draws itself comes after both.  Never runs inside a capture: the sampler words are allocated and written here, and the
+        known-region planes are copied here."""
+        if known is not None:
+            known.check_batch(self.x.shape)
         if not 0 <= int(t_distance) <= self.owner.num_timesteps:
             # extract() of the reference indexes the T-entry tables with t_distance - 1 and raises for anything else
             raise IndexError(f"t_distance {t_distance} is out of range for a {self.owner.num_timesteps}-step schedule")
@@ -439,6 +539,15 @@ class ReverseChain:
             self._draw_tables(self.remaining)
         if self.streams is not None:
             self._set_streams(stream_base)
+        if known is not None:
+            self.k_x0.copy_(known.x_0)                              # a batch of 1 is broadcast over the chain's
+            self.k_keep.copy_(known.keep)
+            if self.k_noise is not None:
+                if torch.is_tensor(known.noise):
+                    self.k_noise.copy_(known.noise)
+                elif int(t_distance) > 0:
+                    t_top = torch.full((self.B,), int(t_distance) - 1, device=self.x.device, dtype=torch.int64)
+                    self.k_noise.copy_(self.owner.noise_fn(self.k_x0, t_top).float())
 
     def step(self):
         if self.sampler is not None:
@@ -500,14 +609,19 @@ class ReverseChain:
                 noise = None                                        # generated inside the update kernel
             else:
                 noise = o._denoise_noise(self.x, self.t, self.denoise_fn)
-            if self.sampler is not None:
-                words = o._sampler_words(self.x.device, None)
+            words = o._sampler_words(self.x.device, None) if self.sampler is not None else None
+            if self.known_mode is not None:
+                o._known_update(self.x, self.t, eps, noise, (self.k_x0, self.k_keep, self.k_noise), words, want_pred=False,
+                                out=self.x, gauss_streams=self.streams)
+            elif self.sampler is not None:
                 o._strided_update(self.x, self.t, eps, noise, None, want_pred=False, out=self.x, gauss_streams=self.streams)
+            else:
+                o._reverse_update(self.x, self.t, eps, noise, want_pred=False, out=self.x, gauss_streams=self.streams)     # in place
+            if self.sampler is not None:
                 check(lib().anoddpm_chain_advance_strided(ptr(self.t), self.B, ptr(self.step_idx), ptr(words.stride),
                                                           current_stream()), "chain_advance_strided")
-                return
-            o._reverse_update(self.x, self.t, eps, noise, want_pred=False, out=self.x, gauss_streams=self.streams)     # in place
-            check(lib().anoddpm_chain_advance(ptr(self.t), self.B, ptr(self.step_idx), current_stream()), "chain_advance")
+            else:
+                check(lib().anoddpm_chain_advance(ptr(self.t), self.B, ptr(self.step_idx), current_stream()), "chain_advance")
 
     def finish(self):
         if self.tables is not None and self._last_seed is not None:
@@ -778,6 +892,73 @@ class GaussianDiffusionModel:
         sample, pred, _ = self._strided_update(x_t, t, eps, noise, sampler)
         return {"sample": sample, "pred_x_0": pred}
 
+    # ------------------------------------------------------------------ known-region conditioning
+    def _known_update(self, x_t, t, eps, noise, planes, words, want_pred=True, want_mean=False, out=None, gauss_streams=None,
+                      stream0=None):
+        """One fused launch of the conditioned step (anoddpm_p_sample_update_known), the counterpart of `_reverse_update`
+        (`words` None) and `_strided_update` (`words`: the device's sampler words, used as they are).  planes = (x_0, keep bytes,
+        known-region noise or None: generated in the launch), each fp32 / uint8, contiguous, batch 1 or B.  The seeded key block is
+        handed over with `gauss_streams` (device int32[B]) or `stream0` (sample b draws from stream0 + b).
+        -> (x_prev, pred_x_0, mean)."""
+        _lib.require_cuda(x_t, "GaussianDiffusionModel.sample_p_known")
+        tb = self._tables(x_t.device)
+        x_t, eps = self._f32(x_t.detach()), self._f32(eps.detach())
+        if noise is not None:
+            noise = self._f32(noise.detach())
+        t = self._t64(t, x_t.device)
+        a = PUpdateArgs()
+        x_prev = out if out is not None else torch.empty_like(x_t)
+        pred = torch.empty_like(x_t) if want_pred else None
+        mean = torch.empty_like(x_t) if want_mean else None
+        a.x_prev, a.pred_x0, a.mean_out = x_prev.data_ptr(), pred.data_ptr() if want_pred else None, mean.data_ptr() if want_mean else None
+        a.x_t, a.eps, a.noise, a.t = x_t.data_ptr(), eps.data_ptr(), noise.data_ptr() if noise is not None else None, t.data_ptr()
+        a.c_recip, a.c_recipm1 = tb.sqrt_recip_alphas_cumprod.data_ptr(), tb.sqrt_recipm1_alphas_cumprod.data_ptr()
+        if words is None:
+            a.c_coef1, a.c_coef2, a.c_sigma = tb.posterior_mean_coef1.data_ptr(), tb.posterior_mean_coef2.data_ptr(), tb.sigma.data_ptr()
+        a.B, a.T = x_t.shape[0], self.num_timesteps
+        a.n = x_t.numel() // max(x_t.shape[0], 1)
+        x_0, keep, kz = planes
+        for p in planes:
+            if p is not None and (p.device != x_t.device or not p.is_contiguous()):
+                raise _lib.AnoddpmError("sample_p_known: the known-region planes must be contiguous tensors on the device of x_t")
+        k = KnownArgs()
+        k.x0, k.keep, k.noise = x_0.data_ptr(), keep.data_ptr(), kz.data_ptr() if kz is not None else None
+        k.ca, k.cb = tb.sqrt_alphas_cumprod.data_ptr(), tb.sqrt_one_minus_alphas_cumprod.data_ptr()
+        k.x0_stride, k.keep_stride = (a.n if x_0.shape[0] == a.B else 0), (a.n if keep.shape[0] == a.B else 0)
+        k.noise_stride = a.n if kz is not None and kz.shape[0] == a.B else 0
+        seeded = gauss_streams is not None or stream0 is not None
+        check(lib().anoddpm_p_sample_update_known(
+            ctypes.byref(a), ctypes.byref(k), ptr(words.acp) if words else None, ptr(words.stride) if words else None,
+            ptr(words.eta) if words else None, ptr(self._gauss_seed_dev(x_t.device)) if seeded else None, ptr(gauss_streams),
+            int(stream0 or 0) & 0xFFFFFFFF, current_stream()), "p_sample_update_known")
+        return x_prev, pred, mean
+
+    def sample_p_known(self, model, x_t, t, known, denoise_fn="gauss", sampler=None):
+        """One conditioned reverse step from t to s = t - 1, or t - sampler.stride: model -> noise -> ONE fused launch.  The pixels
+        `known.keep` marks leave it as `known.x_0` noised to s with `known.noise` (a tensor, or "fresh" on a seeded instance), the
+        rest as `sample_p` / `sample_p_strided` would leave them; "pred_x_0" is the unconditioned one at every pixel.  On a seeded
+        instance the gaussian step noise is drawn as `sample_p` draws it -- B fresh stream ids -- inside the launch."""
+        if _check_known(known) is None:
+            raise TypeError("sample_p_known: a KnownRegion is required")
+        sampler = _check_sampler(sampler)
+        known.check_batch(x_t.shape)
+        mode = ReverseChain._known_mode_of(self, denoise_fn, known)
+        if mode == "fixed" and not torch.is_tensor(known.noise):
+            raise ValueError("sample_p_known: noise='fixed' is a chain's forward noise; a single step needs the tensor itself "
+                             "(or 'fresh' on a seeded instance)")
+        eps = model(x_t, t)
+        drawn = sampler is None or sampler.eta != 0.0             # sample_p_strided draws nothing at eta == 0
+        fn, capture_safe = ReverseChain._resolve_noise(self, denoise_fn)
+        stream0 = noise = None
+        if ReverseChain._seeded_gauss(self, fn, capture_safe) and (drawn or mode == "fresh"):
+            stream0 = self._take_streams(x_t.shape[0])
+        elif drawn:
+            noise = self._denoise_noise(x_t, t, denoise_fn)
+        words = self._sampler_words(x_t.device, sampler) if sampler is not None else None
+        planes = (known.x_0, known.keep, known.noise if mode == "fixed" else None)
+        sample, pred, _ = self._known_update(x_t, t, eps, noise, planes, words, stream0=stream0)
+        return {"sample": sample, "pred_x_0": pred}
+
     # ------------------------------------------------------------------ device plumbing
     def _tables(self, device):
         tb = self._dev.get(device)
@@ -922,9 +1103,13 @@ class GaussianDiffusionModel:
         sample, pred, _ = self._reverse_update(x_t, t, eps, noise)
         return {"sample": sample, "pred_x_0": pred}
 
-    def forward_backward(self, model, x, see_whole_sequence="half", t_distance=None, denoise_fn="gauss", sampler=None):
+    def forward_backward(self, model, x, see_whole_sequence="half", t_distance=None, denoise_fn="gauss", sampler=None, keep=None,
+                         known_noise="fixed"):
         """GaussianDiffusion.py:320-359.  `t` lives on the device for the whole chain.  `sampler` (else `self.sampler`): a
-        StridedSampler runs the reverse half in ceil(t_distance / stride) steps, and `seq` then holds one image per step."""
+        StridedSampler runs the reverse half in ceil(t_distance / stride) steps, and `seq` then holds one image per step.
+        `keep` ([B or 1, C or 1, H, W], nonzero = keep): the reverse half is conditioned on `x` itself (KnownRegion) --
+        with known_noise "fixed" on the forward noise drawn here for sample_q (the "whole" form, which noises gradually, draws one
+        more `noise_fn(x, t_distance - 1)` for it), with "fresh" on a new seeded draw per step."""
         sampler = _check_sampler(sampler) if sampler is not None else self.sampler
         assert see_whole_sequence == "whole" or see_whole_sequence == "half" or see_whole_sequence == None
 
@@ -935,6 +1120,7 @@ class GaussianDiffusionModel:
         _lib.require_cuda(x, "GaussianDiffusionModel.forward_backward")
         seq = [x.cpu().detach()]
         B = x.shape[0]
+        x_in, fwd_noise = x, None
         if see_whole_sequence == "whole":
             for t in range(int(t_distance)):
                 t_batch = torch.full((B,), t, device=x.device, dtype=torch.int64)
@@ -944,30 +1130,38 @@ class GaussianDiffusionModel:
                 seq.append(x.cpu().detach())
         else:
             t_tensor = torch.full((B,), t_distance - 1, device=x.device, dtype=torch.int64)
-            x = self.sample_q(x, t_tensor, self.noise_fn(x, t_tensor).float())
+            fwd_noise = self.noise_fn(x, t_tensor).float()
+            x = self.sample_q(x, t_tensor, fwd_noise)
             if see_whole_sequence == "half":
                 seq.append(x.cpu().detach())
 
+        known = None
+        if keep is not None:
+            if known_noise == "fixed":
+                if fwd_noise is None:
+                    fwd_noise = self.noise_fn(x_in, torch.full((B,), t_distance - 1, device=x.device, dtype=torch.int64)).float()
+                known_noise = fwd_noise
+            known = KnownRegion(x_in, keep, known_noise)
         with torch.no_grad():
-            x = self._reverse_chain(model, x, int(t_distance), denoise_fn, seq if see_whole_sequence else None, sampler)
+            x = self._reverse_chain(model, x, int(t_distance), denoise_fn, seq if see_whole_sequence else None, sampler, known)
         return x.detach() if not see_whole_sequence else seq
 
     p_sample_loop = forward_backward          # north-star alias
 
-    def _chain_for(self, model, x, t_distance, denoise_fn, stream_base=None, sampler=None):
+    def _chain_for(self, model, x, t_distance, denoise_fn, stream_base=None, sampler=None, known=None):
         """A ReverseChain for (model, batch shape, noise source): chains that replay a captured graph are kept -- at most eight,
         oldest dropped first; they hold their model -- and restarted with reset() (same device buffers, same graph); anything
         else is built fresh."""
         cache = self.__dict__.setdefault("_chains", {})
-        want = ReverseChain._reuse_key_of(self, denoise_fn, sampler)
+        want = ReverseChain._reuse_key_of(self, denoise_fn, sampler, known)
         if want is not None:
             key = (id(model), tuple(x.shape), str(x.device), want)
             chain = cache.get(key)
             # a kept chain replays the dropout-free inference graph: not for a model that has since been put in train() mode
             # with dropout > 0 (it gets a fresh eager chain below, which is not kept)
             if chain is not None and chain.model is model and not ReverseChain._draws_dropout(model):
-                return chain.reset(x, t_distance, stream_base, sampler)
-        chain = ReverseChain(self, model, x, t_distance, denoise_fn, stream_base=stream_base, sampler=sampler)
+                return chain.reset(x, t_distance, stream_base, sampler, known)
+        chain = ReverseChain(self, model, x, t_distance, denoise_fn, stream_base=stream_base, sampler=sampler, known=known)
         if chain.use_graph and chain.reuse_key is not None:
             if len(cache) >= 8:
                 if x.is_cuda:
@@ -976,10 +1170,10 @@ class GaussianDiffusionModel:
             cache[(id(model), tuple(x.shape), str(x.device), chain.reuse_key)] = chain
         return chain
 
-    def _reverse_chain(self, model, x, t_distance, denoise_fn, seq, sampler=None):
+    def _reverse_chain(self, model, x, t_distance, denoise_fn, seq, sampler=None, known=None):
         """t = t_distance-1 ... 0 of sample_p with a device-resident timestep (no per-step H2D); with a `sampler` the
         ceil(t_distance / stride) strided steps."""
-        chain = self._chain_for(model, x, t_distance, denoise_fn, sampler=sampler)
+        chain = self._chain_for(model, x, t_distance, denoise_fn, sampler=sampler, known=known)
         for _ in range(chain.remaining):
             chain.step()
             if seq is not None:
@@ -1014,12 +1208,12 @@ class GaussianDiffusionModel:
             new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
-    def reverse_chain(self, model, x_t, t_distance, denoise_fn="gauss", sampler=None):
+    def reverse_chain(self, model, x_t, t_distance, denoise_fn="gauss", sampler=None, known=None):
         """Stepping form of the reverse loop of forward_backward (:351-357): returns a ReverseChain whose
         .step() performs one sample_p on the device-resident state (bench.py times K of these).  `sampler` (else `self.sampler`):
-        a StridedSampler makes each step a strided one."""
+        a StridedSampler makes each step a strided one.  `known`: a KnownRegion makes each step a conditioned one."""
         sampler = _check_sampler(sampler) if sampler is not None else self.sampler
-        return ReverseChain(self, model, x_t, int(t_distance), denoise_fn, sampler=sampler)
+        return ReverseChain(self, model, x_t, int(t_distance), denoise_fn, sampler=sampler, known=known)
 
     def sample_q(self, x_0, t, noise):
         """q(x_t | x_0), GaussianDiffusion.py:361-371 -- one fused launch."""

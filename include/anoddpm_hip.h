@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 37
+#define ANODDPM_ABI_VERSION 38
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -141,7 +141,8 @@ int anoddpm_chain_advance(int64_t *t, int32_t B, int32_t *step, void *stream);
  *   counter    (c0, c1, c2, c3) = (quad, stream, step, domain); quad = i >> 2, i the element index inside ONE sample
  *   normals    u(w) = ((w >> 9) + 0.5) * 2^-23;  r = sqrtf(-2 logf(u(w0)));  elements 4 quad + 0 / 1 = r cos / sin(2 pi u(w1)),
  *              elements 4 quad + 2 / 3 the same from (w2, w3).  A partial last quad uses its leading lanes.
- *   domain     0 reverse-step noise, 1 forward / training noise, 2 plain fill.
+ *   domain     0 reverse-step noise, 1 forward / training noise, 2 plain fill, 3 known-region noise (the step is the timestep
+ *              the step LANDS on; see anoddpm_p_sample_update_known at the end of this file).
  * Key block, the same four arguments in every entry point below:
  *   seed     [dev] one 64-bit seed
  *   streams  [dev] int32[B] read as uint32: the stream of sample b; NULL: stream0 + b
@@ -1442,6 +1443,36 @@ typedef struct anoddpm_ano_slices_args {
 } anoddpm_ano_slices_args;
 
 int anoddpm_ano_slices(const anoddpm_ano_slices_args *a, void *stream);
+
+/* ------------------------------------------------------------------ known-region conditioning */
+
+/* Known-region conditioning of one reverse step: the pixels marked "keep" are tied to an input image at every step,
+ * the rest comes from the ordinary reverse update -- RePaint (Lugmayr et al., CVPR 2022, Algorithm 1 / eq. 8) and the "stitch" of
+ * AutoDDPM (Bercea et al., 2023), on the update of GaussianDiffusion.py:298-318 and the q-sample of :361-371.  ONE launch, per
+ * sample b with ti the normalised t[b] and s = ti - 1 (ancestral) or ti - *stride (strided):
+ *   u      = what anoddpm_p_sample_update / _gauss / anoddpm_strided_update with the same `a`, strided block and key block writes
+ *            to x_prev, its step noise included (a->noise, or domain 0 at step ti)
+ *   kz     = k->noise, or -- when that is NULL -- generated in the kernel from the key block with domain 3 at step s
+ *   kn     = s < 0 ? x0 : ca[s] * x0 + cb[s] * kz           (separate mul, mul, add: no FMA, as anoddpm_q_sample)
+ *   x_prev = keep ? kn : u                                  a select, not a blend: a NaN on one side never reaches the other
+ * pred_x0 and mean_out are those of the unconditioned update at every pixel.  With s < 0 the known noise is neither read nor
+ * generated.  An out-of-range t[b] or a stride < 1 makes every element of x_prev of that sample NaN, kept pixels included; nothing
+ * is read out of bounds.  x_prev may alias x_t.  Bit-identical to the unconditioned launch, anoddpm_philox_fill (kind 1, domain 3,
+ * step s), anoddpm_q_sample at s and a select -- four launches that move 41 B/pixel -- in one launch that moves 17 B/pixel (x_t, eps,
+ * x0, one keep byte, x_prev), plus 4 for each noise that is read from a plane instead of being generated.
+ * alphas_cumprod / stride / eta: all NULL for the ancestral update, all set for the strided one.  seed == NULL: the step noise is
+ * a->noise (or none) and k->noise is required; otherwise a->noise must be NULL. */
+typedef struct anoddpm_known_args {
+    const float *x0;           /* [dev] fp32; sample b at x0 + b * x0_stride */
+    const uint8_t *keep;       /* [dev] bytes; nonzero = keep this pixel; sample b at keep + b * keep_stride */
+    const float *noise;        /* [dev] fp32 known-region noise, sample b at noise + b * noise_stride; or NULL */
+    const float *ca, *cb;      /* sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, fp32[a->T] */
+    int64_t x0_stride, keep_stride, noise_stride;      /* each 0 (one plane for all samples) or a->n */
+} anoddpm_known_args;
+
+int anoddpm_p_sample_update_known(const anoddpm_p_update_args *a, const anoddpm_known_args *k, const double *alphas_cumprod,
+                                  const int32_t *stride, const float *eta, const uint64_t *seed, const int32_t *streams,
+                                  uint32_t stream0, void *stream);
 
 #ifdef __cplusplus
 }
