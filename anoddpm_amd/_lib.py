@@ -122,7 +122,7 @@ _STRUCTS = [globals()[_py] for _py in _PYNAME.values()]
 SYMBOLS = list(_PROTOS)
 
 # limits and selectors the header states in prose only
-PHILOX_REVERSE, PHILOX_FORWARD, PHILOX_FILL, PHILOX_KNOWN = 0, 1, 2, 3                                # the `domain` word of the philox counter
+PHILOX_REVERSE, PHILOX_FORWARD, PHILOX_FILL, PHILOX_KNOWN, PHILOX_RENOISE = 0, 1, 2, 3, 4                          # the `domain` word of the philox counter
 SSIM_MAX_WIN = 15
 MEDIAN_SIZES = (3, 5, 7)                                                                # anoddpm_median_args.k
 ERODE_MAX = 8                                                                           # anoddpm_erode_args.n

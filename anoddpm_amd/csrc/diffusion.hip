@@ -416,6 +416,146 @@ __global__ __launch_bounds__(256) void p_update_known_kernel(anoddpm_p_update_ar
     }
 }
 
+// ---------------------------------------------------------------- resampling jumps
+// The jump schedule of RePaint's sampler (Lugmayr et al., CVPR 2022, Algorithm 1) decided per sample on the device: an update that
+// lands on level s jumps back up to s + J when s is a jump point of the chain (s >= 0, s % J == 0, s + J <= top) and the chain
+// still has repetitions left.  The update kernel and the advance kernel evaluate THIS predicate from the same words.
+__device__ __forceinline__ bool resample_jumps(long long s, long long J, long long R, long long top, long long rep)
+{
+    return J >= 1 && R >= 1 && s >= 0 && s % J == 0 && s + J <= top && rep > 0;
+}
+
+// A sibling of p_update_known_kernel (ancestral only): the conditioned image x_s of the step, and where the step jumps the
+// re-noising q(x_land | x_s) = A x_s + C rz of EVERY pixel in the same pass.  Philox domains carry the visit index v of the sample:
+// 8 v (step noise, step ti), 3 + 8 v (known-region noise, step s), 4 + 8 v (re-noise, step land).
+template <int VEC, bool GAUSS>
+__global__ __launch_bounds__(256) void p_update_resample_kernel(anoddpm_p_update_args a, anoddpm_known_args kr, anoddpm_resampling_args r,
+                                                                PhiloxKey key)
+{
+    const int b = blockIdx.y;
+    long long ti;
+    bool bad;
+    const StepCoef k = step_coef<false>(a, StridedArgs{}, b, ti, bad);
+    const long long J = *r.jump, R = *r.reps;
+    KnownSample ks;
+    ks.poison = bad || J < 1 || R < 1;
+    const long long s = ks.poison ? -1 : ti - 1;               // < a.T: never outside the tables
+    bool jump = !ks.poison && resample_jumps(s, J, R, r.top[b], r.rep[b]);
+    if (jump && s + J >= a.T) {                                 // a `top` beyond the schedule: poisoned, no table read
+        ks.poison = true;
+        jump = false;
+    }
+    const long long land = jump ? s + J : s;
+    const uint32_t v8 = 8u * (uint32_t)r.visit[b];
+    const bool noised = !ks.poison && s >= 0;
+    ks.exact = !ks.poison && !noised;
+    ks.qa = noised ? kr.ca[s] : 0.0f;
+    ks.qc = noised ? kr.cb[s] : 0.0f;
+    ks.x0 = kr.x0 + (int64_t)b * kr.x0_stride;
+    ks.keep = kr.keep + (int64_t)b * kr.keep_stride;
+    ks.noise = noised && kr.noise ? kr.noise + (int64_t)b * kr.noise_stride : nullptr;
+    float A = 1.0f, C = 0.0f;
+    if (jump) {                                                  // uniform over the workgroup: `jump` depends on b alone
+        __shared__ float renoise[2];
+        if (threadIdx.x == 0) {                                  // fp64, each rounded to fp32 once (as strided_coef)
+            const double ratio = r.alphas_cumprod[land] / r.alphas_cumprod[s];
+            renoise[0] = (float)sqrt(ratio);
+            renoise[1] = (float)sqrt(1.0 - ratio);
+        }
+        __syncthreads();
+        A = renoise[0], C = renoise[1];
+    }
+    const float *rnoise = jump && r.noise ? r.noise + (int64_t)b * r.noise_stride : nullptr;
+    const bool kgen = GAUSS && noised && !kr.noise, rgen = GAUSS && jump && !r.noise;
+    PhiloxSample ps = {}, pk = {}, pr = {};
+    if (GAUSS) {
+        ps = philox_sample(key, b, (uint32_t)ti);
+        ps.domain = v8;                                          // step noise
+        pk = ps;
+        pk.step = (uint32_t)(noised ? s : 0);
+        pk.domain = 3u + v8;                                     // known-region noise
+        pr = ps;
+        pr.step = (uint32_t)(jump ? land : 0);
+        pr.domain = 4u + v8;                                     // re-noise
+    }
+    const float *step_noise = !GAUSS && a.noise ? a.noise + (int64_t)b * a.n : nullptr;
+    const int64_t base = (int64_t)b * a.n;
+    const int64_t nq = (a.n + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f}, w[4] = {0.f, 0.f, 0.f, 0.f}, y[4] = {0.f, 0.f, 0.f, 0.f};
+        if (GAUSS) philox_normals(ps, (uint32_t)q, z);
+        if (kgen) philox_normals(pk, (uint32_t)q, w);
+        if (rgen) philox_normals(pr, (uint32_t)q, y);
+        const int64_t j = 4 * q, i = base + j;
+        if (VEC == 4) {
+            if (step_noise) {
+                const float4 nv = *reinterpret_cast<const float4 *>(step_noise + j);
+                z[0] = nv.x, z[1] = nv.y, z[2] = nv.z, z[3] = nv.w;
+            }
+            if (ks.noise) {
+                const float4 nv = *reinterpret_cast<const float4 *>(ks.noise + j);
+                w[0] = nv.x, w[1] = nv.y, w[2] = nv.z, w[3] = nv.w;
+            }
+            if (rnoise) {
+                const float4 nv = *reinterpret_cast<const float4 *>(rnoise + j);
+                y[0] = nv.x, y[1] = nv.y, y[2] = nv.z, y[3] = nv.w;
+            }
+            const float4 xv = *reinterpret_cast<const float4 *>(a.x_t + i);
+            const float4 ev = *reinterpret_cast<const float4 *>(a.eps + i);
+            const float4 cv = *reinterpret_cast<const float4 *>(ks.x0 + j);
+            const uint32_t kb = *reinterpret_cast<const uint32_t *>(ks.keep + j);
+            float4 o, p0, mu;
+            o.x = known_one(reverse_one<false>(xv.x, ev.x, z[0], k, &p0.x, &mu.x), cv.x, w[0], (kb & 0x000000ffu) != 0, ks);
+            o.y = known_one(reverse_one<false>(xv.y, ev.y, z[1], k, &p0.y, &mu.y), cv.y, w[1], (kb & 0x0000ff00u) != 0, ks);
+            o.z = known_one(reverse_one<false>(xv.z, ev.z, z[2], k, &p0.z, &mu.z), cv.z, w[2], (kb & 0x00ff0000u) != 0, ks);
+            o.w = known_one(reverse_one<false>(xv.w, ev.w, z[3], k, &p0.w, &mu.w), cv.w, w[3], (kb & 0xff000000u) != 0, ks);
+            if (jump) {
+                o.x = A * o.x + C * y[0];
+                o.y = A * o.y + C * y[1];
+                o.z = A * o.z + C * y[2];
+                o.w = A * o.w + C * y[3];
+            }
+            *reinterpret_cast<float4 *>(a.x_prev + i) = o;
+            if (a.pred_x0) *reinterpret_cast<float4 *>(a.pred_x0 + i) = p0;
+            if (a.mean_out) *reinterpret_cast<float4 *>(a.mean_out + i) = mu;
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                if (j + l < a.n) {
+                    float p0, mu;
+                    const float nz = step_noise ? step_noise[j + l] : z[l];
+                    const float u = reverse_one<false>(a.x_t[i + l], a.eps[i + l], nz, k, &p0, &mu);
+                    const float xs = known_one(u, ks.x0[j + l], ks.noise ? ks.noise[j + l] : w[l], ks.keep[j + l] != 0, ks);
+                    a.x_prev[i + l] = jump ? A * xs + C * (rnoise ? rnoise[j + l] : y[l]) : xs;
+                    if (a.pred_x0) a.pred_x0[i + l] = p0;
+                    if (a.mean_out) a.mean_out[i + l] = mu;
+                }
+            }
+        }
+    }
+}
+
+// The only writer of a resampled chain's state: one thread per sample.  A landing that jumps goes back up to s + J with
+// one repetition less and the next visit index; a landing on a multiple of J that does not jump refills the repetitions; everything
+// else counts down, floored at 0 as chain_advance_strided floors it.
+__global__ void chain_advance_resample_kernel(int64_t *t, int B, int32_t *step, const int32_t *jump, const int32_t *reps,
+                                              const int32_t *top, int32_t *rep, int32_t *visit)
+{
+    const int i = threadIdx.x;
+    if (i < B) {
+        const long long J = *jump, R = *reps, s = (long long)t[i] - 1;
+        if (resample_jumps(s, J, R, top[i], rep[i])) {
+            t[i] = s + J;
+            rep[i] -= 1;
+            visit[i] += 1;
+        } else {
+            if (J >= 1 && R >= 1 && s >= 0 && s % J == 0) rep[i] = (int32_t)(R - 1);
+            t[i] = s < 0 ? 0 : s;
+        }
+    }
+    if (i == 0 && step) *step += 1;
+}
+
 __global__ void chain_advance_kernel(int64_t *t, int B, int32_t *step)
 {
     const int i = threadIdx.x;
@@ -886,6 +1026,47 @@ extern "C" int anoddpm_p_sample_update_known(const anoddpm_p_update_args *a, con
         strided ? p_update_known_dispatch<false, true>(v4, gx, *a, *k, key, sa, stream)
                 : p_update_known_dispatch<false, false>(v4, gx, *a, *k, key, sa, stream);
     return anoddpm::check_launch(who);
+}
+
+extern "C" int anoddpm_p_sample_update_resample(const anoddpm_p_update_args *a, const anoddpm_known_args *k,
+                                                const anoddpm_resampling_args *r, const uint64_t *seed, const int32_t *streams,
+                                                uint32_t stream0, void *stream)
+{
+    const char *who = "p_sample_update_resample";
+    ANODDPM_REQUIRE(k, "%s: null known-region struct", who);
+    ANODDPM_REQUIRE(r, "%s: null resampling struct", who);
+    ANODDPM_REQUIRE(seed || k->noise, "%s: no known-region noise tensor and no seed to generate it from", who);
+    ANODDPM_REQUIRE(seed || r->noise, "%s: no re-noise tensor and no seed to generate it from", who);
+    const PhiloxKey key = {seed, streams, stream0, 0u};       // the kernel forms the three domains from the visit index
+    const int rc = p_update_check(a, seed ? &key : nullptr, nullptr, who);
+    if (rc < 0) return rc;
+    ANODDPM_REQUIRE(k->x0 && k->keep && k->ca && k->cb, "%s: null x0 / keep / ca / cb", who);
+    ANODDPM_REQUIRE(r->jump && r->reps && r->top && r->rep && r->visit && r->alphas_cumprod,
+                    "%s: null jump / reps / top / rep / visit / alphas_cumprod", who);
+    for (const int64_t w : {k->x0_stride, k->keep_stride, k->noise_stride, r->noise_stride})
+        ANODDPM_REQUIRE(w == 0 || w == a->n, "%s: a sample stride of %lld is neither 0 nor n", who, (long long)w);
+    if (rc) return ANODDPM_OK;
+    const bool v4 = p_update_v4(a) && aligned16(k->x0) && (!k->noise || aligned16(k->noise)) && ((uintptr_t)k->keep & 3) == 0 &&
+                    (!r->noise || aligned16(r->noise));
+    const dim3 grid(grid_x((a->n + 3) / 4), a->B);
+    if (seed && v4)
+        hipLaunchKernelGGL((p_update_resample_kernel<4, true>), grid, dim3(256), 0, anoddpm::as_stream(stream), *a, *k, *r, key);
+    else if (seed)
+        hipLaunchKernelGGL((p_update_resample_kernel<1, true>), grid, dim3(256), 0, anoddpm::as_stream(stream), *a, *k, *r, key);
+    else if (v4)
+        hipLaunchKernelGGL((p_update_resample_kernel<4, false>), grid, dim3(256), 0, anoddpm::as_stream(stream), *a, *k, *r, key);
+    else
+        hipLaunchKernelGGL((p_update_resample_kernel<1, false>), grid, dim3(256), 0, anoddpm::as_stream(stream), *a, *k, *r, key);
+    return anoddpm::check_launch(who);
+}
+
+extern "C" int anoddpm_chain_advance_resample(int64_t *t, int32_t B, int32_t *step, const int32_t *jump, const int32_t *reps,
+                                              const int32_t *top, int32_t *rep, int32_t *visit, void *stream)
+{
+    ANODDPM_REQUIRE(t && jump && reps && top && rep && visit && B >= 0 && B <= 1024, "chain_advance_resample: bad arguments");
+    hipLaunchKernelGGL(chain_advance_resample_kernel, dim3(1), dim3(B < 64 ? 64 : ((B + 63) / 64) * 64), 0,
+                       anoddpm::as_stream(stream), t, (int)B, step, jump, reps, top, rep, visit);
+    return anoddpm::check_launch("chain_advance_resample");
 }
 
 extern "C" int anoddpm_chain_advance(int64_t *t, int32_t B, int32_t *step, void *stream)

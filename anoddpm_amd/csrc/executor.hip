@@ -211,7 +211,8 @@ extern "C" int anoddpm_prof_list(int32_t *codes, float *ms, int32_t cap)
     X(anoddpm_loss_args) X(anoddpm_dropout_args) X(anoddpm_roc_args) X(anoddpm_ssim_args) X(anoddpm_component_areas_args) \
     X(anoddpm_pro_args) X(anoddpm_distance_args) X(anoddpm_surface_args) X(anoddpm_median_args) X(anoddpm_erode_args) \
     X(anoddpm_components_args) X(anoddpm_gauss_args) X(anoddpm_map_scores_args) \
-    X(anoddpm_ano_slices_args) X(anoddpm_select_args) X(anoddpm_threshold_counts_args) X(anoddpm_known_args)
+    X(anoddpm_ano_slices_args) X(anoddpm_select_args) X(anoddpm_threshold_counts_args) X(anoddpm_known_args) \
+    X(anoddpm_resampling_args)
 
 extern "C" int anoddpm_struct_size(const char *name)
 {

@@ -28,10 +28,10 @@ import numpy as np
 import torch
 
 from . import _lib, philox
-from ._lib import KnownArgs, LossArgs, PUpdateArgs, VlbArgs, check, current_stream, lib, ptr
+from ._lib import KnownArgs, LossArgs, PUpdateArgs, ResamplingArgs, VlbArgs, check, current_stream, lib, ptr
 from .simplex import Simplex_CLASS, perm_tables
 
-__all__ = ["SimplexNoiseFn", "GaussNoiseFn", "ReverseChain", "StridedSampler", "KnownRegion", "get_beta_schedule", "extract", "mean_flat", "normal_kl", "approx_standard_normal_cdf",
+__all__ = ["SimplexNoiseFn", "GaussNoiseFn", "ReverseChain", "StridedSampler", "KnownRegion", "Resampling", "get_beta_schedule", "extract", "mean_flat", "normal_kl", "approx_standard_normal_cdf",
            "discretised_gaussian_log_likelihood", "generate_simplex_noise", "random_noise",
            "GaussianDiffusionModel"]
 
@@ -233,8 +233,8 @@ class KnownRegion:
              it noised `x` with; a chain built directly draws `noise_fn(x_0, t_distance - 1)` once);
              "fresh": a new draw per step, made inside the kernel from the seeded stream (domain 3): seeded owners only;
              a tensor [B or 1, C, H, W]: that plane, as "fixed".
-    A hard select, no resampling jumps, single chains only (not the slot-batched detection sweeps).  What it does to detection
-    quality has not been measured."""
+    A hard select.  Resampling jumps are a `Resampling` handed over next to it; the slot-batched detection sweeps take one through
+    `_run_chains(known=)` / the `detection_keep` attribute.  What it does to detection quality has not been measured."""
     __slots__ = ("x_0", "keep", "noise")
 
     def __init__(self, x_0, keep, noise="fixed"):
@@ -280,6 +280,84 @@ def _check_known(known):
     if known is not None and not isinstance(known, KnownRegion):
         raise TypeError(f"known must be None or a KnownRegion, got {type(known).__name__}")
     return known
+
+
+class Resampling:
+    """Opt-in resampling jumps of a conditioned reverse chain (RePaint, Lugmayr et al., CVPR 2022, Algorithm 1; DESIGN 9r);
+    immutable.  `jump` >= 1: the length of a jump; `reps` >= 1: how often each segment is sampled (1: no resampling).  A chain that
+    starts at level top = t_distance - 1 has a jump point at every level p >= 0 with p % jump == 0 and p + jump <= top.  The update
+    that lands on a jump point with repetitions left re-noises its image back up to p + jump -- q(x_{p+jump} | x_p), every pixel --
+    and the chain comes down the same `jump` levels again, `reps` times in all, each pass with its own noise (the pass count,
+    `visit`, is part of the Philox domain).  The device decides and carries out the jump per sample, inside the fused update
+    launch (anoddpm_p_sample_update_resample) and its advance launch.  Only with a KnownRegion, only the ancestral sampler, only
+    gaussian step noise.  What it does to detection quality has not been measured."""
+    __slots__ = ("jump", "reps")
+
+    def __init__(self, jump, reps):
+        for name, v in (("jump", jump), ("reps", reps)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 or v > 2 ** 31 - 1:
+                raise ValueError(f"Resampling: {name} must be an integer >= 1, got {v!r}")
+        object.__setattr__(self, "jump", int(jump))
+        object.__setattr__(self, "reps", int(reps))
+
+    @classmethod
+    def parse(cls, text):
+        """"<jump>,<reps>", the form of the ANODDPM_RESAMPLE environment variable."""
+        parts = [p.strip() for p in str(text).split(",")]
+        try:
+            if len(parts) != 2:
+                raise ValueError
+            return cls(int(parts[0], 10), int(parts[1], 10))
+        except ValueError:
+            raise ValueError(f"ANODDPM_RESAMPLE={text!r}: expected '<jump>,<reps>' with two integers >= 1") from None
+
+    def steps(self, t_distance):
+        """UNet evaluations of a chain of `t_distance` timesteps: every jump point adds (reps - 1) passes over `jump` levels."""
+        L = int(t_distance)
+        return L + ((L - 1) // self.jump) * (self.reps - 1) * self.jump if L >= 1 else 0
+
+    def timesteps(self, t_distance):
+        """[(ti, land, visit)] of every evaluation, in order: the level the UNet sees, the level the update leaves the image at
+        (-1: the clean image) and the visit index the step's noise is drawn with.  Written segment by segment, from the highest
+        jump point down; the device runs the same schedule as a per-sample state machine (anoddpm_chain_advance_resample)."""
+        top, J = int(t_distance) - 1, self.jump
+        out, cur, visit = [], top, 0
+        for p in range(((top - J) // J) * J if top >= J else -1, -1, -J):
+            for r in range(self.reps):
+                jumps = r < self.reps - 1
+                for ti in range(cur, p, -1):
+                    out.append((ti, p + J if jumps and ti - 1 == p else ti - 1, visit))
+                visit += jumps
+                cur = p + J if jumps else p
+        out.extend((ti, ti - 1, visit) for ti in range(cur, -1, -1))
+        return out
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Resampling is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("Resampling is immutable")
+
+    def _key(self):
+        return (self.jump, self.reps)
+
+    def __eq__(self, other):
+        return isinstance(other, Resampling) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"Resampling(jump={self.jump!r}, reps={self.reps!r})"
+
+    def __reduce__(self):
+        return Resampling, self._key()
+
+
+def _check_resampling(resampling):
+    if resampling is not None and not isinstance(resampling, Resampling):
+        raise TypeError(f"resampling must be None or a Resampling, got {type(resampling).__name__}")
+    return resampling
 
 
 def plan_chain_slots(lengths, slots):
@@ -338,9 +416,13 @@ class ReverseChain:
     live in HBM; one step = model forward + noise + ONE fused update launch + t -= 1.  With a `sampler` (StridedSampler) the
     update is the strided one, t -= stride (floored at 0), and `remaining` counts ceil(t_distance / stride) steps.  With `known`
     (KnownRegion) the update is the conditioned one; the image, the keep bytes and the fixed noise live in static
-    buffers of the chain, so a kept graph follows the `known` of every reset()."""
+    buffers of the chain, so a kept graph follows the `known` of every reset().  With `resampling` (Resampling) the
+    conditioned update also carries out the schedule's jumps: `t` is then not monotone, the per-sample state (top, rep, visit) and
+    the two schedule words live in static buffers, and `remaining` counts UNet evaluations.  `shared_planes`: the image and the
+    keep bytes are ONE plane for the whole batch (the slot-batched sweep of one image)."""
 
-    def __init__(self, owner, model, x, t_distance, denoise_fn, use_graph=None, stream_base=None, sampler=None, known=None):
+    def __init__(self, owner, model, x, t_distance, denoise_fn, use_graph=None, stream_base=None, sampler=None, known=None,
+                 resampling=None, shared_planes=False):
         """Everything a chain allocates, once; `_start` (shared with reset()) then begins the chain itself."""
         _lib.require_cuda(x, "ReverseChain")
         self.owner, self.model, self.denoise_fn = owner, model, denoise_fn
@@ -370,16 +452,26 @@ class ReverseChain:
             self.noise = torch.empty_like(self.x)
             # room for the permutation tables of a full-length chain, so that reset() can start another chain on the same buffers
             self.tables = torch.empty((owner.num_timesteps * fn.in_channels, 512), dtype=torch.int16, device=x.device)
-        self.reuse_key = self._reuse_key_of(owner, denoise_fn, sampler, known)
+        self.resampling = self._check_resample_request(owner, denoise_fn, sampler, known, resampling)
+        self.reuse_key = self._reuse_key_of(owner, denoise_fn, sampler, known, resampling, shared_planes)
         self.capture_safe = capture_safe
         # known-region conditioning: static planes, allocated here and copied into by _start, never inside a capture
         self.known_mode = self._known_mode_of(owner, denoise_fn, known)
         self.k_x0 = self.k_keep = self.k_noise = None
+        self.shared_planes = bool(shared_planes) and self.known_mode is not None
         if self.known_mode is not None:
-            self.k_x0 = torch.empty_like(self.x)
-            self.k_keep = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
+            plane = (1,) + tuple(x.shape[1:]) if self.shared_planes else tuple(x.shape)
+            self.k_x0 = torch.empty(plane, device=x.device, dtype=torch.float32)
+            self.k_keep = torch.empty(plane, device=x.device, dtype=torch.uint8)
             if self.known_mode == "fixed":
                 self.k_noise = torch.empty_like(self.x)
+        # resampling: the per-sample state and the two schedule words, written by _start (and by the sweep's refills), read by the
+        # update launch, advanced by anoddpm_chain_advance_resample alone
+        self.rs_top = self.rs_rep = self.rs_visit = self.rs_jump = self.rs_reps = None
+        if self.resampling is not None:
+            self.rs_top, self.rs_rep, self.rs_visit = (torch.empty((self.B,), dtype=torch.int32, device=x.device) for _ in range(3))
+            self.rs_jump, self.rs_reps = (torch.empty(1, dtype=torch.int32, device=x.device) for _ in range(2))
+            owner._sampler_words(x.device, None)                    # the fp64 alphas_cumprod table: allocated now
         # A seeded owner's gaussian step noise is generated inside the update kernel: no noise buffer, no ATen launch.
         # The kernel reads the seed and this chain's per-sample stream ids from device memory, so a kept graph follows
         # seed_gauss() and every reset() / slot refill without a recapture.
@@ -451,12 +543,31 @@ class ReverseChain:
         return known.mode
 
     @staticmethod
-    def _reuse_key_of(owner, denoise_fn, sampler=None, known=None):
+    def _check_resample_request(owner, denoise_fn, sampler, known, resampling):
+        """`resampling` as a chain may run it: with a KnownRegion, the ancestral sampler and gaussian step noise only."""
+        if _check_resampling(resampling) is None:
+            return None
+        if known is None:
+            raise ValueError("resampling: the jumps harmonise a generated region with a kept one; without `known` (a KnownRegion) "
+                             "there is nothing to harmonise")
+        if sampler is not None:
+            raise ValueError("resampling: a strided sampler is refused -- the jump schedule is stated in single ancestral steps "
+                             "(a level lands on level - 1); resampling under a stride is not provided")
+        fn, _ = ReverseChain._resolve_noise(owner, denoise_fn)
+        if isinstance(fn, SimplexNoiseFn):
+            raise ValueError("resampling: the step noise is a simplex field; the re-noise of a jump takes the chain's step-noise "
+                             "kind and a simplex re-noise is not provided -- use the gaussian step noise")
+        return resampling
+
+    @staticmethod
+    def _reuse_key_of(owner, denoise_fn, sampler=None, known=None, resampling=None, shared_planes=False):
         """Key under which a graph-replaying chain for this noise request may be restarted with reset() (None: never).  A graph
         captured with torch.randn_like is never replayed for a seeded run, nor the reverse: the keys differ.  Likewise an
         ancestral graph and a strided one (tag "strided"); stride and eta are NOT in the key -- the strided launches read them
         from device words, so one strided graph serves every stride.  A conditioned graph carries ("known", mode): it is never
-        replayed for an unconditioned request, nor the reverse, and "fixed" and "fresh" are different launches."""
+        replayed for an unconditioned request, nor the reverse, and "fixed" and "fresh" are different launches.  A resampled
+        graph carries ("resample",) -- other launches -- but not (jump, reps): they are device words.  ("shared",): the image and
+        keep planes of a slot chain have a sample stride of 0, which a capture bakes in."""
         fn, capture_safe = ReverseChain._resolve_noise(owner, denoise_fn)
         if isinstance(fn, SimplexNoiseFn):
             key = ("simplex", id(fn.simplex), fn.octave, fn.persistence, fn.frequency, fn.in_channels)
@@ -468,6 +579,10 @@ class ReverseChain:
             key += ("strided",)
         if key is not None and known is not None:
             key += (("known", ReverseChain._known_mode_of(owner, denoise_fn, known)),)
+        if key is not None and resampling is not None:
+            key += ("resample",)
+        if key is not None and known is not None and shared_planes:
+            key += ("shared",)
         return key
 
     def _set_streams(self, stream_base):
@@ -496,11 +611,16 @@ class ReverseChain:
         self.table_setup_ms = 1000.0 * (time.perf_counter() - t0)
         self.table_setup_steps = nsteps
 
-    def reset(self, x, t_distance, stream_base=None, sampler=None, known=None):
+    def reset(self, x, t_distance, stream_base=None, sampler=None, known=None, resampling=None):
         """Start another chain of the same batch shape on this chain's device buffers: the captured HIP graph (and the plan behind
         it) is reused instead of being built again -- the detection loops run hundreds of chains of one shape.  A strided chain
         may be handed another `sampler` (None: keep its own): the kept graph follows the re-written stride / eta words.  A
-        conditioned chain may be handed another `known` of its own mode (None: the planes stay as they are)."""
+        conditioned chain may be handed another `known` of its own mode (None: the planes stay as they are), a resampled one
+        another `resampling` (None: keep its own): the kept graph reads (jump, reps) from the re-written device words."""
+        if resampling is not None:
+            if self.resampling is None:
+                raise ValueError("ReverseChain.reset: a chain without resampling cannot be restarted as a resampled one")
+            self.resampling = _check_resampling(resampling)
         if known is not None:
             if self.known_mode is None:
                 raise ValueError("ReverseChain.reset: an unconditioned chain cannot be restarted as a conditioned one")
@@ -533,6 +653,13 @@ class ReverseChain:
         self.t.fill_(int(t_distance) - 1)
         self.step_idx.zero_()
         self.remaining = int(t_distance) if self.sampler is None else self.sampler.steps(t_distance)
+        if self.resampling is not None:
+            self.remaining = self.resampling.steps(t_distance)
+            self.rs_top.fill_(int(t_distance) - 1)
+            self.rs_rep.fill_(self.resampling.reps - 1)
+            self.rs_visit.zero_()
+            self.rs_jump.fill_(self.resampling.jump)
+            self.rs_reps.fill_(self.resampling.reps)
         if self.sampler is not None:
             self.owner._sampler_words(self.x.device, self.sampler)
         if self.tables is not None:
@@ -545,7 +672,7 @@ class ReverseChain:
             if self.k_noise is not None:
                 if torch.is_tensor(known.noise):
                     self.k_noise.copy_(known.noise)
-                elif int(t_distance) > 0:
+                elif int(t_distance) > 0 and not self.shared_planes:      # a slot chain's planes are filled per refill
                     t_top = torch.full((self.B,), int(t_distance) - 1, device=self.x.device, dtype=torch.int64)
                     self.k_noise.copy_(self.owner.noise_fn(self.k_x0, t_top).float())
 
@@ -610,6 +737,15 @@ class ReverseChain:
             else:
                 noise = o._denoise_noise(self.x, self.t, self.denoise_fn)
             words = o._sampler_words(self.x.device, None) if self.sampler is not None else None
+            if self.resampling is not None:
+                # an unseeded chain draws the re-noise plane next to its step-noise plane; a seeded one generates both in the launch
+                renoise = torch.randn_like(self.x) if self.streams is None else None
+                state = (self.rs_jump, self.rs_reps, self.rs_top, self.rs_rep, self.rs_visit)
+                o._known_update(self.x, self.t, eps, noise, (self.k_x0, self.k_keep, self.k_noise), None, want_pred=False,
+                                out=self.x, gauss_streams=self.streams, resample=state + (renoise,))
+                check(lib().anoddpm_chain_advance_resample(ptr(self.t), self.B, ptr(self.step_idx), *(ptr(w) for w in state),
+                                                           current_stream()), "chain_advance_resample")
+                return
             if self.known_mode is not None:
                 o._known_update(self.x, self.t, eps, noise, (self.k_x0, self.k_keep, self.k_noise), words, want_pred=False,
                                 out=self.x, gauss_streams=self.streams)
@@ -760,6 +896,12 @@ class GaussianDiffusionModel:
     # Read by ReverseChain / reverse_chain / forward_backward and the detection loops unless they are handed `sampler=`; also set at
     # construction from ANODDPM_SAMPLER="<stride>[,<eta>]".  A plain attribute like `postprocess`.
     sampler = None
+    # opt-in known-region conditioning of the detection sweeps: `detection_keep`, a mask tensor [1 or C, H, W] or
+    # [1, 1 or C, H, W] (nonzero = keep), ties those pixels of every chain of detection_A / detection_B to the input image
+    # (KnownRegion(x_0, keep, "fixed")); `resampling` (Resampling; also ANODDPM_RESAMPLE="<jump>,<reps>") adds the jumps.  Both
+    # None: the sweeps issue exactly the unconditioned launches.  `resampling` without `detection_keep` is refused by the sweep.
+    detection_keep = None
+    resampling = None
 
     def __init__(self, img_size, betas, img_channels=1, loss_type="l2", loss_weight='none', noise="gauss"):
         super().__init__()
@@ -811,6 +953,9 @@ class GaussianDiffusionModel:
         env = os.environ.get("ANODDPM_SAMPLER")
         if env:
             self.sampler = StridedSampler.parse(env)
+        env = os.environ.get("ANODDPM_RESAMPLE")
+        if env:
+            self.resampling = Resampling.parse(env)
 
     # ------------------------------------------------------------------ seeded gaussian noise
     def seed_gauss(self, seed):
@@ -894,11 +1039,13 @@ class GaussianDiffusionModel:
 
     # ------------------------------------------------------------------ known-region conditioning
     def _known_update(self, x_t, t, eps, noise, planes, words, want_pred=True, want_mean=False, out=None, gauss_streams=None,
-                      stream0=None):
+                      stream0=None, resample=None):
         """One fused launch of the conditioned step (anoddpm_p_sample_update_known), the counterpart of `_reverse_update`
         (`words` None) and `_strided_update` (`words`: the device's sampler words, used as they are).  planes = (x_0, keep bytes,
         known-region noise or None: generated in the launch), each fp32 / uint8, contiguous, batch 1 or B.  The seeded key block is
         handed over with `gauss_streams` (device int32[B]) or `stream0` (sample b draws from stream0 + b).
+        resample = (jump word, reps word, top, rep, visit, re-noise or None: generated), device tensors: the launch is
+        anoddpm_p_sample_update_resample (ancestral only, `words` None), which also carries out the samples' jumps.
         -> (x_prev, pred_x_0, mean)."""
         _lib.require_cuda(x_t, "GaussianDiffusionModel.sample_p_known")
         tb = self._tables(x_t.device)
@@ -927,6 +1074,20 @@ class GaussianDiffusionModel:
         k.x0_stride, k.keep_stride = (a.n if x_0.shape[0] == a.B else 0), (a.n if keep.shape[0] == a.B else 0)
         k.noise_stride = a.n if kz is not None and kz.shape[0] == a.B else 0
         seeded = gauss_streams is not None or stream0 is not None
+        if resample is not None:
+            if words is not None:
+                raise ValueError("sample_p_known: resampling is refused under a strided sampler")
+            r = ResamplingArgs()
+            rz = resample[5]
+            if rz is not None:
+                rz = self._f32(rz.detach())
+            r.jump, r.reps, r.top, r.rep, r.visit = (w.data_ptr() for w in resample[:5])
+            r.noise, r.noise_stride = (rz.data_ptr() if rz is not None else None), (a.n if rz is not None and rz.shape[0] == a.B else 0)
+            r.alphas_cumprod = self._sampler_words(x_t.device, None).acp.data_ptr()
+            check(lib().anoddpm_p_sample_update_resample(
+                ctypes.byref(a), ctypes.byref(k), ctypes.byref(r), ptr(self._gauss_seed_dev(x_t.device)) if seeded else None,
+                ptr(gauss_streams), int(stream0 or 0) & 0xFFFFFFFF, current_stream()), "p_sample_update_resample")
+            return x_prev, pred, mean
         check(lib().anoddpm_p_sample_update_known(
             ctypes.byref(a), ctypes.byref(k), ptr(words.acp) if words else None, ptr(words.stride) if words else None,
             ptr(words.eta) if words else None, ptr(self._gauss_seed_dev(x_t.device)) if seeded else None, ptr(gauss_streams),
@@ -1104,13 +1265,17 @@ class GaussianDiffusionModel:
         return {"sample": sample, "pred_x_0": pred}
 
     def forward_backward(self, model, x, see_whole_sequence="half", t_distance=None, denoise_fn="gauss", sampler=None, keep=None,
-                         known_noise="fixed"):
+                         known_noise="fixed", resampling=None):
         """GaussianDiffusion.py:320-359.  `t` lives on the device for the whole chain.  `sampler` (else `self.sampler`): a
         StridedSampler runs the reverse half in ceil(t_distance / stride) steps, and `seq` then holds one image per step.
         `keep` ([B or 1, C or 1, H, W], nonzero = keep): the reverse half is conditioned on `x` itself (KnownRegion) --
         with known_noise "fixed" on the forward noise drawn here for sample_q (the "whole" form, which noises gradually, draws one
-        more `noise_fn(x, t_distance - 1)` for it), with "fresh" on a new seeded draw per step."""
+        more `noise_fn(x, t_distance - 1)` for it), with "fresh" on a new seeded draw per step.  `resampling` (a Resampling, with
+        `keep` only, and never under a sampler -- `self.sampler` included): the reverse half takes the schedule's jumps (DESIGN
+        9r), and `seq` holds one image per UNet evaluation."""
         sampler = _check_sampler(sampler) if sampler is not None else self.sampler
+        if _check_resampling(resampling) is not None and keep is None:
+            raise ValueError("forward_backward: resampling requires `keep` (a known region)")
         assert see_whole_sequence == "whole" or see_whole_sequence == "half" or see_whole_sequence == None
 
         if t_distance == 0:
@@ -1143,25 +1308,29 @@ class GaussianDiffusionModel:
                 known_noise = fwd_noise
             known = KnownRegion(x_in, keep, known_noise)
         with torch.no_grad():
-            x = self._reverse_chain(model, x, int(t_distance), denoise_fn, seq if see_whole_sequence else None, sampler, known)
+            x = self._reverse_chain(model, x, int(t_distance), denoise_fn, seq if see_whole_sequence else None, sampler, known,
+                                    resampling)
         return x.detach() if not see_whole_sequence else seq
 
     p_sample_loop = forward_backward          # north-star alias
 
-    def _chain_for(self, model, x, t_distance, denoise_fn, stream_base=None, sampler=None, known=None):
+    def _chain_for(self, model, x, t_distance, denoise_fn, stream_base=None, sampler=None, known=None, resampling=None,
+                   shared_planes=False):
         """A ReverseChain for (model, batch shape, noise source): chains that replay a captured graph are kept -- at most eight,
         oldest dropped first; they hold their model -- and restarted with reset() (same device buffers, same graph); anything
         else is built fresh."""
         cache = self.__dict__.setdefault("_chains", {})
-        want = ReverseChain._reuse_key_of(self, denoise_fn, sampler, known)
+        ReverseChain._check_resample_request(self, denoise_fn, sampler, known, resampling)
+        want = ReverseChain._reuse_key_of(self, denoise_fn, sampler, known, resampling, shared_planes)
         if want is not None:
             key = (id(model), tuple(x.shape), str(x.device), want)
             chain = cache.get(key)
             # a kept chain replays the dropout-free inference graph: not for a model that has since been put in train() mode
             # with dropout > 0 (it gets a fresh eager chain below, which is not kept)
             if chain is not None and chain.model is model and not ReverseChain._draws_dropout(model):
-                return chain.reset(x, t_distance, stream_base, sampler, known)
-        chain = ReverseChain(self, model, x, t_distance, denoise_fn, stream_base=stream_base, sampler=sampler, known=known)
+                return chain.reset(x, t_distance, stream_base, sampler, known, resampling)
+        chain = ReverseChain(self, model, x, t_distance, denoise_fn, stream_base=stream_base, sampler=sampler, known=known,
+                             resampling=resampling, shared_planes=shared_planes)
         if chain.use_graph and chain.reuse_key is not None:
             if len(cache) >= 8:
                 if x.is_cuda:
@@ -1170,10 +1339,10 @@ class GaussianDiffusionModel:
             cache[(id(model), tuple(x.shape), str(x.device), chain.reuse_key)] = chain
         return chain
 
-    def _reverse_chain(self, model, x, t_distance, denoise_fn, seq, sampler=None, known=None):
+    def _reverse_chain(self, model, x, t_distance, denoise_fn, seq, sampler=None, known=None, resampling=None):
         """t = t_distance-1 ... 0 of sample_p with a device-resident timestep (no per-step H2D); with a `sampler` the
         ceil(t_distance / stride) strided steps."""
-        chain = self._chain_for(model, x, t_distance, denoise_fn, sampler=sampler, known=known)
+        chain = self._chain_for(model, x, t_distance, denoise_fn, sampler=sampler, known=known, resampling=resampling)
         for _ in range(chain.remaining):
             chain.step()
             if seq is not None:
@@ -1208,12 +1377,13 @@ class GaussianDiffusionModel:
             new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
-    def reverse_chain(self, model, x_t, t_distance, denoise_fn="gauss", sampler=None, known=None):
+    def reverse_chain(self, model, x_t, t_distance, denoise_fn="gauss", sampler=None, known=None, resampling=None):
         """Stepping form of the reverse loop of forward_backward (:351-357): returns a ReverseChain whose
         .step() performs one sample_p on the device-resident state (bench.py times K of these).  `sampler` (else `self.sampler`):
-        a StridedSampler makes each step a strided one.  `known`: a KnownRegion makes each step a conditioned one."""
+        a StridedSampler makes each step a strided one.  `known`: a KnownRegion makes each step a conditioned one; `resampling`: a
+        Resampling adds the schedule's jumps to a conditioned ancestral chain (`remaining` then counts UNet evaluations)."""
         sampler = _check_sampler(sampler) if sampler is not None else self.sampler
-        return ReverseChain(self, model, x_t, int(t_distance), denoise_fn, sampler=sampler, known=known)
+        return ReverseChain(self, model, x_t, int(t_distance), denoise_fn, sampler=sampler, known=known, resampling=resampling)
 
     def sample_q(self, x_0, t, noise):
         """q(x_t | x_0), GaussianDiffusion.py:361-371 -- one fused launch."""
@@ -1380,7 +1550,7 @@ class GaussianDiffusionModel:
         t_tensor = torch.full((1,), int(t_distance), device=x_0.device, dtype=torch.int64)
         return [self.noise_fn(x_0, t_tensor).float() for _ in range(n)]
 
-    def _run_chains(self, model, x_0, t_distances, noise, slots=None, sampler=None):
+    def _run_chains(self, model, x_0, t_distances, noise, slots=None, sampler=None, known=None, resampling=None):
         """Reverse chains of ONE image with individual lengths, batched over `slots` chain slots.
 
         t_distances[c] / noise[c]: chain c is `sample_q(x_0, t_distances[c], noise[c])` followed by t_distances[c] steps of
@@ -1389,15 +1559,29 @@ class GaussianDiffusionModel:
         `noise=None` asks for the seeded forward noise of the same streams.  Returns the final
         images, [len(t_distances), C, H, W].  The schedule (which slot, which global step) is kept in `self.last_chain_schedule`.
         `sampler` (else `self.sampler`): with a StridedSampler chain c takes ceil(t_distances[c] / stride) strided steps, and the
-        schedule counts those."""
+        schedule counts those.
+        `known` (a KnownRegion of ONE image: x_0 and keep of batch 1, noise "fixed" or "fresh"): every step is the conditioned one
+        (DESIGN 9q), the image and keep planes shared by all slots; with "fixed" the known-region noise of chain c is the forward
+        noise chain c was noised with, copied into the slot's plane on refill.  `resampling` (a Resampling, with `known`, never
+        with a sampler): chain c takes resampling.steps(t_distances[c]) evaluations, the schedule counts those, and a refill also
+        writes the slot's (top, rep, visit).  Neither is taken from `self`: the detection routines hand them over."""
         import os
         _lib.require_cuda(x_0, "GaussianDiffusionModel.detection")
         if x_0.shape[0] != 1:
             raise ValueError("detection loops take one image (upstream stores each chain into output[avg], :514)")
         sampler = _check_sampler(sampler) if sampler is not None else self.sampler
+        ReverseChain._check_resample_request(self, "gauss", sampler, _check_known(known), resampling)
+        if known is not None:
+            known.check_batch((1,) + tuple(x_0.shape[1:]))
+            if torch.is_tensor(known.noise):
+                raise ValueError("_run_chains: the fixed known-region noise of a sweep is each chain's own forward noise; a noise "
+                                 "tensor is refused -- use noise='fixed' or 'fresh'")
+            known_mode = ReverseChain._known_mode_of(self, "gauss", known)
         n = len(t_distances)
         lens = [int(d) for d in t_distances]
         steps = lens if sampler is None else [sampler.steps(l) for l in lens]      # reverse steps of each chain
+        if resampling is not None:
+            steps = [resampling.steps(l) for l in lens]
         out = torch.empty((n,) + tuple(x_0.shape[1:]), device=x_0.device, dtype=torch.float32)
         if n == 0:
             return out
@@ -1422,10 +1606,13 @@ class GaussianDiffusionModel:
         t_all = torch.tensor(lens, device=x_0.device, dtype=torch.int64)
         seeded = self.gauss_seed is not None
         base = self._take_streams(n) if seeded else None
+        fixed = known is not None and known_mode == "fixed"                # the chains' forward noise is kept for the known region
         if noise is None and seeded:
-            x_start, _ = self._q_sample_gauss(x_0.repeat(n, 1, 1, 1), t_all, base)
+            x_start, noise = self._q_sample_gauss(x_0.repeat(n, 1, 1, 1), t_all, base, want_noise=fixed)
         else:
             x_start = self.sample_q(x_0.repeat(n, 1, 1, 1), t_all, noise)
+        if fixed:
+            noise = self._f32(noise).to(x_0.device)
         live = [c for c in range(n) if lens[c] > 0]
         live_steps = [steps[c] for c in live]
         for c in range(n):
@@ -1446,7 +1633,7 @@ class GaussianDiffusionModel:
             try:
                 with torch.no_grad():
                     chain = self._chain_for(model, x_start[:1].expand(G, -1, -1, -1).contiguous(), 1, "gauss", stream_base=base,
-                                            sampler=sampler)
+                                            sampler=sampler, known=known, resampling=resampling, shared_planes=known is not None)
                     chain.slot_chain = True
                     if chain.hip_model:
                         model._plan_for(G, x_start.shape[2], x_start.device)     # the large allocation: not left to the first step
@@ -1468,6 +1655,8 @@ class GaussianDiffusionModel:
             for slot in range(G):
                 if last_busy[slot] == 0:                                # no chain (n counts the zero-length ones): a valid timestep to idle on
                     chain.t[slot:slot + 1].fill_(makespan - 1)
+            if resampling is not None:
+                chain.rs_top.fill_(-1)                                  # a slot without a chain never jumps; refills write the rest
             for k in range(makespan):
                 for slot, i in refill.get(k, ()):
                     c = live[i]
@@ -1475,10 +1664,18 @@ class GaussianDiffusionModel:
                     chain.t[slot:slot + 1].fill_(lens[c] - 1)
                     if seeded:
                         chain.streams[slot:slot + 1].fill_(philox.signed32(base + c))
+                    if fixed:
+                        chain.k_noise[slot].copy_(noise[c])
+                    if resampling is not None:
+                        chain.rs_top[slot:slot + 1].fill_(lens[c] - 1)
+                        chain.rs_rep[slot:slot + 1].fill_(resampling.reps - 1)
+                        chain.rs_visit[slot:slot + 1].zero_()
                 chain.step()
                 for slot, i in harvest.get(k, ()):
                     out[live[i]].copy_(chain.x[slot])
-                    if last_busy[slot] == k + 1 and k + 1 < makespan and sampler is None:
+                    if last_busy[slot] == k + 1 and k + 1 < makespan and resampling is not None:
+                        chain.rs_top[slot:slot + 1].fill_(-1)           # idle: never jumps; the advance floors its t at 0
+                    elif last_busy[slot] == k + 1 and k + 1 < makespan and sampler is None:
                         # nothing left for this slot: it idles on its last image with a timestep that stays >= 0 to the end
                         # (a strided chain's advance floors t at 0 by itself)
                         chain.t[slot:slot + 1].fill_(makespan - k - 2)
@@ -1531,6 +1728,18 @@ class GaussianDiffusionModel:
             for j, rec in enumerate(self.last_detection):
                 rec.update({k + "_at": at[k][j] for k in ("dice", "precision", "recall", "fpr")})
 
+    def _detection_conditioning(self, x_0):
+        """What `detection_keep` / `resampling` add to the sweep's `_run_chains` call; both unset: nothing at all."""
+        if self.detection_keep is None:
+            if self.resampling is not None:
+                raise ValueError("detection: `resampling` is set without `detection_keep`; resampling needs a known region")
+            return {}
+        keep = self.detection_keep
+        if not torch.is_tensor(keep) or keep.dim() not in (3, 4):
+            raise ValueError("detection_keep must be a mask tensor [1 or C, H, W] or [1, 1 or C, H, W]")
+        keep = keep if keep.dim() == 4 else keep[None]
+        return {"known": KnownRegion(x_0, keep.to(x_0.device), noise="fixed"), "resampling": self.resampling}
+
     def detection_A(self, model, x_0, args, file, mask, total_avg=2):
         """GaussianDiffusion.py:480-529: simplex frequencies 2^7..2^1 x t_distance 50..0.6T step 50, `total_avg` chains each -- all
         of them one batched reverse loop (`_run_chains`).  Returns None as upstream; the per-setting results upstream only plots
@@ -1544,7 +1753,7 @@ class GaussianDiffusionModel:
                 settings.append({"freq": i, "t_distance": t_distance})
                 dists += [t_distance] * total_avg
                 noise += self._forward_noise(x_0, t_distance, total_avg)
-        outputs = self._run_chains(model, x_0, dists, torch.cat(noise) if noise else None)
+        outputs = self._run_chains(model, x_0, dists, torch.cat(noise) if noise else None, **self._detection_conditioning(x_0))
         self._score_settings(settings, outputs, total_avg, x_0, mask)
 
     def detection_B(self, model, x_0, args, file, mask, denoise_fn="gauss", total_avg=5):
@@ -1564,6 +1773,6 @@ class GaussianDiffusionModel:
         for t_distance in settings:
             dists += [t_distance] * total_avg
             noise += self._forward_noise(x_0, t_distance, total_avg)
-        outputs = self._run_chains(model, x_0, dists, torch.cat(noise) if noise else None)
+        outputs = self._run_chains(model, x_0, dists, torch.cat(noise) if noise else None, **self._detection_conditioning(x_0))
         self._score_settings([{"t_distance": t_distance} for t_distance in settings], outputs, total_avg, x_0, mask)
         return [None] * len(settings)                               # evaluation.heatmap() returns None (evaluation.py:12-22)

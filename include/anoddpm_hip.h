@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 38
+#define ANODDPM_ABI_VERSION 39
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -142,7 +142,8 @@ int anoddpm_chain_advance(int64_t *t, int32_t B, int32_t *step, void *stream);
  *   normals    u(w) = ((w >> 9) + 0.5) * 2^-23;  r = sqrtf(-2 logf(u(w0)));  elements 4 quad + 0 / 1 = r cos / sin(2 pi u(w1)),
  *              elements 4 quad + 2 / 3 the same from (w2, w3).  A partial last quad uses its leading lanes.
  *   domain     0 reverse-step noise, 1 forward / training noise, 2 plain fill, 3 known-region noise (the step is the timestep
- *              the step LANDS on; see anoddpm_p_sample_update_known at the end of this file).
+ *              the step LANDS on; see anoddpm_p_sample_update_known at the end of this file), 4 re-noise of a resampling jump.
+ *              A resampled chain adds 8 * visit to 0, 3 and 4 (anoddpm_p_sample_update_resample).
  * Key block, the same four arguments in every entry point below:
  *   seed     [dev] one 64-bit seed
  *   streams  [dev] int32[B] read as uint32: the stream of sample b; NULL: stream0 + b
@@ -1473,6 +1474,44 @@ typedef struct anoddpm_known_args {
 int anoddpm_p_sample_update_known(const anoddpm_p_update_args *a, const anoddpm_known_args *k, const double *alphas_cumprod,
                                   const int32_t *stride, const float *eta, const uint64_t *seed, const int32_t *streams,
                                   uint32_t stream0, void *stream);
+
+/* ------------------------------------------------------------------ resampling jumps */
+
+/* The resampling loop of RePaint (Lugmayr et al., CVPR 2022, Algorithm 1) on the conditioned step above, ancestral
+ * only.  A chain carries, per sample, the level `top` it started from, the repetitions `rep` it has left and the count `visit` of
+ * jumps it has taken; `jump` (J) and `reps` (R) are one word each.  ONE launch, per sample b with ti the normalised t[b],
+ * s = ti - 1 and v = visit[b]:
+ *   x_s    = what anoddpm_p_sample_update_known (ancestral) writes to x_prev, except that generated noise uses Philox domain
+ *            0 + 8 v (step noise, step ti) and 3 + 8 v (known-region noise, step s)
+ *   jumps  = s >= 0 && s % J == 0 && s + J <= top[b] && rep[b] > 0
+ *   land   = jumps ? s + J : s
+ *   x_prev = jumps ? A * x_s + C * rz : x_s                       separate mul, mul, add; EVERY pixel, kept ones included
+ *   A, C   = (float)sqrt(acp[land] / acp[s]), (float)sqrt(1 - acp[land] / acp[s])      fp64, each rounded to fp32 once
+ *   rz     = r->noise, or -- when that is NULL -- generated from the key block in domain 4 + 8 v at step land
+ * pred_x0 and mean_out are those of the unconditioned update.  With v == 0 and no jump the launch writes the bits of
+ * anoddpm_p_sample_update_known.  The launch reads the state and writes none of it: anoddpm_chain_advance_resample is its only
+ * writer.  An out-of-range t[b], a J or R word < 1, or a jump that would land beyond the schedule (a `top` >= a->T) makes every
+ * element of x_prev of that sample NaN; such a sample takes no jump and nothing is read out of bounds.
+ * seed == NULL: a->noise (or none), k->noise and r->noise are read, the latter two are required; otherwise a->noise must be NULL. */
+/* (anoddpm_resample_args is the 2x up / down resampling of the UNet: this one is named for the schedule.) */
+typedef struct anoddpm_resampling_args {
+    const int32_t *jump, *reps;        /* [dev] one word each, read at run time: a kept graph follows re-written words */
+    const int32_t *top, *rep, *visit;  /* [dev] int32[B] chain state */
+    const float *noise;                /* [dev] fp32 re-noise, sample b at noise + b * noise_stride; or NULL */
+    const double *alphas_cumprod;      /* [dev] fp64[a->T] */
+    int64_t noise_stride;              /* 0 (one plane for all samples) or a->n */
+} anoddpm_resampling_args;
+
+int anoddpm_p_sample_update_resample(const anoddpm_p_update_args *a, const anoddpm_known_args *k, const anoddpm_resampling_args *r,
+                                     const uint64_t *seed, const int32_t *streams, uint32_t stream0, void *stream);
+
+/* The state rules of a resampled chain, one thread per sample (B <= 1024), then *step += 1 (step may be NULL).  With s = t[b] - 1:
+ *   jumps (the predicate above)               t[b] = s + J, rep[b] -= 1, visit[b] += 1
+ *   else s >= 0 && s % J == 0                 rep[b] = R - 1, t[b] = s
+ *   else                                      t[b] = max(s, 0)
+ * With a J or R word < 1 only the last rule applies. */
+int anoddpm_chain_advance_resample(int64_t *t, int32_t B, int32_t *step, const int32_t *jump, const int32_t *reps,
+                                   const int32_t *top, int32_t *rep, int32_t *visit, void *stream);
 
 #ifdef __cplusplus
 }
