@@ -126,6 +126,7 @@ PHILOX_REVERSE, PHILOX_FORWARD, PHILOX_FILL, PHILOX_KNOWN, PHILOX_RENOISE = 0, 1
 SSIM_MAX_WIN = 15
 MEDIAN_SIZES = (3, 5, 7)                                                                # anoddpm_median_args.k
 ERODE_MAX = 8                                                                           # anoddpm_erode_args.n
+KEEP_DILATE_MAX = 8                                                                     # anoddpm_keep_mask_args.r
 
 _lib = None
 

@@ -1776,3 +1776,61 @@ class GaussianDiffusionModel:
         outputs = self._run_chains(model, x_0, dists, torch.cat(noise) if noise else None, **self._detection_conditioning(x_0))
         self._score_settings([{"t_distance": t_distance} for t_distance in settings], outputs, total_avg, x_0, mask)
         return [None] * len(settings)                               # evaluation.heatmap() returns None (evaluation.py:12-22)
+
+    def detection_two_pass(self, model, x_0, mask, threshold, t_first, t_second, total_avg=5, dilate=2, smooth=None, roi=None,
+                           resampling=None, denoise_fn="gauss"):
+        """Two-pass detection (the mask / stitch / resample of AutoDDPM, Bercea et al., 2023) of ONE image; no
+        counterpart upstream.  Pass 1: `total_avg` unconditioned chains of length `t_first`, forward noise drawn as detection_B
+        draws it (`denoise_fn` "gauss" or "octave").  Their squared error against `x_0` (the maximum over the channels; with
+        `smooth=sigma` through `metrics.gaussian_filter`) is the score plane; `metrics.keep_mask(score, threshold, dilate, roi)` marks
+        what exceeds `threshold` (a number or a device tensor, e.g. `HealthyPool.thresholds`; never read on the host), grown by
+        `dilate` pixels, as the region to regenerate and stitches the start image: the first pass's mean there, `x_0` elsewhere.
+        Pass 2: for every entry of `t_second` (an int or a list) `total_avg` chains from the stitched image, every step conditioned
+        on it outside the region (KnownRegion(stitched, keep, "fixed")), with `resampling` (else `self.resampling`) and
+        `self.sampler` as in any conditioned sweep -- all in one `_run_chains` call, on pass 1's slot count so that neither pass
+        drops the other's kept graph.  Nothing exceeds the threshold: pass 2 keeps everything and returns the input, "nothing found".
+        Returns None; `self.last_detection` holds one record for pass 1 ({"t_distance": t_first, "pass": 1, ...}) and one per entry
+        of `t_second` ({"t_distance": t2, "pass": 2, "t_first": t_first, ...}), scored against `x_0` and `mask` by one
+        `_score_settings`; every record also carries `keep` (uint8 [1, 1, H, W]) and `regen` (int32 [1], on the device).  On a seeded
+        owner stream ids are taken in order: pass 1's chains, then pass 2's in setting order.  Between the passes and through the
+        scoring nothing synchronises with the host.  What this does to detection quality has not been measured."""
+        from . import metrics
+        if denoise_fn not in ("gauss", "octave"):
+            raise ValueError(f"detection_two_pass: denoise_fn must be 'gauss' or 'octave', got {denoise_fn!r}")
+        if isinstance(dilate, bool) or not isinstance(dilate, (int, np.integer)) or not 0 <= dilate <= _lib.KEEP_DILATE_MAX:
+            raise ValueError(f"detection_two_pass: dilate must be an integer in 0 ... {_lib.KEEP_DILATE_MAX}, got {dilate!r}")
+        if not torch.is_tensor(x_0) or x_0.dim() != 4 or x_0.shape[0] != 1:
+            raise ValueError("detection_two_pass: x_0 must be one image [1, C, H, W] (the detection loops take one image)")
+        if isinstance(total_avg, bool) or not isinstance(total_avg, (int, np.integer)) or total_avg < 1:
+            raise ValueError(f"detection_two_pass: total_avg must be an integer >= 1, got {total_avg!r}")
+        seconds = [t_second] if isinstance(t_second, (int, np.integer)) and not isinstance(t_second, bool) else list(t_second)
+        for name, v in [("t_first", t_first)] + [("t_second", v) for v in seconds]:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= self.num_timesteps - 1:
+                raise ValueError(f"detection_two_pass: {name} {v!r} is outside the schedule (an integer in 0 ... {self.num_timesteps - 1})")
+        resampling = _check_resampling(resampling) if resampling is not None else self.resampling
+        # what pass 2's sweep refuses (a sampler together with a resampling), before pass 1 is run: pass 2 always has a known region
+        ReverseChain._check_resample_request(self, "gauss", self.sampler, True, resampling)
+        t_first, seconds = int(t_first), [int(v) for v in seconds]
+        if denoise_fn == "octave":
+            self.noise_fn = SimplexNoiseFn(self.simplex, octave=6, persistence=0.8, frequency=64)
+        else:
+            self.noise_fn = GaussNoiseFn(self)
+        noise = self._forward_noise(x_0, t_first, total_avg)
+        outputs1 = self._run_chains(model, x_0, [t_first] * total_avg, torch.cat(noise) if noise else None)
+        slots = self.last_chain_schedule["slots"]
+        maps, _ = metrics.anomaly_maps(x_0, outputs1, None, want=("mean", "sqerr"))
+        score = maps["sqerr"] if x_0.shape[1] == 1 else maps["sqerr"].amax(dim=1, keepdim=True)
+        if smooth is not None:
+            score = metrics.gaussian_filter(score, sigma=smooth)
+        km = metrics.keep_mask(score[:, 0], threshold, dilate, roi, real=x_0, recon=maps["mean"])
+        stitched, keep = km["stitched"], km["keep"]
+        dists, noise = [], []
+        for t2 in seconds:
+            dists += [t2] * total_avg
+            noise += self._forward_noise(stitched, t2, total_avg)
+        outputs2 = self._run_chains(model, stitched, dists, torch.cat(noise) if noise else None, slots=slots,
+                                    known=KnownRegion(stitched, keep, "fixed"), resampling=resampling)
+        settings = [{"t_distance": t_first, "pass": 1}] + [{"t_distance": t2, "pass": 2, "t_first": t_first} for t2 in seconds]
+        self._score_settings(settings, torch.cat((outputs1, outputs2)), total_avg, x_0, mask)
+        for rec in self.last_detection:
+            rec["keep"], rec["regen"] = keep, km["regen"]

@@ -83,6 +83,11 @@ between workgroups, the fp64 sums in `image_scores`' order; `order_stats` is the
 `anomaly_metrics_at` score maps at thresholds that stay on the device (`anoddpm_threshold_counts`: exact tp / fp for up to 16
 thresholds from one pass).  No result is copied to the host, and no threshold is read there.
 
+Keep mask of a two-pass detection.  `keep_mask` turns a first-pass score plane and such a device-resident threshold into
+the bytes a `KnownRegion` stores -- threshold, scipy's `binary_dilation` by 0 ... 8 pixels inside an optional roi -- with the stitched
+start image of the second pass and the size of the region, in one launch (`anoddpm_keep_mask`, csrc/keepmask.hip);
+`GaussianDiffusionModel.detection_two_pass` is its caller.
+
 `score_maps` states the scoring pipeline once: R stacks of maps in, one launch per step whatever R is -- curve scores, SSIM, and
 opt-in the post-processing with its own curve scores, AUPRO and the boundary distances -- a dict of device tensors with a leading
 R axis out, without a host synchronisation; a score that cannot be computed has no key.  Its callers only say how a result
@@ -93,15 +98,16 @@ settings of a sweep and puts row j into record j as device tensors (None where t
 The individual functions accept the reference's arguments; they use the fused pass when handed device tensors of
 the shapes the reference passes and raise `AnoddpmError` otherwise (no CPU path)."""
 import ctypes
+import numbers
 import os
 
 import torch
 
 from . import _lib
-from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs, ErodeArgs, GaussArgs, MapScoresArgs, MedianArgs, ProArgs, RocArgs, SelectArgs,
+from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs, ErodeArgs, GaussArgs, KeepMaskArgs, MapScoresArgs, MedianArgs, ProArgs, RocArgs, SelectArgs,
                    SsimArgs, SurfaceArgs, ThresholdCountsArgs, check, current_stream, lib)
 
-__all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "PooledCurves", "PooledRegionCurves", "ssim", "median_filter", "erode_mask",
+__all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "PooledCurves", "PooledRegionCurves", "ssim", "median_filter", "erode_mask", "keep_mask",
            "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "aupro", "pro_points", "AUPRO", "distance_transform",
            "surface_distance", "HD95", "anomaly_metrics_surface", "gaussian_filter", "image_scores", "image_auc", "anomaly_metrics_image", "order_stats", "counts_at", "scores_at",
            "anomaly_metrics_at", "HealthyPool", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
@@ -516,6 +522,77 @@ def erode_mask(x, iterations=3, level=0.0):
     a.src, a.dst, a.src_stride = xt.data_ptr(), out.data_ptr(), H * W
     a.S, a.H, a.W, a.n, a.level = C, H, W, int(iterations), float(level)
     _launch("erode2d", a, xt.device)
+    return out
+
+
+def keep_mask(score, threshold, dilate=2, roi=None, real=None, recon=None, return_status=False):
+    """The step between the two passes of a two-pass detection, ONE launch (`anoddpm_keep_mask`, csrc/keepmask.hip), per
+    H x W plane of score ([..., H, W]; the leading dimensions are the S planes):
+      seed  = (plane > threshold) & roi;  grown = scipy.ndimage.binary_dilation(seed, iterations=dilate)  (the 4-neighbour cross,
+      nothing outside the image; dilate 0 ... 8);  regen = grown & roi;  keep = ~regen;  stitched = where(regen, recon, real)
+    `threshold`: a Python number (becomes a device fill, not a synchronising copy), a 1-element device tensor or a [S] device
+    tensor -- e.g. `HealthyPool.thresholds`; it is never read on the host.  Strictly greater; NaN is above nothing, and a NaN
+    threshold marks nothing.  `roi`: a 0 / 1 tensor of H * W (shared by all planes) or S * H * W values.  `real` [S or 1, C, H, W]
+    and `recon` [S, C, H, W] come together; the C channels share the plane's mask.  Returns a dict of device tensors, no host
+    synchronisation, the same bits every run: `keep` uint8, shaped like score with a channel dimension of 1 ([S, 1, H, W]: what
+    `KnownRegion` takes), `stitched` fp32 [S, C, H, W] or None, `regen` int32 [S] (the pixels with keep == 0) and, with
+    `return_status=True`, `status` int32 [S] (`ROC_NAN`: a NaN in the plane or its threshold; `ROC_BAD_MASK`: a roi value other
+    than 0 / 1).  What the mask does to detection quality has not been measured."""
+    if not isinstance(score, torch.Tensor):
+        raise TypeError("keep_mask: score must be a device tensor")
+    if isinstance(dilate, bool) or int(dilate) != dilate or not 0 <= dilate <= _lib.KEEP_DILATE_MAX:
+        raise ValueError(f"keep_mask: dilate must be an integer in 0 ... {_lib.KEEP_DILATE_MAX}, got {dilate!r}")
+    if score.dim() < 2 or score.numel() == 0:
+        raise ValueError(f"keep_mask: score must be [..., H, W] and not empty, got shape {tuple(score.shape)}")
+    if (real is None) != (recon is None):
+        raise ValueError("keep_mask: real and recon come together (the stitch needs both)")
+    H, W = score.shape[-2:]
+    S = score.numel() // (H * W)
+    if isinstance(threshold, torch.Tensor):
+        if threshold.numel() not in (1, S):
+            raise ValueError(f"keep_mask: threshold must hold 1 or {S} values (one per plane), got shape {tuple(threshold.shape)}")
+    elif isinstance(threshold, bool) or not isinstance(threshold, numbers.Real):
+        raise TypeError(f"keep_mask: threshold must be a number or a device tensor, got {type(threshold).__name__}")
+    for name, x in (("roi", roi), ("real", real), ("recon", recon)):
+        if x is not None and not isinstance(x, torch.Tensor):
+            raise TypeError(f"keep_mask: {name} must be a device tensor")
+    if roi is not None and roi.numel() not in (H * W, S * H * W):
+        raise ValueError(f"keep_mask: roi {tuple(roi.shape)} is neither one plane nor the shape of score {tuple(score.shape)}")
+    C = 1
+    if real is not None:
+        if recon.dim() != 4 or recon.shape[0] != S or tuple(recon.shape[2:]) != (H, W):
+            raise ValueError(f"keep_mask: recon must be [{S}, C, {H}, {W}], got {tuple(recon.shape)}")
+        C = recon.shape[1]
+        if real.dim() != 4 or real.shape[0] not in (1, S) or tuple(real.shape[1:]) != (C, H, W):
+            raise ValueError(f"keep_mask: real must be [{S} or 1, {C}, {H}, {W}], got {tuple(real.shape)}")
+    sc = _f32c(score, "keep_mask(score)")
+    dev = sc.device
+    a = KeepMaskArgs()
+    if isinstance(threshold, torch.Tensor):
+        thr = _f32c(threshold, "keep_mask(threshold)").reshape(-1)
+    else:
+        thr = torch.full((1,), float(threshold), dtype=torch.float32, device=dev)
+    hold = [sc, thr]                                                 # the fp32 copies live until the launch is enqueued
+    for name, x in (("roi", roi), ("real", real), ("recon", recon), ("threshold", thr)):
+        if x is not None:
+            x = _f32c(x, f"keep_mask({name})")
+            if x.device != dev:
+                raise ValueError(f"keep_mask: {name} and score are on different devices")
+            hold.append(x)
+            setattr(a, name, x.data_ptr())
+    out = {"keep": torch.empty((S, 1, H, W), dtype=torch.uint8, device=dev),
+           "stitched": torch.empty((S, C, H, W), dtype=torch.float32, device=dev) if real is not None else None,
+           "regen": torch.empty((S,), dtype=torch.int32, device=dev)}
+    status = torch.empty((S,), dtype=torch.int32, device=dev)
+    a.score, a.keep, a.regen_count, a.status = sc.data_ptr(), out["keep"].data_ptr(), out["regen"].data_ptr(), status.data_ptr()
+    a.stitched = out["stitched"].data_ptr() if real is not None else None
+    a.score_stride, a.thr_stride = H * W, (1 if thr.numel() == S and S > 1 else 0)
+    a.roi_stride = H * W if roi is not None and roi.numel() == S * H * W and S > 1 else 0
+    a.real_stride = C * H * W if real is not None and real.shape[0] == S and S > 1 else 0
+    a.S, a.H, a.W, a.C, a.r = S, H, W, C, int(dilate)
+    _launch("keep_mask", a, dev)
+    if return_status:
+        out["status"] = status
     return out
 
 

@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 39
+#define ANODDPM_ABI_VERSION 40
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -1512,6 +1512,51 @@ int anoddpm_p_sample_update_resample(const anoddpm_p_update_args *a, const anodd
  * With a J or R word < 1 only the last rule applies. */
 int anoddpm_chain_advance_resample(int64_t *t, int32_t B, int32_t *step, const int32_t *jump, const int32_t *reps,
                                    const int32_t *top, int32_t *rep, int32_t *visit, void *stream);
+
+/* ------------------------------------------------------------------ keep mask of a two-pass detection */
+
+/* The step between the two passes of a two-pass detection (the mask / stitch of AutoDDPM, Bercea et al., 2023): a first
+ * reconstruction says where the image looks abnormal, that region grown by a margin is regenerated in a second, conditioned pass
+ * (anoddpm_p_sample_update_known) and everything else stays tied to the input.  ONE launch, per plane p of S; the plane is H x W
+ * fp32 at score + p * score_stride, score_stride >= H*W:
+ *   thr        = threshold[p * thr_stride]            device memory, thr_stride 0 or 1; never a host value
+ *   seed(y,x)  = score(y,x) > thr  &&  (roi == NULL || roi(y,x) == 1)
+ *                NaN is above nothing; -0.0 is not above +0.0; strictly greater
+ *   grown      = scipy.ndimage.binary_dilation(seed, iterations=r) with scipy's defaults (4-neighbour cross, border_value=0),
+ *                0 <= r <= 8: r passes of the cross are ONE pass of the L1 ball of radius r, the outside of the image contributing
+ *                nothing; r = 0: grown = seed
+ *   regen(y,x) = grown(y,x)  &&  (roi == NULL || roi(y,x) == 1)
+ *   keep[p][y][x]        = regen ? 0 : 1              uint8, contiguous [S][H][W]: the byte format anoddpm_known_args.keep reads
+ *   stitched[p][c][y][x] = regen ? recon[p][c][y][x] : real[p][c][y][x]
+ *                optional, all three pointers or none; C >= 1 channels share the plane's mask; a select, so a NaN on one side
+ *                never reaches the other
+ *   regen_count[p]       = number of pixels with keep == 0   (int32)
+ *   status[p]            = ANODDPM_ROC_NAN if the plane's score or its threshold holds a NaN; ANODDPM_ROC_BAD_MASK for a roi value
+ *                other than 0 / 1
+ * roi: optional fp32 0/1 planes at roi + p * roi_stride, roi_stride 0 (one plane for all) or H*W, as in anoddpm_median2d.  real is
+ * at real + p * real_stride, real_stride 0 or C*H*W; recon and stitched are contiguous [S][C][H][W].  A NaN threshold marks
+ * nothing: all comparisons are false, every pixel is kept, and the status bit is set.  No allocation and no host synchronisation:
+ * regen_count and status are cleared by an asynchronous memset on the stream before the launch.  A workgroup stages a 16 x 32 tile
+ * of a plane with an r-pixel LDS halo (several tiles of a tile row, one after the other, once the grid would exceed what the chip
+ * holds at a time) and adds its count once; outputs are a set and integers, so the bits are the same every run.
+ * Refused (ANODDPM_EINVAL): null args; null score, threshold, keep, regen_count or status; r outside 0 ... 8; S, H, W or C < 1, or
+ * S * tiles >= 2^31; score_stride < H*W with S > 1; thr_stride not 0 / 1; roi_stride not 0 / H*W; real_stride not 0 / C*H*W; only
+ * one or two of real, recon, stitched. */
+typedef struct anoddpm_keep_mask_args {
+    const float *score;             /* [dev] */
+    const float *threshold;         /* [dev] one word, or [S] */
+    const float *roi;               /* [dev] or NULL */
+    const float *real;              /* [dev] or NULL */
+    const float *recon;             /* [dev] [S][C][H][W] or NULL */
+    uint8_t *keep;                  /* [dev] [S][H][W] */
+    float *stitched;                /* [dev] [S][C][H][W] or NULL */
+    int32_t *regen_count;           /* [dev] [S] */
+    int32_t *status;                /* [dev] [S] */
+    int64_t score_stride, thr_stride, roi_stride, real_stride;
+    int32_t S, H, W, C, r;
+} anoddpm_keep_mask_args;
+
+int anoddpm_keep_mask(const anoddpm_keep_mask_args *a, void *stream);
 
 #ifdef __cplusplus
 }
