@@ -125,6 +125,7 @@ SYMBOLS = list(_PROTOS)
 PHILOX_REVERSE, PHILOX_FORWARD, PHILOX_FILL, PHILOX_KNOWN, PHILOX_RENOISE = 0, 1, 2, 3, 4                          # the `domain` word of the philox counter
 SSIM_MAX_WIN = 15
 MEDIAN_SIZES = (3, 5, 7)                                                                # anoddpm_median_args.k
+MEDIAN3D_SIZES = (3, 5)                                                                 # anoddpm_median3d_args.k
 ERODE_MAX = 8                                                                           # anoddpm_erode_args.n
 KEEP_DILATE_MAX = 8                                                                     # anoddpm_keep_mask_args.r
 

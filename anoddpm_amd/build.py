@@ -39,6 +39,7 @@ SOURCES = {
     "surface.hip": ["-ffp-contract=off"],
     "ssim.hip": ["-ffp-contract=off"],
     "postproc.hip": [],
+    "postproc3d.hip": [],
     "keepmask.hip": ["-ffp-contract=off"],
     "smooth.hip": ["-ffp-contract=off"],
     "select_wide.hip": ["-ffp-contract=off"],

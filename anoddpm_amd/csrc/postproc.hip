@@ -33,6 +33,7 @@
 // size[root] at every foreground pixel, 0 elsewhere, and counts the roots of each plane.
 #include <math.h>
 #include "common.h"
+#include "cc_shared.h"
 
 namespace {
 
@@ -155,45 +156,15 @@ __global__ __launch_bounds__(THREADS) void erode_kernel(anoddpm_erode_args a, in
 }
 
 // ---------------------------------------------------------------------------------------------------- small components
-// Every kernel: blocks_per_plane workgroups per plane, thread -> pixel p of its plane, global index plane * H*W + p < 2^31.
-struct Pixel { int64_t plane; int p, idx; bool valid; };
-
-__device__ __forceinline__ Pixel pixel_of(int bpp, int hw)
-{
-    Pixel q;
-    q.plane = blockIdx.x / bpp;
-    q.p = (int)(blockIdx.x % bpp) * THREADS + (int)threadIdx.x;
-    q.valid = q.p < hw;
-    q.idx = (int)(q.plane * hw + q.p);
-    return q;
-}
-
-__device__ __forceinline__ int load_label(const int *label, int i)
-{
-    return __hip_atomic_load(label + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int find_root(const int *label, int x)
-{
-    for (;;) {
-        const int p = load_label(label, x);                          // p <= x always: the walk ends
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-__device__ void link(int *label, int a, int b)
-{
-    for (;;) {
-        a = find_root(label, a);
-        b = find_root(label, b);
-        if (a == b) return;
-        if (a > b) { const int s = a; a = b; b = s; }
-        const int old = atomicMin(&label[b], a);
-        if (old == b) return;                                        // b was a root and now hangs below a
-        b = old;                                                     // b had a parent already: join that one with a as well
-    }
-}
+// Every kernel: blocks_per_plane workgroups per plane, thread -> pixel p of its plane, global index plane * H*W + p < 2^31.  The
+// union-find primitives are those of cc_shared.h, shared with the volumes of postproc3d.hip.
+using anoddpm::cc::Pixel;
+using anoddpm::cc::pixel_of;
+using anoddpm::cc::load_label;
+using anoddpm::cc::find_root;
+using anoddpm::cc::link;
+using anoddpm::cc::add_sizes;
+static_assert(THREADS == anoddpm::cc::THREADS, "pixel_of counts in workgroups of cc::THREADS");
 
 __global__ __launch_bounds__(THREADS) void cc_clear_kernel(anoddpm_components_args a, int *label, int *size, int bpp)
 {
@@ -231,16 +202,7 @@ __global__ __launch_bounds__(THREADS) void cc_flatten_kernel(anoddpm_components_
 __global__ __launch_bounds__(THREADS) void cc_size_kernel(anoddpm_components_args a, const int *__restrict__ label, int *size, int bpp)
 {
     const Pixel q = pixel_of(bpp, a.H * a.W);
-    const int root = q.valid ? label[q.idx] : -1;
-    const bool fg = root >= 0;
-    const unsigned long long any = __ballot(fg);
-    if (any == 0) return;
-    const int leader = __ffsll(any) - 1;
-    const int first = __shfl(root, leader);
-    const bool same = fg && root == first;
-    const unsigned long long group = __ballot(same);
-    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&size[first], __popcll(group));
-    else if (fg && !same) atomicAdd(&size[root], 1);
+    add_sizes(size, q.valid ? label[q.idx] : -1);
 }
 
 __global__ __launch_bounds__(THREADS) void cc_filter_kernel(anoddpm_components_args a, const int *__restrict__ label,

@@ -67,6 +67,13 @@ prediction against its reference or against one shared reference, in four launch
 selected on the integer squared distances and the means are fp64 sums in a fixed order, so the same input gives the same bits.
 `HD95` returns a Python float.  Pixel units only (no `sampling=`), 2-D planes only, one threshold per call.
 
+Volume-wise post-processing (csrc/postproc3d.hip).  The protocols the defaults above come from report one Dice per volume:
+they filter the residual volume, erode the brain mask and drop small components in 3-D, which is not the plane-wise result slice
+by slice.  `median_filter3d` (windows 3 / 5, reflect border on all three axes, any depth), `erode_mask3d` (the 6-neighbour cross)
+and `remove_small_components3d` / `component_areas3d` (6 / 18 / 26 neighbours) are scipy's results bit for bit on `[..., D, H, W]`
+tensors; `VolumePostProcess` holds the settings, `postprocess_volumes` applies them and `anomaly_metrics_volume` scores every
+volume as ONE segment.  Nothing above changes when they are not called.
+
 Texture protocol (Bergmann et al.; the reference evaluates DAGM carpet and MVTec leather with the brain-MRI code path).  Published
 pipelines smooth the anomaly map with `scipy.ndimage.gaussian_filter(map, sigma=4)` before AUROC / PRO and report an image-level
 AUROC of one score per image first.  `gaussian_filter` is that filter on the device (`anoddpm_gauss2d`, csrc/smooth.hip: one launch
@@ -108,7 +115,8 @@ from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs
                    SsimArgs, SurfaceArgs, ThresholdCountsArgs, check, current_stream, lib)
 
 __all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "PooledCurves", "PooledRegionCurves", "ssim", "median_filter", "erode_mask", "keep_mask",
-           "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "aupro", "pro_points", "AUPRO", "distance_transform",
+           "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "median_filter3d", "erode_mask3d", "remove_small_components3d",
+           "component_areas3d", "VolumePostProcess", "postprocess_volumes", "anomaly_metrics_volume", "aupro", "pro_points", "AUPRO", "distance_transform",
            "surface_distance", "HD95", "anomaly_metrics_surface", "gaussian_filter", "image_scores", "image_auc", "anomaly_metrics_image", "order_stats", "counts_at", "scores_at",
            "anomaly_metrics_at", "HealthyPool", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
@@ -1346,6 +1354,264 @@ def anomaly_metrics_at(real, recon, mask, thresholds, postprocess=None, roi=None
         for k in _AT_KEYS + ("tp", "fp"):
             r[k + "_at" + sfx] = o[k][0]
     return r
+
+
+# ---------------------------------------------------------------------------------- volume-wise post-processing (csrc/postproc3d.hip)
+def _volumes(x, batched, what, name):
+    """Shape bookkeeping of [..., D, H, W]: (V, D, H, W), every dimension before the last three a stack of independent volumes.  A
+    3-D tensor is one volume; `batched=True` asks for at least one leading dimension."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a device tensor")
+    if x.dim() < 3 or (batched and x.dim() < 4):
+        raise ValueError(f"{what}: a volume is [..., D, H, W], got {name} of shape {tuple(x.shape)}" + (" as a batch" if batched else ""))
+    if x.numel() == 0:
+        raise ValueError(f"{what}: empty {name} {tuple(x.shape)}")
+    D, H, W = x.shape[-3:]
+    return x.numel() // (D * H * W), D, H, W
+
+
+def median_filter3d(score, size=5, roi=None, batched=None, return_status=False):
+    """`scipy.ndimage.median_filter(vol, size=size)` (reflect border on all three axes) of every D x H x W volume of score:
+    [..., D, H, W] -- a 3-D tensor is one volume, four or more dimensions a batch of volumes (`batched=False`: the leading
+    dimensions are still a stack of independent volumes; `batched=True` refuses a 3-D tensor).  size 3 or 5, at most min(H, W);
+    any D >= 1 (the border is reflected as often as the window asks).  `roi`: a 0 / 1 tensor shaped like one plane (shared by
+    every slice), one volume (shared by the batch) or score; the result is +0.0 where it is 0 (the filter itself sees the
+    unmasked volume).  Returns a device tensor shaped like score, bit for bit scipy's, without a host synchronisation.  Scores
+    must be finite and >= 0 as for `median_filter`: a volume that is not gets a non-zero status word (`return_status=True` also
+    returns them, int32, shaped like score without its last three dimensions) and an unspecified result."""
+    V, D, H, W = _volumes(score, batched, "median_filter3d", "score")
+    if size not in _lib.MEDIAN3D_SIZES:
+        raise ValueError(f"median_filter3d: size must be one of {_lib.MEDIAN3D_SIZES}, got {size!r}")
+    if min(H, W) < size:
+        raise ValueError(f"median_filter3d: window of {size} exceeds the {H} x {W} slices")
+    sc, _, s_stride = _segments(score, V, "median_filter3d(score)")
+    dev = sc.device
+    a = _lib.Median3dArgs()
+    if roi is not None:
+        if not isinstance(roi, torch.Tensor):
+            raise TypeError("median_filter3d: roi must be a device tensor")
+        if roi.numel() == H * W:
+            a.roi_slice_stride, a.roi_stride = 0, 0
+        elif roi.numel() == D * H * W:
+            a.roi_slice_stride, a.roi_stride = H * W, 0
+        elif roi.numel() == V * D * H * W:
+            a.roi_slice_stride, a.roi_stride = H * W, D * H * W
+        else:
+            raise ValueError(f"median_filter3d: roi {tuple(roi.shape)} is neither a plane, a volume nor the shape of score {tuple(score.shape)}")
+        rt = _f32c(roi, "median_filter3d(roi)")
+        if rt.device != dev:
+            raise ValueError("median_filter3d: roi and score are on different devices")
+        a.roi = rt.data_ptr()
+    out = torch.empty(tuple(score.shape), dtype=torch.float32, device=dev)
+    status = torch.empty(tuple(score.shape[:-3]), dtype=torch.int32, device=dev)
+    a.src, a.dst, a.status, a.src_stride = sc.data_ptr(), out.data_ptr(), status.data_ptr(), s_stride
+    a.S, a.D, a.H, a.W, a.k = V, D, H, W, int(size)
+    _launch("median3d", a, dev)
+    return (out, status) if return_status else out
+
+
+def erode_mask3d(x, iterations=3, level=0.0):
+    """`scipy.ndimage.binary_erosion(vol > level, iterations=iterations)` (the 6-neighbour cross, zero outside the volume) of
+    every D x H x W volume of x ([..., D, H, W]); 1 ... 8 iterations.  Returns an fp32 0 / 1 device tensor shaped like x, no host
+    synchronisation.  With the default level a 0 / 1 mask is eroded; with `level` a volume is thresholded and eroded at once."""
+    V, D, H, W = _volumes(x, None, "erode_mask3d", "x")
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= iterations <= _lib.ERODE_MAX:
+        raise ValueError(f"erode_mask3d: iterations must be in 1 ... {_lib.ERODE_MAX}, got {iterations!r}")
+    xt, _, stride = _segments(x, V, "erode_mask3d(x)")
+    out = torch.empty(tuple(x.shape), dtype=torch.float32, device=xt.device)
+    a = _lib.Erode3dArgs()
+    a.src, a.dst, a.src_stride = xt.data_ptr(), out.data_ptr(), stride
+    a.S, a.D, a.H, a.W, a.n, a.level = V, D, H, W, int(iterations), float(level)
+    _launch("erode3d", a, xt.device)
+    return out
+
+
+def _check_connectivity3d(connectivity, what):
+    if connectivity not in (1, 2, 3):
+        raise ValueError(f"{what}: connectivity must be 1 (6 neighbours), 2 (18) or 3 (26), got {connectivity!r}")
+
+
+def _small_components3d(x, level, min_size, connectivity):
+    """One `anoddpm_small_components3d` run on the volumes of x > level: (fp32 0 / 1 map shaped like x, int64 counts [..., 2])."""
+    V, D, H, W = _volumes(x, None, "remove_small_components3d", "pred")
+    if isinstance(min_size, bool) or int(min_size) != min_size or min_size < 0:
+        raise ValueError(f"remove_small_components3d: min_size must be an integer >= 0, got {min_size!r}")
+    _check_connectivity3d(connectivity, "remove_small_components3d")
+    xt, _, stride = _segments(x, V, "remove_small_components3d(pred)")
+    dev = xt.device
+    out = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)
+    counts = torch.empty(tuple(x.shape[:-3]) + (2,), dtype=torch.int64, device=dev)
+    a = _lib.Components3dArgs()
+    a.src, a.dst, a.counts = xt.data_ptr(), out.data_ptr(), counts.data_ptr()
+    a.src_stride, a.S, a.D, a.H, a.W = stride, V, D, H, W
+    a.min_size, a.connectivity, a.level = int(min_size), int(connectivity), float(level)
+    _launch("small_components3d", a, dev, (lib().anoddpm_components3d_workspace_bytes(V, D, H, W), torch.int32,
+                                           f"remove_small_components3d: {tuple(x.shape)} has 2^31 voxels or more"))
+    return out, counts
+
+
+def remove_small_components3d(pred, min_size=7, connectivity=1, return_counts=False):
+    """The binary prediction `pred` ([..., D, H, W], fp32 0 / 1) without its connected components of fewer than `min_size`
+    voxels: `lab, _ = scipy.ndimage.label(vol, generate_binary_structure(3, connectivity)); keep =
+    numpy.bincount(lab.ravel()) >= min_size; keep[0] = False; keep[lab]` per volume.  connectivity 1: 6 neighbours (label's
+    default), 2: 18, 3: 26.  Returns an fp32 0 / 1 device tensor shaped like pred, with `return_counts=True` also int64
+    `[..., 2]`: components found and components kept per volume.  No host synchronisation; the same bits every run."""
+    out, counts = _small_components3d(pred, 0.0, min_size, connectivity)
+    return (out, counts) if return_counts else out
+
+
+def component_areas3d(mask, connectivity=3, level=0.0, batched=None):
+    """The size of every voxel's connected component of `vol > level`, per D x H x W volume of mask ([..., D, H, W]; batching as
+    `median_filter3d`): `lab, m = scipy.ndimage.label(vol > level, generate_binary_structure(3, connectivity));
+    numpy.bincount(lab.ravel())[lab]` with 0 on the background.  connectivity 3: 26 neighbours (the 3-D counterpart of the PRO
+    score's 8), 2: 18, 1: 6.  Returns `(areas, counts)`: int32 shaped like mask and int64 shaped like mask without its last three
+    dimensions (the `m` of every volume), device tensors, no host synchronisation, the same bits every run."""
+    V, D, H, W = _volumes(mask, batched, "component_areas3d", "mask")
+    _check_connectivity3d(connectivity, "component_areas3d")
+    xt, _, stride = _segments(mask, V, "component_areas3d(mask)")
+    dev = xt.device
+    areas = torch.empty(tuple(mask.shape), dtype=torch.int32, device=dev)
+    counts = torch.empty(tuple(mask.shape[:-3]), dtype=torch.int64, device=dev)
+    a = _lib.ComponentAreas3dArgs()
+    a.src, a.area, a.counts = xt.data_ptr(), areas.data_ptr(), counts.data_ptr()
+    a.src_stride, a.S, a.D, a.H, a.W = stride, V, D, H, W
+    a.connectivity, a.level = int(connectivity), float(level)
+    _launch("component_areas3d", a, dev, (lib().anoddpm_components3d_workspace_bytes(V, D, H, W), torch.int32,
+                                          f"component_areas3d: {tuple(mask.shape)} has 2^31 voxels or more"))
+    return areas, counts
+
+
+class VolumePostProcess:
+    """Settings of the volume-wise post-processing between the squared error of a volume and its scores; immutable, hashable,
+    picklable.  `median`: window of the 3-D median filter (3, 5; None: off).  `erode`: 3-D erosions of the region of interest
+    (0 ... 8; 0: used as it is).  `roi_level`: when not None the region of interest is `real > roi_level` unless the caller hands
+    one in.  `min_size` / `connectivity` (1, 2, 3: 6 / 18 / 26 neighbours): 3-D components of the thresholded volume below that
+    many voxels are dropped (0: off).  The defaults are `PostProcess`'s."""
+    __slots__ = ("median", "erode", "roi_level", "min_size", "connectivity")
+
+    def __init__(self, median=5, erode=3, roi_level=None, min_size=7, connectivity=1):
+        if median is not None and median not in _lib.MEDIAN3D_SIZES:
+            raise ValueError(f"VolumePostProcess: median must be None or one of {_lib.MEDIAN3D_SIZES}, got {median!r}")
+        if isinstance(erode, bool) or int(erode) != erode or not 0 <= erode <= _lib.ERODE_MAX:
+            raise ValueError(f"VolumePostProcess: erode must be in 0 ... {_lib.ERODE_MAX}, got {erode!r}")
+        if isinstance(min_size, bool) or int(min_size) != min_size or min_size < 0:
+            raise ValueError(f"VolumePostProcess: min_size must be an integer >= 0, got {min_size!r}")
+        if connectivity not in (1, 2, 3):
+            raise ValueError(f"VolumePostProcess: connectivity must be 1, 2 or 3, got {connectivity!r}")
+        for k, v in (("median", median), ("erode", int(erode)), ("roi_level", None if roi_level is None else float(roi_level)),
+                     ("min_size", int(min_size)), ("connectivity", int(connectivity))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("VolumePostProcess is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("VolumePostProcess is immutable")
+
+    def _key(self):
+        return tuple(getattr(self, k) for k in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, VolumePostProcess) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "VolumePostProcess(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+    def __reduce__(self):
+        return VolumePostProcess, self._key()
+
+
+def postprocess_volumes(sqerr, pp, real=None, roi=None):
+    """The squared-error volumes `sqerr` ([..., D, H, W]; batching as `median_filter3d`) after `pp`'s 3-D median filter inside the
+    region of interest.  The region is `roi` (a 0 / 1 tensor) when given, else `real > pp.roi_level` when `pp.roi_level` is set,
+    else everything; it has the shape of one plane (the same column through every slice), one volume (shared by the batch) or sqerr,
+    and is thresholded and eroded `pp.erode` times in 3-D in ONE launch -- with nothing outside the volume, so the erosion also
+    takes `pp.erode` slices off either end of the column.  ONE median launch then applies it.  Returns a
+    device tensor shaped like sqerr, no host synchronisation.  With `pp.median` None the region is applied by an elementwise
+    product."""
+    if not isinstance(pp, VolumePostProcess):
+        raise TypeError("postprocess_volumes: pp must be a VolumePostProcess")
+    V, D, H, W = _volumes(sqerr, None, "postprocess_volumes", "sqerr")
+    level = 0.0
+    if roi is None and pp.roi_level is not None:
+        if real is None:
+            raise ValueError("postprocess_volumes: VolumePostProcess.roi_level needs the real volume")
+        roi, level = real, pp.roi_level
+    if roi is not None:
+        if not isinstance(roi, torch.Tensor):
+            raise TypeError("postprocess_volumes: roi must be a device tensor")
+        if roi.numel() not in (H * W, D * H * W, V * D * H * W):
+            raise ValueError(f"postprocess_volumes: roi {tuple(roi.shape)} does not match sqerr {tuple(sqerr.shape)}")
+        if not pp.erode:
+            roi = (_f32c(roi, "postprocess_volumes(roi)") > level).float()
+        else:                                                        # one plane: the same column through every slice, eroded as that volume
+            roi = erode_mask3d(roi.reshape(1, H, W).expand(D, H, W) if roi.numel() == H * W else roi.reshape((-1, D, H, W)), pp.erode, level)
+    if pp.median is not None:
+        return median_filter3d(sqerr, pp.median, roi=roi)
+    out = _f32c(sqerr, "postprocess_volumes(sqerr)")
+    if roi is None:
+        return out.clone()
+    shape = (1, 1, H, W) if roi.numel() == H * W else ((1, D, H, W) if roi.numel() == D * H * W else (V, D, H, W))
+    return (out.reshape(V, D, H, W) * roi.reshape(shape)).reshape(out.shape)
+
+
+_VOLUME_KEYS = (("dice", "dice"), ("precision", "precision"), ("recall", "recall"), ("FPR", "fpr"), ("AUC", "auc"), ("AP", "ap"),
+                ("best_dice", "best_dice"), ("best_threshold", "best_threshold"), ("AUC_status", "status"))
+
+
+def anomaly_metrics_volume(real, recon, mask, threshold=0.5, postprocess=None, roi=None):
+    """The scores of whole volumes: real, recon and mask `[D, H, W]` (one volume; returns one record) or `[V, D, H, W]` (returns a
+    list of V records).  Nothing of a volume is averaged over its slices: per volume, the squared error `(recon - real)^2` of the
+    fused `anomaly_maps` pass is ONE segment of D * H * W voxels, and a record holds
+      `dice`, `precision`, `recall`, `FPR`       of the prediction `sqerr > threshold` (`scores_at`: 2 tp / (tp + fp + P), tp / (tp + fp),
+                                                 tp / P, fp / N; NaN for an empty class)
+      `AUC`, `AP`, `best_dice`, `best_threshold` of `curve_scores` over the volume (the chip-wide sort from 65 536 voxels on), and
+      `AUC_status`, the status word of that launch
+    as Python numbers from one copy to the host, and `maps`: `sqerr` and `pred` of the volume as device tensors [D, H, W].
+    `postprocess` (a `VolumePostProcess`; `roi`: see `postprocess_volumes`) ADDS the `_pp` twin of every key: the curve scores of
+    `maps["sqerr_pp"]` (`postprocess_volumes`) and the scores at `threshold` of `maps["pred_pp"]`, the filtered volume cut at
+    `threshold` without its 3-D components below `postprocess.min_size` voxels."""
+    if not all(isinstance(x, torch.Tensor) for x in (real, recon, mask)):
+        raise TypeError("anomaly_metrics_volume: real, recon and mask must be device tensors")
+    if postprocess is not None and not isinstance(postprocess, VolumePostProcess):
+        raise TypeError("anomaly_metrics_volume: postprocess must be a VolumePostProcess")
+    if real.dim() not in (3, 4) or real.numel() == 0:
+        raise ValueError(f"anomaly_metrics_volume: real must be [D, H, W] or [V, D, H, W], got shape {tuple(real.shape)}")
+    if recon.shape != real.shape or mask.shape != real.shape:
+        raise ValueError(f"anomaly_metrics_volume: recon {tuple(recon.shape)} and mask {tuple(mask.shape)} must have real's shape {tuple(real.shape)}")
+    single = real.dim() == 3
+    D, H, W = real.shape[-3:]
+    V = 1 if single else real.shape[0]
+    rl, mk = real.reshape(V, D, H, W), _f32c(mask, "anomaly_metrics_volume(mask)").reshape(V, D, H, W)
+    maps = anomaly_maps(rl, recon.reshape(V, D, H, W), mk, threshold, want=("sqerr", "pred"))[0]
+    stacks = [("", maps["sqerr"], maps["sqerr"], float(threshold))]
+    if postprocess is not None:
+        maps["sqerr_pp"] = postprocess_volumes(maps["sqerr"], postprocess, real=rl, roi=roi)
+        maps["pred_pp"] = _small_components3d(maps["sqerr_pp"], float(threshold), postprocess.min_size, postprocess.connectivity)[0]
+        stacks.append(("_pp", maps["sqerr_pp"], maps["pred_pp"], 0.5))                    # a 0 / 1 volume cut at 0.5 is itself
+    dev = {}
+    for sfx, sq, cut, thr in stacks:
+        at = scores_at(mk.reshape(V, -1), cut.reshape(V, -1), torch.full((1,), thr, dtype=torch.float32, device=sq.device), batched=True)
+        for v in range(V):                                           # one segment per launch: a volume goes to the chip-wide sort
+            o = curve_scores(mk[v].reshape(-1), sq[v].reshape(-1), batched=False)
+            dev.update({f"{k}{sfx}/{v}": o[src] for k, src in _VOLUME_KEYS if src in o})
+            dev.update({f"{k}{sfx}/{v}": at[src][v] for k, src in _VOLUME_KEYS if src not in o})
+    h = _to_host(dev)
+    records = []
+    for v in range(V):
+        r = {}
+        for sfx, _, _, _ in stacks:
+            for k, _ in _VOLUME_KEYS:
+                x = float(h[f"{k}{sfx}/{v}"].reshape(-1)[0])
+                r[k + sfx] = int(x) if k == "AUC_status" else x
+            if r["best_dice" + sfx] != r["best_dice" + sfx]:
+                r["best_threshold" + sfx] = NAN                      # no positive: no threshold is better than another
+        r["maps"] = {k: m[v] for k, m in maps.items()}
+        records.append(r)
+    return records[0] if single else records
 
 
 # ---------------------------------------------------------------------------------- evaluation.py surface

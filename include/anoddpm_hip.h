@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 40
+#define ANODDPM_ABI_VERSION 41
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -948,6 +948,85 @@ int anoddpm_median2d(const anoddpm_median_args *a, void *stream);
 int anoddpm_erode2d(const anoddpm_erode_args *a, void *stream);
 int anoddpm_small_components(const anoddpm_components_args *a, void *stream);
 int64_t anoddpm_small_components_workspace_bytes(int32_t S, int32_t H, int32_t W);  /* HOST function; -1 for an extent < 1 or S*H*W >= 2^31 */
+
+/* ------------------------------------------------------------------ volume-wise post-processing of anomaly maps
+ * The same three steps on whole volumes, as the published brain-MRI protocols that report one Dice per volume apply them: the
+ * residual volume is median-filtered, the brain mask eroded and small components dropped in 3-D.  The results are NOT those of
+ * the plane-wise entry points above applied slice by slice.  All three select or count: every output equals scipy's bit for bit.
+ * S volumes of D x H x W fp32, volume v at src + v * src_stride (src_stride >= D*H*W), slices and rows contiguous; outputs are
+ * contiguous [S][D][H][W].  D >= 1: a single slice is a volume.
+ *
+ * anoddpm_median3d replaces scipy.ndimage.median_filter(vol, size=k) (mode="reflect" on all three axes), k in {3, 5},
+ *   min(H, W) >= k as for anoddpm_median2d; along depth any D >= 1 is taken and the index is reflected as often as needed
+ *   (period 2 D: ... b a | a b ... | ... b a | a b ..., what numpy.pad(mode="symmetric") does for a pad wider than the axis).
+ *   dst = the (k*k*k / 2)-th smallest of the k*k*k values of the window, selected on the 31-bit pattern exactly as
+ *   anoddpm_median2d selects (-0.0 is reported as +0.0).  Precondition and status bits as there, one status word per VOLUME.
+ *   roi     optional fp32 0 / 1, voxel (v, z, y, x) at roi + v * roi_stride + z * roi_slice_stride + y * W + x:
+ *           roi_slice_stride 0 and roi_stride 0: one plane for every slice of every volume; roi_slice_stride H*W and roi_stride
+ *           0: one volume shared by the batch; roi_slice_stride H*W and roi_stride >= D*H*W: one per volume.  dst is +0.0 where
+ *           the ROI is 0 (the filter itself sees the unmasked volume); a value other than 0 / 1 sets ANODDPM_ROC_BAD_MASK.
+ *   One launch (after an asynchronous clear of status): a workgroup stages a 4 x 8 x 32 tile and its k/2 halo in LDS once; a
+ *   thread walks the tile's four slices of one (y, x), keeps the k*k*k patterns in registers and replaces one k*k plane of them
+ *   per step.  The grid is tiles x volumes, below 2^31 workgroups.
+ *
+ * anoddpm_erode3d replaces scipy.ndimage.binary_erosion(vol > level, iterations=n) with scipy's defaults (the 6-neighbour cross,
+ *   border_value=0), 1 <= n <= 8: one AND over the L1 ball (octahedron) of radius n with everything outside the volume counting
+ *   as 0.  dst is fp32 0 / 1.  NaN is not above any level.  One launch.
+ *
+ * anoddpm_small_components3d replaces  lab, m = scipy.ndimage.label(vol > level, scipy.ndimage.generate_binary_structure(3, c));
+ *   sizes = numpy.bincount(lab.ravel());  (sizes >= min_size)[lab]  (with label 0 cleared): dst is fp32 0 / 1.  connectivity
+ *   c = 1: 6 neighbours (label's default), 2: 18, 3: 26.  counts[v] = {components found, components kept} per volume.
+ * anoddpm_component_areas3d: area = numpy.bincount(lab.ravel())[lab], 0 where lab == 0; counts[v] = m.
+ *   Both are the five launches of anoddpm_small_components / anoddpm_component_areas with a link launch that visits the 3 / 9 /
+ *   13 forward neighbours; components never link across volumes.
+ *   workspace  [dev] anoddpm_components3d_workspace_bytes(S, D, H, W) bytes = 8 per voxel; S * D * H * W must be below 2^31
+ * No allocation and no host synchronisation in any of them: capturable in a hipGraph. */
+typedef struct anoddpm_median3d_args {
+    const float *src;               /* [dev] */
+    const float *roi;               /* [dev] or NULL */
+    float *dst;                     /* [dev] [S][D][H][W] */
+    int32_t *status;                /* [dev] [S] */
+    int64_t src_stride, roi_stride, roi_slice_stride;
+    int32_t S, D, H, W, k;
+} anoddpm_median3d_args;
+
+typedef struct anoddpm_erode3d_args {
+    const float *src;               /* [dev] */
+    float *dst;                     /* [dev] [S][D][H][W] */
+    int64_t src_stride;
+    int32_t S, D, H, W, n;
+    float level;
+} anoddpm_erode3d_args;
+
+typedef struct anoddpm_components3d_args {
+    const float *src;               /* [dev] */
+    float *dst;                     /* [dev] [S][D][H][W] */
+    int64_t *counts;                /* [dev] [S][2] */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    int64_t src_stride;
+    int32_t S, D, H, W;
+    int32_t min_size, connectivity;
+    float level;
+} anoddpm_components3d_args;
+
+typedef struct anoddpm_component_areas3d_args {
+    const float *src;               /* [dev] */
+    int32_t *area;                  /* [dev] [S][D][H][W] */
+    int64_t *counts;                /* [dev] [S] */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    int64_t src_stride;
+    int32_t S, D, H, W;
+    int32_t connectivity;
+    float level;
+} anoddpm_component_areas3d_args;
+
+int anoddpm_median3d(const anoddpm_median3d_args *a, void *stream);
+int anoddpm_erode3d(const anoddpm_erode3d_args *a, void *stream);
+int anoddpm_small_components3d(const anoddpm_components3d_args *a, void *stream);
+int anoddpm_component_areas3d(const anoddpm_component_areas3d_args *a, void *stream);
+int64_t anoddpm_components3d_workspace_bytes(int32_t S, int32_t D, int32_t H, int32_t W);  /* HOST function; -1 for an extent < 1 or S*D*H*W >= 2^31 */
 
 /* ------------------------------------------------------------------ Gaussian smoothing and image-level scores of anomaly maps
  * The two steps the texture protocol (Bergmann et al., MVTec AD) puts between an anomaly map and its scores; the reference has
