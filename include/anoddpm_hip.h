@@ -611,6 +611,22 @@ typedef struct anoddpm_anomaly_args {
 
 int anoddpm_anomaly_map(const anoddpm_anomaly_args *a, void *stream);
 
+/* ------------------------------------------------------------------ what every metric / post-processing entry point below keeps
+ * anoddpm_roc_auc, anoddpm_pro_auc, anoddpm_component_areas, anoddpm_ssim, anoddpm_distance_transform, anoddpm_surface_distance,
+ * anoddpm_median2d, anoddpm_erode2d, anoddpm_small_components, anoddpm_gauss2d, anoddpm_map_scores, anoddpm_median3d,
+ * anoddpm_erode3d, anoddpm_small_components3d, anoddpm_component_areas3d (tests/contract_cases.py holds the table that
+ * tests/test_gpu_contract.py audits them by):
+ *   memory     a call reads only the elements of its inputs the field comments name (n per segment, the strides between them
+ *              are never touched) and writes only its outputs and its workspace: nothing in front of, between or behind them
+ *   outputs    every element of every output is written by an accepted call, in every defined case (P == 0, K == 0, an empty
+ *              border, a plane without foreground or background, a segment that breaks the precondition), except the curve
+ *              arrays: entries [s][min(curve_len[s], curve_cap) ... curve_cap) are left untouched
+ *   workspace  its contents need no initialisation on entry and are unspecified on exit; the outputs do not depend on them.
+ *              `workspace_bytes` as reported is enough; nothing outside it is touched
+ *   alignment  every pointer is aligned to its element type, and that is all: segments may start at any element (odd strides).
+ *              The workspace is 4-byte aligned, 8-byte for anoddpm_pro_auc and anoddpm_ssim (they keep fp64 values in it)
+ *   refusal    a call that returns an error has launched nothing and written nothing, neither outputs nor workspace */
+
 /* ------------------------------------------------------------------ ROC curve + AUC of anomaly maps
  * Replaces sklearn.metrics.roc_curve / auc as the reference calls them on a flattened mask and squared-error map
  * (evaluation.py:79-87 ROC_AUC / AUC_score; detection.py:230-231 and :553-554, :569-570, :583-584 per test image, :640-643
