@@ -37,6 +37,7 @@ SOURCES = {
     "pro.hip": ["-ffp-contract=off"],
     "pro_wide.hip": ["-ffp-contract=off"],
     "surface.hip": ["-ffp-contract=off"],
+    "surface3d.hip": ["-ffp-contract=off"],
     "ssim.hip": ["-ffp-contract=off"],
     "postproc.hip": [],
     "postproc3d.hip": [],

@@ -30,13 +30,9 @@
 //            distances of both directions, one behind the other, into its share of the g^2 buffer (dead by then), so a select
 //            pass walks the border pixels instead of the plane and the pooled multiset is one array.
 // Four launches whatever the batch; no floating-point atomics; no host synchronisation.  Compiled with -ffp-contract=off.
-#include <math.h>
-#include "common.h"
+#include "surface_shared.h"                                          // the column sweep, the row search, the selects, the trees
 
 namespace {
-
-constexpr int THREADS = 256, STAT_THREADS = 1024, STAT_WAVES = STAT_THREADS / 64, ROW_LDS = 4096, CHUNK = 8;
-constexpr uint32_t FAR = 0x7fffffffu;                                // "no zero in reach"; every real squared distance is below it
 
 // ---------------------------------------------------------------------------------------------------- border
 __global__ __launch_bounds__(THREADS) void border_kernel(anoddpm_surface_args a, int shared_ref, uint32_t *__restrict__ g2, int bpp)
@@ -56,91 +52,7 @@ __global__ __launch_bounds__(THREADS) void border_kernel(anoddpm_surface_args a,
     g2[(int64_t)q * hw + p] = border ? 0u : 1u;
 }
 
-// ---------------------------------------------------------------------------------------------------- column sweeps
-// src != nullptr: the zero set is !(src > level) (NaN is not above any level); else the zeros already stored in g2.
-__global__ __launch_bounds__(THREADS) void column_kernel(const float *__restrict__ src, int64_t src_stride, float level,
-                                                         uint32_t *g2, int planes, int H, int W)
-{
-    const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
-    if (i >= (int64_t)planes * W) return;
-    const int q = (int)(i / W), x = (int)(i - (int64_t)q * W);
-    uint32_t *col = g2 + (int64_t)q * H * W + x;
-    const float *in = src ? src + (int64_t)q * src_stride + x : nullptr;
-    uint32_t d = FAR;
-    for (int y0 = 0; y0 < H; y0 += CHUNK) {
-        bool zero[CHUNK];
-#pragma unroll
-        for (int j = 0; j < CHUNK; ++j) {
-            const int y = y0 + j;
-            zero[j] = y < H && (in ? !(in[(int64_t)y * W] > level) : col[(int64_t)y * W] == 0u);
-        }
-#pragma unroll
-        for (int j = 0; j < CHUNK; ++j) {
-            const int y = y0 + j;
-            if (y < H) {
-                d = zero[j] ? 0u : (d == FAR ? FAR : d + 1u);
-                col[(int64_t)y * W] = d;
-            }
-        }
-    }
-    d = FAR;
-    for (int y0 = H - 1; y0 >= 0; y0 -= CHUNK) {
-        uint32_t t[CHUNK];
-#pragma unroll
-        for (int j = 0; j < CHUNK; ++j) {
-            const int y = y0 - j;
-            t[j] = y >= 0 ? col[(int64_t)y * W] : FAR;
-        }
-#pragma unroll
-        for (int j = 0; j < CHUNK; ++j) {
-            const int y = y0 - j;
-            if (y >= 0) {
-                d = t[j] == 0u ? 0u : (d == FAR ? FAR : d + 1u);
-                const uint32_t m = min(t[j], d);                     // <= H - 1 or FAR
-                col[(int64_t)y * W] = m == FAR ? FAR : m * m;
-            }
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------- row pass
-// min over x' of (x - x')^2 + row[x'], walking outwards from x while k^2 can still win.  k^2 < best <= FAR and row[] <= FAR: the
-// sum stays below 2^32.
-__device__ __forceinline__ uint32_t nearest(const uint32_t *row, int x, int W)
-{
-    uint32_t best = row[x];
-    for (int k = 1; (uint32_t)k * (uint32_t)k < best; ++k) {         // k <= W <= 46341: k^2 fits 32 bits unsigned
-        const int l = x - k, r = x + k;
-        if (l < 0 && r >= W) break;
-        const uint32_t kk = (uint32_t)k * (uint32_t)k;
-        if (l >= 0) best = min(best, kk + row[l]);
-        if (r < W) best = min(best, kk + row[r]);
-    }
-    return best;
-}
-
-// the row of g^2 a workgroup searches: in LDS when it fits
-__device__ __forceinline__ const uint32_t *stage_row(const uint32_t *__restrict__ grow, uint32_t *tile, int W)
-{
-    if (W > ROW_LDS) return grow;                                    // block-uniform
-    for (int x = threadIdx.x; x < W; x += THREADS) tile[x] = grow[x];
-    __syncthreads();
-    return tile;
-}
-
-__global__ __launch_bounds__(THREADS) void dt_row_kernel(anoddpm_distance_args a, const uint32_t *__restrict__ g2)
-{
-    __shared__ uint32_t tile[ROW_LDS];
-    const int W = a.W;
-    const int64_t base = (int64_t)blockIdx.x * W;                    // blockIdx.x = plane * H + y; g2 and the outputs are [S][H][W]
-    const uint32_t *row = stage_row(g2 + base, tile, W);
-    for (int x = threadIdx.x; x < W; x += THREADS) {
-        const uint32_t r = nearest(row, x, W);
-        a.sq[base + x] = r >= FAR ? -1 : (int32_t)r;
-        if (a.dist) a.dist[base + x] = r >= FAR ? (double)INFINITY : sqrt((double)r);
-    }
-}
-
 __global__ __launch_bounds__(THREADS) void surface_row_kernel(const uint32_t *__restrict__ g2, int32_t *__restrict__ d2,
                                                               int S, int shared_ref, int H, int W)
 {
@@ -166,52 +78,12 @@ __global__ __launch_bounds__(THREADS) void surface_row_kernel(const uint32_t *__
 }
 
 // ---------------------------------------------------------------------------------------------------- per-pair statistics
-// The value of rank `rank` (0-based, ascending) among the words v[0 ... n), all below 2^31: radix select from the top byte down.
-__device__ uint32_t block_select(const uint32_t *v, uint32_t n, uint32_t rank, uint32_t *hist, uint32_t *sel)
-{
-    const int tid = threadIdx.x;
-    uint32_t prefix = 0, mask = 0;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        for (int i = tid; i < 256; i += STAT_THREADS) hist[i] = 0;
-        __syncthreads();
-        for (uint32_t i = tid; i < n; i += STAT_THREADS) {
-            const uint32_t w = v[i];
-            if ((w & mask) == prefix) atomicAdd(&hist[(w >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t b = 0, r = rank;
-            while (b < 255u && r >= hist[b]) { r -= hist[b]; ++b; }
-            sel[0] = b;
-            sel[1] = r;
-        }
-        __syncthreads();
-        prefix |= sel[0] << shift;
-        rank = sel[1];
-        mask |= 255u << shift;
-        __syncthreads();
-    }
-    return prefix;
-}
-
-// the percentile of include/anoddpm_hip.h over the n squared distances v[0 ... n)
-__device__ double percentile95(const uint32_t *v, uint32_t n, uint32_t *hist, uint32_t *sel)
-{
-    const unsigned long long k = 19ull * (n - 1u);
-    const uint32_t lo = (uint32_t)(k / 20ull), r = (uint32_t)(k % 20ull), hi = min(lo + 1u, n - 1u);
-    const uint32_t va = block_select(v, n, lo, hist, sel);
-    const uint32_t vb = hi == lo ? va : block_select(v, n, hi, hist, sel);
-    const double a = sqrt((double)va), b = sqrt((double)vb);
-    return a + (b - a) * ((double)r / 20.0);
-}
-
 __global__ __launch_bounds__(STAT_THREADS) void surface_stats_kernel(anoddpm_surface_args a, const int32_t *__restrict__ d2, uint32_t *g2)
 {
-    __shared__ uint32_t hist[256], sel[2], wcnt[2][STAT_WAVES], s_n[2], s_fill[2];
-    __shared__ int32_t wmax[2][STAT_WAVES];
-    __shared__ double wsum[2][STAT_WAVES];
+    __shared__ uint32_t hist[256], sel[2], s_n[2], s_fill[2];
+    __shared__ PairFold fold;
 
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const uint32_t hw = (uint32_t)(a.H * a.W);
     const int32_t *__restrict__ v = d2 + (int64_t)s * 2 * hw;       // direction 0, then direction 1
 
@@ -230,43 +102,8 @@ __global__ __launch_bounds__(STAT_THREADS) void surface_stats_kernel(anoddpm_sur
             }
         }
     }
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            cnt[d] += __shfl_xor(cnt[d], off);
-            mx[d] = max(mx[d], __shfl_xor(mx[d], off));
-            sum[d] += __shfl_xor(sum[d], off);
-        }
-        if (lane == 0) { wcnt[d][wave] = cnt[d]; wmax[d][wave] = mx[d]; wsum[d][wave] = sum[d]; }
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            cnt[d] = lane < STAT_WAVES ? wcnt[d][lane] : 0u;
-            mx[d] = lane < STAT_WAVES ? wmax[d][lane] : -1;
-            sum[d] = lane < STAT_WAVES ? wsum[d][lane] : 0.0;
-#pragma unroll
-            for (int off = STAT_WAVES / 2; off > 0; off >>= 1) {
-                cnt[d] += __shfl_xor(cnt[d], off);
-                mx[d] = max(mx[d], __shfl_xor(mx[d], off));
-                sum[d] += __shfl_xor(sum[d], off);
-            }
-        }
-        if (lane == 0) {
-            const int st = (cnt[0] == 0 ? ANODDPM_SURFACE_EMPTY_PRED : 0) | (cnt[1] == 0 ? ANODDPM_SURFACE_EMPTY_REF : 0);
-            a.status[s] = st;
-#pragma unroll
-            for (int d = 0; d < 2; ++d) {
-                a.counts[(int64_t)s * 2 + d] = (int32_t)cnt[d];
-                a.max2[(int64_t)s * 2 + d] = st ? -1 : mx[d];
-                a.mean[(int64_t)s * 2 + d] = st ? (double)NAN : sum[d] / (double)cnt[d];
-                s_n[d] = st ? 0u : cnt[d];
-            }
-            if (st) a.p95[(int64_t)s * 3] = a.p95[(int64_t)s * 3 + 1] = a.p95[(int64_t)s * 3 + 2] = (double)NAN;
-        }
-    }
+    fold_pair(cnt, mx, sum, fold);
+    if (tid == 0) finish_pair(s, cnt, mx, sum, a.counts, a.max2, a.mean, a.p95, a.status, s_n);
     __syncthreads();
     const uint32_t n0 = s_n[0], n1 = s_n[1];
     if (n0 == 0) return;                                             // block-uniform: an empty border on either side
@@ -290,14 +127,7 @@ __global__ __launch_bounds__(STAT_THREADS) void surface_stats_kernel(anoddpm_sur
         }
     }
     __syncthreads();
-    const double p0 = percentile95(packed, n0, hist, sel);
-    const double p1 = percentile95(packed + n0, n1, hist, sel);
-    const double pp = percentile95(packed, n0 + n1, hist, sel);
-    if (tid == 0) {
-        a.p95[(int64_t)s * 3] = p0;
-        a.p95[(int64_t)s * 3 + 1] = p1;
-        a.p95[(int64_t)s * 3 + 2] = pp;
-    }
+    write_percentiles(packed, n0, n1, a.p95 + (int64_t)s * 3, hist, sel);
 }
 
 // S, H, W >= 1, every squared distance below 2^31 and both planes sets of a surface run indexable with 31 bits

@@ -73,6 +73,10 @@ by slice.  `median_filter3d` (windows 3 / 5, reflect border on all three axes, a
 and `remove_small_components3d` / `component_areas3d` (6 / 18 / 26 neighbours) are scipy's results bit for bit on `[..., D, H, W]`
 tensors; `VolumePostProcess` holds the settings, `postprocess_volumes` applies them and `anomaly_metrics_volume` scores every
 volume as ONE segment.  Nothing above changes when they are not called.
+Boundary distances of whole volumes (csrc/surface3d.hip), in voxel units: `distance_transform3d` is scipy's
+`distance_transform_edt` of a volume bit for bit, `surface_distance3d` gives one `hd` / `hd95` / `assd` per volume (6-neighbour
+border; not the planes' numbers averaged), `HD95_volume` a float, and `anomaly_metrics_volume_surface` is `anomaly_metrics_volume`
+with `HD`, `HD95`, `ASSD`, `surface_status` added to every record.
 
 Texture protocol (Bergmann et al.; the reference evaluates DAGM carpet and MVTec leather with the brain-MRI code path).  Published
 pipelines smooth the anomaly map with `scipy.ndimage.gaussian_filter(map, sigma=4)` before AUROC / PRO and report an image-level
@@ -116,7 +120,7 @@ from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs
 
 __all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "PooledCurves", "PooledRegionCurves", "ssim", "median_filter", "erode_mask", "keep_mask",
            "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "median_filter3d", "erode_mask3d", "remove_small_components3d",
-           "component_areas3d", "VolumePostProcess", "postprocess_volumes", "anomaly_metrics_volume", "aupro", "pro_points", "AUPRO", "distance_transform",
+           "component_areas3d", "VolumePostProcess", "postprocess_volumes", "anomaly_metrics_volume", "anomaly_metrics_volume_surface", "distance_transform3d", "surface_distance3d", "HD95_volume", "aupro", "pro_points", "AUPRO", "distance_transform",
            "surface_distance", "HD95", "anomaly_metrics_surface", "gaussian_filter", "image_scores", "image_auc", "anomaly_metrics_image", "order_stats", "counts_at", "scores_at",
            "anomaly_metrics_at", "HealthyPool", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
@@ -1481,6 +1485,77 @@ def component_areas3d(mask, connectivity=3, level=0.0, batched=None):
     return areas, counts
 
 
+# ---------------------------------------------------------------------------------- distances on whole volumes (csrc/surface3d.hip)
+def _surface3d_workspace(S, D, H, W, what, transform=False):
+    """`_launch`'s workspace of the two entry points of csrc/surface3d.hip: what `anoddpm_surface3d_workspace_bytes` answers, or
+    the transform's stated share of it (8 * S * D * H * W bytes: half of its voxel part)."""
+    nbytes = lib().anoddpm_surface3d_workspace_bytes(S, D, H, W)
+    return (8 * S * D * H * W if transform and nbytes >= 0 else nbytes, torch.int32,
+            f"{what}: {S} volumes of {D} x {H} x {W} are too large: (D-1)^2 + (H-1)^2 + (W-1)^2, D*H*W and 2 * volumes * D*H must stay below 2^31")
+
+
+def distance_transform3d(x, level=0.0, squared=False, batched=None):
+    """`scipy.ndimage.distance_transform_edt(vol > level)` of every D x H x W volume of x ([..., D, H, W]; a 3-D tensor is one
+    volume, `batched=True` refuses it; NaN is background), in voxels: an fp64 device tensor shaped like x, bit for bit scipy's
+    wherever the volume has a background voxel, without a host synchronisation.  `squared=True`: the exact int32 squared distance
+    instead.  A volume without a background voxel has no defined answer: +inf (squared: -1) everywhere in it."""
+    V, D, H, W = _volumes(x, batched, "distance_transform3d", "x")
+    xt = _f32c(x, "distance_transform3d(x)")
+    dev = xt.device
+    sq = torch.empty(tuple(x.shape), dtype=torch.int32, device=dev)
+    dist = None if squared else torch.empty(tuple(x.shape), dtype=torch.float64, device=dev)
+    a = _lib.Distance3dArgs()
+    a.src, a.sq, a.dist = xt.data_ptr(), sq.data_ptr(), (None if squared else dist.data_ptr())
+    a.src_stride, a.S, a.D, a.H, a.W, a.level = D * H * W, V, D, H, W, float(level)
+    _launch("distance_transform3d", a, dev, _surface3d_workspace(V, D, H, W, "distance_transform3d", transform=True))
+    return sq if squared else dist
+
+
+def surface_distance3d(pred, ref, level=0.0, return_status=False):
+    """Boundary distances of every D x H x W volume of pred ([..., D, H, W]) against the volume of ref at the same place, or against
+    ONE `[D, H, W]` reference shared by all (its border is computed once), in voxels.  With `m = vol > level`, the border of m is
+    `m & ~scipy.ndimage.binary_erosion(m)` on the 3-D array (6 face neighbours, everything outside the volume counts as
+    background -- so in a volume of ONE slice every foreground voxel is border; `surface_distance` is the function for planes).
+    Returns the dict of `surface_distance` -- `hd`, `hd95`, `assd`, `p95` [..., 3], `mean` [..., 2], `max2` [..., 2], `counts`
+    [..., 2], `status` -- as device tensors shaped like pred without its last three dimensions, no host synchronisation (usable
+    inside a captured graph), the same bits every run.  Where the status is non-zero every fp64 value is NaN and `max2` is -1.
+    `return_status=True` returns `(dict, status)`."""
+    V, D, H, W = _volumes(pred, None, "surface_distance3d", "pred")
+    if not isinstance(ref, torch.Tensor):
+        raise TypeError("surface_distance3d: ref must be a device tensor")
+    if tuple(ref.shape) != tuple(pred.shape) and tuple(ref.shape) != (D, H, W):
+        raise ValueError(f"surface_distance3d: ref {tuple(ref.shape)} is neither the shape of pred {tuple(pred.shape)} nor one [D, H, W] volume")
+    pt = _f32c(pred, "surface_distance3d(pred)")
+    rt = _f32c(ref, "surface_distance3d(ref)")
+    if rt.device != pt.device:
+        raise ValueError("surface_distance3d: pred and ref are on different devices")
+    dev = pt.device
+    lead = tuple(pred.shape[:-3])
+    out = {"counts": torch.empty(lead + (2,), dtype=torch.int32, device=dev), "max2": torch.empty(lead + (2,), dtype=torch.int32, device=dev),
+           "mean": torch.empty(lead + (2,), dtype=torch.float64, device=dev), "p95": torch.empty(lead + (3,), dtype=torch.float64, device=dev),
+           "status": torch.empty(lead, dtype=torch.int32, device=dev)}
+    a = _lib.Surface3dArgs()
+    a.pred, a.ref = pt.data_ptr(), rt.data_ptr()
+    for k in ("counts", "max2", "mean", "p95", "status"):
+        setattr(a, k, out[k].data_ptr())
+    n = D * H * W
+    a.pred_stride, a.ref_stride = n, (n if rt.numel() == V * n and V > 1 else 0)
+    a.S, a.D, a.H, a.W, a.level = V, D, H, W, float(level)
+    _launch("surface_distance3d", a, dev, _surface3d_workspace(V, D, H, W, "surface_distance3d"))
+    out["hd"] = torch.sqrt(out["max2"].max(dim=-1).values.double())              # max2 is -1 where the status is set: NaN
+    out["hd95"] = out["p95"][..., 2]
+    out["assd"] = (out["mean"][..., 0] + out["mean"][..., 1]) / 2
+    return (out, out["status"]) if return_status else out
+
+
+def HD95_volume(real_mask, pred_mask):
+    """`HD95` for whole volumes: the 95th-percentile Hausdorff distance (both directions pooled) between the 0 / 1 masks
+    `[..., D, H, W]` in voxels as a Python float, `surface_distance3d(pred_mask, real_mask)["hd95"]`, and for several volumes its
+    mean over the volumes where both borders exist.  NaN when there is no such volume."""
+    o = surface_distance3d(pred_mask, real_mask)
+    return float(_valid_mean(o["hd95"].reshape(-1), o["status"].reshape(-1))[0])
+
+
 class VolumePostProcess:
     """Settings of the volume-wise post-processing between the squared error of a volume and its scores; immutable, hashable,
     picklable.  `median`: window of the 3-D median filter (3, 5; None: off).  `erode`: 3-D erosions of the region of interest
@@ -1560,6 +1635,7 @@ def postprocess_volumes(sqerr, pp, real=None, roi=None):
 
 _VOLUME_KEYS = (("dice", "dice"), ("precision", "precision"), ("recall", "recall"), ("FPR", "fpr"), ("AUC", "auc"), ("AP", "ap"),
                 ("best_dice", "best_dice"), ("best_threshold", "best_threshold"), ("AUC_status", "status"))
+_VOLUME_SURFACE_KEYS = (("HD", "hd"), ("HD95", "hd95"), ("ASSD", "assd"), ("surface_status", "status"))
 
 
 def anomaly_metrics_volume(real, recon, mask, threshold=0.5, postprocess=None, roi=None):
@@ -1573,7 +1649,20 @@ def anomaly_metrics_volume(real, recon, mask, threshold=0.5, postprocess=None, r
     as Python numbers from one copy to the host, and `maps`: `sqerr` and `pred` of the volume as device tensors [D, H, W].
     `postprocess` (a `VolumePostProcess`; `roi`: see `postprocess_volumes`) ADDS the `_pp` twin of every key: the curve scores of
     `maps["sqerr_pp"]` (`postprocess_volumes`) and the scores at `threshold` of `maps["pred_pp"]`, the filtered volume cut at
-    `threshold` without its 3-D components below `postprocess.min_size` voxels."""
+    `threshold` without its 3-D components below `postprocess.min_size` voxels.
+    `anomaly_metrics_volume_surface` is this function with the boundary distances of every volume added."""
+    return _metrics_volume(real, recon, mask, threshold, postprocess, roi, False)
+
+
+def anomaly_metrics_volume_surface(real, recon, mask, threshold=0.5, postprocess=None, roi=None):
+    """`anomaly_metrics_volume` (same arguments, same records, same bits) with `HD`, `HD95`, `ASSD` (voxels; NaN where a border is
+    empty) and `surface_status` ADDED to every record: `surface_distance3d` between `maps["pred"]` and the mask, one launch
+    sequence for all V volumes, and with `postprocess` their `_pp` twins from `maps["pred_pp"]`.  They reach the host in the same
+    single copy as the other scores.  (A function of its own, as `anomaly_metrics_surface` is beside `anomaly_metrics`.)"""
+    return _metrics_volume(real, recon, mask, threshold, postprocess, roi, True)
+
+
+def _metrics_volume(real, recon, mask, threshold, postprocess, roi, surface):
     if not all(isinstance(x, torch.Tensor) for x in (real, recon, mask)):
         raise TypeError("anomaly_metrics_volume: real, recon and mask must be device tensors")
     if postprocess is not None and not isinstance(postprocess, VolumePostProcess):
@@ -1599,14 +1688,18 @@ def anomaly_metrics_volume(real, recon, mask, threshold=0.5, postprocess=None, r
             o = curve_scores(mk[v].reshape(-1), sq[v].reshape(-1), batched=False)
             dev.update({f"{k}{sfx}/{v}": o[src] for k, src in _VOLUME_KEYS if src in o})
             dev.update({f"{k}{sfx}/{v}": at[src][v] for k, src in _VOLUME_KEYS if src not in o})
+        if surface:
+            sd = surface_distance3d(maps["pred" + sfx], mk)
+            dev.update({f"{k}{sfx}/{v}": sd[src][v] for k, src in _VOLUME_SURFACE_KEYS for v in range(V)})
+    keys = _VOLUME_KEYS + (_VOLUME_SURFACE_KEYS if surface else ())
     h = _to_host(dev)
     records = []
     for v in range(V):
         r = {}
         for sfx, _, _, _ in stacks:
-            for k, _ in _VOLUME_KEYS:
+            for k, _ in keys:
                 x = float(h[f"{k}{sfx}/{v}"].reshape(-1)[0])
-                r[k + sfx] = int(x) if k == "AUC_status" else x
+                r[k + sfx] = int(x) if k in ("AUC_status", "surface_status") else x
             if r["best_dice" + sfx] != r["best_dice" + sfx]:
                 r["best_threshold" + sfx] = NAN                      # no positive: no threshold is better than another
         r["maps"] = {k: m[v] for k, m in maps.items()}

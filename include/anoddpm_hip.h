@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 41
+#define ANODDPM_ABI_VERSION 42
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -904,6 +904,82 @@ typedef struct anoddpm_surface_args {
 int anoddpm_distance_transform(const anoddpm_distance_args *a, void *stream);
 int anoddpm_surface_distance(const anoddpm_surface_args *a, void *stream);
 int64_t anoddpm_surface_workspace_bytes(int32_t S, int32_t H, int32_t W);   /* HOST function; -1 when the extents break the conditions above */
+
+/* ------------------------------------------------------------------ distance transform and boundary distances of whole volumes
+ * The two entry points above for D x H x W volumes in VOXEL units: one Hausdorff distance, one HD95 and one ASSD per volume, as
+ * the protocols that report one Dice per volume report them (taking the planes one by one gives another answer: an outline on
+ * slice z is often nearest to the other outline on slice z +- 1).  Every quantity is an integer squared distance or the fp64
+ * square root of one, so what is said above about bits holds unchanged.
+ *
+ * anoddpm_distance_transform3d: S volumes of D x H x W fp32 at src + s * src_stride.  Foreground is value > level (NaN is
+ *   background).
+ *   sq[s][z][y][x]    int32: the squared Euclidean distance from (z, y, x) to the nearest background voxel of the same volume,
+ *                     exact; 0 on the background
+ *   dist[s][z][y][x]  optional fp64: sqrt(sq), correctly rounded.  With at least one background voxel in the volume it equals
+ *                     scipy.ndimage.distance_transform_edt(vol > level) bit for bit (scipy's 3-D output is the square root of the
+ *                     integer minimum)
+ *   A volume without a background voxel gets sq = -1 and dist = +inf everywhere; no other volume of the batch is touched.
+ *   workspace         [dev] 8 * S * D * H * W bytes: two buffers of squared distances, half of the 16 * S * D * H * W bytes that
+ *                     lead anoddpm_surface3d_workspace_bytes(S, D, H, W)
+ *   Three launches: the sweep along z (the column sweep of the plane transform over H * W columns), per (z, 64 columns) the
+ *   minimum over y' of (y - y')^2 + g(z, y', x)^2 into the SECOND buffer (it reads whole y columns, so it never runs in place),
+ *   and per row the minimum over x' as in the plane transform.  Integer adds and minima only.
+ *
+ * anoddpm_surface_distance3d: S pairs of volumes, pred at pred + s * pred_stride and ref at ref + s * ref_stride; ref_stride 0 =
+ *   one reference volume shared by every prediction (its border and its z and y passes are computed once).  With m = vol > level:
+ *     border(m)  the voxels of m with at least one of the 6 FACE neighbours background or outside the volume
+ *                = m & ~scipy.ndimage.binary_erosion(m, iterations=1, border_value=0) on the 3-D array.
+ *                D = 1 IS NOT THE PLANE CASE: both z neighbours lie outside the volume, so every foreground voxel is on the
+ *                border (as scipy answers for a [1, H, W] array); anoddpm_surface_distance is the entry point for planes.
+ *     d_pr       for every voxel of border(pred) the distance to the nearest voxel of border(ref); d_rp the reverse
+ *   counts, max2, mean, p95, status: as anoddpm_surface_distance, with the same status bits and the same percentile (lo and hi
+ *   are selected on the integer squared distances; only the two selected values get a square root).
+ *   mean[s]    the fp64 sum of the square roots divided by the count, in THIS order: the border voxels of one direction are
+ *              ranked by their linear voxel index (z * H + y) * W + x; thread t of 1024 adds sqrt(d^2) of the ranks t, t + 1024,
+ *              ... in that order; the two halving trees of anoddpm_surface_distance fold the 1024 partials.  (The plane kernel
+ *              strides over pixels, this one over ranks: no workgroup walks a whole volume.)
+ *   workspace  [dev] anoddpm_surface3d_workspace_bytes(S, D, H, W) bytes = 16 * S * D * H * W (two buffers of 2 S volumes)
+ *              + 16 * S * D * H (a count and an offset per pair, direction and row) + 8 * S (two totals per pair); 4-byte words
+ *   Seven launches whatever S: border, z sweep, y pass, the x pass (which writes d^2 at the own border voxels and one count per
+ *   row; rows without an own border voxel skip the search), a scan of the counts, a pack of every row's values to its offset in
+ *   voxel order (direction 1 directly behind direction 0: the pooled multiset is one array), and one workgroup per pair over
+ *   the packed list.  Integer atomics only; no allocation, no host synchronisation; the same bits on every launch, whatever
+ *   the workspace held before and wherever a pair sits in a batch.
+ * Both need D, H, W, S >= 1, D * H * W < 2^31, (D - 1)^2 + (H - 1)^2 + (W - 1)^2 < 2^31 (every squared distance fits int32) and
+ * every grid below 2^31 workgroups (S * D * H rows; 2 * S * D * H for the surface call); S > 1 needs strides >= D * H * W
+ * (ref_stride 0 excepted).  Indices are 64-bit.  Refused before anything is launched otherwise.
+ * Still open: spacing in millimetres (the squared distances become rounded fp64 values and the equality with scipy needs a new
+ * argument), 18- / 26-neighbour surfaces, several thresholds per call, and a chip-wide select for borders of many millions of
+ * voxels (one workgroup per pair selects today). */
+typedef struct anoddpm_distance3d_args {
+    const float *src;               /* [dev] */
+    int32_t *sq;                    /* [dev] [S][D][H][W] */
+    double *dist;                   /* [dev] [S][D][H][W] or NULL */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    int64_t src_stride;
+    int32_t S, D, H, W;
+    float level;
+} anoddpm_distance3d_args;
+
+typedef struct anoddpm_surface3d_args {
+    const float *pred;              /* [dev] */
+    const float *ref;               /* [dev] */
+    void *workspace;                /* [dev] */
+    int64_t workspace_bytes;
+    int32_t *counts;                /* [dev] [S][2] */
+    int32_t *max2;                  /* [dev] [S][2] */
+    double *mean;                   /* [dev] [S][2] */
+    double *p95;                    /* [dev] [S][3] */
+    int32_t *status;                /* [dev] [S] */
+    int64_t pred_stride, ref_stride;
+    int32_t S, D, H, W;
+    float level;
+} anoddpm_surface3d_args;
+
+int anoddpm_distance_transform3d(const anoddpm_distance3d_args *a, void *stream);
+int anoddpm_surface_distance3d(const anoddpm_surface3d_args *a, void *stream);
+int64_t anoddpm_surface3d_workspace_bytes(int32_t S, int32_t D, int32_t H, int32_t W);   /* HOST function; -1 where the call would be refused */
 
 /* ------------------------------------------------------------------ post-processing of anomaly maps before they are scored
  * The three steps published brain-MRI anomaly-segmentation pipelines apply between the squared error and AP / Dice (the
