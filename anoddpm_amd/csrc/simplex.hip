@@ -14,6 +14,12 @@
 // with (A,C) = (offset, 0) normally.  Two reference branches build one component as
 // "(d0 - 1 - 3*SQUISH) - 1" (simplex.py:503,506) or "(d0 - 2*SQUISH) - 2" (:737-743); they map
 // to (A,C) = (offset-1, 1) and (0, 2).  Subtracting +0.0 is exact, so one formula serves all.
+//
+// Domain: |coordinate of any octave| <= 2^52 (index / frequency of the last octave, or a coordinate handed to the grid entry
+// points).  Up to there this formulation (lattice floors kept as doubles, their sum formed in fp64) and the reference's (int64
+// floors) are the same function bit for bit, and the tests compare against the C oracle on every launch path
+// (tests/simplex_cases.py, tests/test_gpu_simplex_launch.py).  Beyond 2^52 the two part (at 2^60 they differ) and neither the
+// reference nor the oracle is a yardstick: results there are unspecified and not tested.
 #include "common.h"
 #include "simplex_tables.h"
 
@@ -78,8 +84,10 @@ __device__ __forceinline__ void load_tables(Tables &T, const int16_t *src)
 }
 
 // x / 103 with IEEE rounding from the correctly rounded reciprocal and two FMAs (Markstein): q = x*r, q' = q + (x - 103 q) r.
-// Exact for every normal-range quotient (checked against hardware division on 4e8 samples, incl. random bit patterns) and for
-// +-0 (q = q' = the zero).  A noise value is 0 or a sum of terms attn^4 (g . d) with attn >= 2^-52 and |sum| < 1e4, far inside
+// Exact for every normal-range quotient (checked against hardware division on 4e8 samples, incl. random bit patterns; the emulation
+// with exact rationals in tests/test_simplex_reference.py keeps checking it, on quotients next to rounding midpoints) and for
+// +0.0.  NOT for -0.0, which comes back as +0.0 (the residual fma(-103, -0, -0) is +0): the caller's sum starts at +0.0 and can
+// never become -0.0, so that input does not occur.  A noise value is 0 or a sum of terms attn^4 (g . d) with attn >= 2^-52 and |sum| < 1e4, far inside
 // the range where the residual x - 103 q is exact; NaN / inf / subnormal inputs (coordinates beyond the double range) take the
 // plain division -- one v_cmp_class_f64 instead of two range comparisons.
 __device__ __forceinline__ double div_norm3(double v)

@@ -7,6 +7,7 @@ from the generated header -- and pins it bit for bit to the C oracle (itself pin
 tests/test_oracle_simplex.py) on random points, lattice points and ties.  A wrong permutation of the region table, a wrong vertex
 row or a stale header fails here without a GPU; the kernel itself is checked against the same oracle by tests/test_gpu_simplex.py.
 """
+import math
 import os
 import re
 import subprocess
@@ -137,3 +138,22 @@ def test_table_driven_noise3_equals_the_oracle_bit_for_bit(tables, seed):
     bad = np.nonzero(got.view(np.uint64) != ref.view(np.uint64))[0]
     # +0.0 / -0.0: the kernel's sum starts at +0.0 and can never become -0.0; the oracle agrees (compared as bit patterns)
     assert bad.size == 0, (bad[:5], p[bad[:5]], got[bad[:5]], ref[bad[:5]])
+
+
+@pytest.mark.parametrize("scale", [1e3, 1e6, 2.0 ** 31, 3e10, 1e13, 2.0 ** 52])
+def test_table_driven_noise3_equals_the_oracle_at_large_coordinates(tables, scale):
+    """Up to |coordinate| = 2^52 -- the domain of tests/simplex_cases.py -- the kernel's formulation (floors kept as doubles, their
+    sum formed in fp64) and the oracle's (int64 floors) are the same function: past 2^31 the lattice base of the kernel comes from
+    its non-SAFE conversions, and the oracle stays the yardstick there."""
+    from oracle.simplex_oracle import OracleSimplex, init
+    seed = 12345
+    perm, pgi3 = init(seed)
+    o = OracleSimplex(seed)
+    rng = np.random.RandomState(int(math.log2(scale)))
+    p = rng.uniform(-scale, scale, size=(3000, 3))
+    p[:300] = np.floor(p[:300])                                              # lattice-aligned, as index / power-of-two frequency gives
+    got = _noise3_tables(tables, perm, pgi3, p[:, 0].copy(), p[:, 1].copy(), p[:, 2].copy())
+    ref = np.array([o.noise3(*q) for q in p])
+    bad = np.nonzero(got.view(np.uint64) != ref.view(np.uint64))[0]
+    assert bad.size == 0, (scale, bad.size, p[bad[:5]], got[bad[:5]], ref[bad[:5]])
+    assert (ref != 0).mean() > 0.9
