@@ -43,6 +43,7 @@ SOURCES = {
     "postproc3d.hip": [],
     "keepmask.hip": ["-ffp-contract=off"],
     "smooth.hip": ["-ffp-contract=off"],
+    "gauss3d.hip": ["-ffp-contract=off"],
     "select_wide.hip": ["-ffp-contract=off"],
     "wgrad.hip": [],
     "wgrad43.hip": [],

@@ -213,7 +213,8 @@ extern "C" int anoddpm_prof_list(int32_t *codes, float *ms, int32_t cap)
     X(anoddpm_components_args) X(anoddpm_gauss_args) X(anoddpm_map_scores_args) \
     X(anoddpm_ano_slices_args) X(anoddpm_select_args) X(anoddpm_threshold_counts_args) X(anoddpm_known_args) \
     X(anoddpm_resampling_args) X(anoddpm_keep_mask_args) X(anoddpm_median3d_args) X(anoddpm_erode3d_args) \
-    X(anoddpm_components3d_args) X(anoddpm_component_areas3d_args) X(anoddpm_distance3d_args) X(anoddpm_surface3d_args)
+    X(anoddpm_components3d_args) X(anoddpm_component_areas3d_args) X(anoddpm_distance3d_args) X(anoddpm_surface3d_args) \
+    X(anoddpm_gauss3d_args)
 
 extern "C" int anoddpm_struct_size(const char *name)
 {

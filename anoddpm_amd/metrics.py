@@ -72,7 +72,8 @@ they filter the residual volume, erode the brain mask and drop small components 
 by slice.  `median_filter3d` (windows 3 / 5, reflect border on all three axes, any depth), `erode_mask3d` (the 6-neighbour cross)
 and `remove_small_components3d` / `component_areas3d` (6 / 18 / 26 neighbours) are scipy's results bit for bit on `[..., D, H, W]`
 tensors; `VolumePostProcess` holds the settings, `postprocess_volumes` applies them and `anomaly_metrics_volume` scores every
-volume as ONE segment.  Nothing above changes when they are not called.
+volume as ONE segment.  Nothing above changes when they are not called.  `gaussian_filter3d` (csrc/gauss3d.hip) is
+`scipy.ndimage.gaussian_filter` of a volume with a sigma per axis, bit for bit; `VolumePostProcess(gaussian=)` puts it first.
 Boundary distances of whole volumes (csrc/surface3d.hip), in voxel units: `distance_transform3d` is scipy's
 `distance_transform_edt` of a volume bit for bit, `surface_distance3d` gives one `hd` / `hd95` / `assd` per volume (6-neighbour
 border; not the planes' numbers averaged), `HD95_volume` a float, and `anomaly_metrics_volume_surface` is `anomaly_metrics_volume`
@@ -120,7 +121,7 @@ from ._lib import (AnomalyArgs, ComponentAreasArgs, ComponentsArgs, DistanceArgs
 
 __all__ = ["anomaly_maps", "score_maps", "anomaly_metrics", "anomaly_metrics_pro", "roc_auc", "roc_points", "curve_scores", "average_precision", "best_dice", "pr_points", "PR_curve", "PooledCurves", "PooledRegionCurves", "ssim", "median_filter", "erode_mask", "keep_mask",
            "remove_small_components", "PostProcess", "postprocess_maps", "component_areas", "median_filter3d", "erode_mask3d", "remove_small_components3d",
-           "component_areas3d", "VolumePostProcess", "postprocess_volumes", "anomaly_metrics_volume", "anomaly_metrics_volume_surface", "distance_transform3d", "surface_distance3d", "HD95_volume", "aupro", "pro_points", "AUPRO", "distance_transform",
+           "component_areas3d", "gaussian_filter3d", "VolumePostProcess", "postprocess_volumes", "anomaly_metrics_volume", "anomaly_metrics_volume_surface", "distance_transform3d", "surface_distance3d", "HD95_volume", "aupro", "pro_points", "AUPRO", "distance_transform",
            "surface_distance", "HD95", "anomaly_metrics_surface", "gaussian_filter", "image_scores", "image_auc", "anomaly_metrics_image", "order_stats", "counts_at", "scores_at",
            "anomaly_metrics_at", "HealthyPool", "heatmap", "dice_coeff", "PSNR", "SSIM", "IoU", "precision", "recall",
            "FPR", "ROC_AUC", "AUC_score", "testing"]
@@ -1485,6 +1486,59 @@ def component_areas3d(mask, connectivity=3, level=0.0, batched=None):
     return areas, counts
 
 
+# ---------------------------------------------------------------------------------- smoothing of whole volumes (csrc/gauss3d.hip)
+def _gauss3d_radii(sigma, truncate, what):
+    """`sigma`: one number or three in (z, y, x) order, each finite and >= 0; `truncate`: a positive finite number.  Returns
+    (the three sigmas as floats, scipy's radius `int(truncate * sigma + 0.5)` of each axis -- 0 where scipy skips the axis (sigma
+    <= 1e-15) or applies the one-tap kernel).  ValueError for anything else and for a radius above GAUSS_MAX_RADIUS."""
+    def number(v):
+        return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+    sig = (sigma,) * 3 if number(sigma) else (tuple(sigma) if isinstance(sigma, (tuple, list)) else None)
+    if sig is None or len(sig) != 3 or not all(number(s) and 0.0 <= float(s) < float("inf") for s in sig):
+        raise ValueError(f"{what}: sigma must be a finite number >= 0 or a sequence of three in (z, y, x) order, got {sigma!r}")
+    if not number(truncate) or not 0.0 < float(truncate) < float("inf"):
+        raise ValueError(f"{what}: truncate must be a positive finite number, got {truncate!r}")
+    sig = tuple(float(s) for s in sig)
+    radii = tuple(0 if s <= 1e-15 else int(float(truncate) * s + 0.5) for s in sig)
+    if max(radii) > _lib.GAUSS_MAX_RADIUS:
+        raise ValueError(f"{what}: the radius int(truncate * sigma + 0.5) of every axis must be at most {_lib.GAUSS_MAX_RADIUS}, got "
+                         f"{radii} for sigma={sigma!r}, truncate={truncate!r}")
+    return sig, radii
+
+
+def gaussian_filter3d(score, sigma=4.0, truncate=4.0, batched=None):
+    """`scipy.ndimage.gaussian_filter(vol, sigma, truncate=truncate)` (order 0, reflect border) of every D x H x W volume of
+    score: [..., D, H, W], batching and strides as `median_filter3d`.  `sigma`: one number, or three in (z, y, x) order -- slices
+    are usually thicker than the pixels in them, and a sigma in millimetres is `sigma_mm / spacing` per axis; each finite and >=
+    0.  The radius of an axis is `int(truncate * sigma + 0.5)`, at most 32 (else ValueError); an axis of radius 0 is skipped, as
+    scipy's one-tap kernel leaves it.  Returns an fp32 device tensor shaped like score, bit for bit scipy's on the fp32 volumes for
+    finite inputs, without a host synchronisation: the z pass of all volumes in one launch and the two in-plane passes in another
+    (`anoddpm_gauss3d`; one launch when the z axis, or both others, are skipped).  Any D >= 1: the border reflects as often as the
+    radius asks.  With all three axes skipped the result is an fp32 copy and nothing is launched.  NaN / inf spread within the
+    radii by IEEE rules; no other volume is touched.  The tap tables are `gaussian_filter`'s, cached per (sigma, truncate,
+    device); the workspace of the z pass is allocated per call (the caching allocator: capturable after the first use)."""
+    V, D, H, W = _volumes(score, batched, "gaussian_filter3d", "score")
+    sig, radii = _gauss3d_radii(sigma, truncate, "gaussian_filter3d")
+    if not any(radii):
+        return score.to(dtype=torch.float32, copy=True, memory_format=torch.contiguous_format)
+    sc, _, s_stride = _segments(score, V, "gaussian_filter3d(score)")
+    dev = sc.device
+    out = torch.empty(tuple(score.shape), dtype=torch.float32, device=dev)
+    a = _lib.Gauss3dArgs()
+    a.src, a.dst, a.src_stride = sc.data_ptr(), out.data_ptr(), s_stride
+    if radii[0] and (radii[1] or radii[2]):
+        tmp = torch.empty((V * D * H * W,), dtype=torch.float32, device=dev)
+        a.tmp = tmp.data_ptr()
+    for axis, s, r in zip("zyx", sig, radii):
+        setattr(a, "r" + axis, r)
+        if r:
+            setattr(a, "w" + axis, _gauss_table(s, truncate, r, dev).data_ptr())
+    a.S, a.D, a.H, a.W = V, D, H, W
+    _launch("gauss3d", a, dev)
+    return out
+
+
 # ---------------------------------------------------------------------------------- distances on whole volumes (csrc/surface3d.hip)
 def _surface3d_workspace(S, D, H, W, what, transform=False):
     """`_launch`'s workspace of the two entry points of csrc/surface3d.hip: what `anoddpm_surface3d_workspace_bytes` answers, or
@@ -1556,13 +1610,26 @@ def HD95_volume(real_mask, pred_mask):
     return float(_valid_mean(o["hd95"].reshape(-1), o["status"].reshape(-1))[0])
 
 
-class VolumePostProcess:
+class _VolumePostProcessType(type):
+    """`VolumePostProcess(..., gaussian=sigma)`: `_PostProcessType`'s arrangement -- the trailing keyword is taken by the call of
+    the class, and `__init__` keeps its five positional settings and its signature."""
+
+    def __call__(cls, *args, gaussian=None, **kw):
+        self = super().__call__(*args, **kw)
+        if gaussian is not None:
+            object.__setattr__(self, "gaussian", _gauss3d_radii(gaussian, 4.0, "VolumePostProcess: gaussian")[0])
+        return self
+
+
+class VolumePostProcess(metaclass=_VolumePostProcessType):
     """Settings of the volume-wise post-processing between the squared error of a volume and its scores; immutable, hashable,
     picklable.  `median`: window of the 3-D median filter (3, 5; None: off).  `erode`: 3-D erosions of the region of interest
     (0 ... 8; 0: used as it is).  `roi_level`: when not None the region of interest is `real > roi_level` unless the caller hands
     one in.  `min_size` / `connectivity` (1, 2, 3: 6 / 18 / 26 neighbours): 3-D components of the thresholded volume below that
-    many voxels are dropped (0: off).  The defaults are `PostProcess`'s."""
-    __slots__ = ("median", "erode", "roi_level", "min_size", "connectivity")
+    many voxels are dropped (0: off).  The defaults are `PostProcess`'s.  `gaussian` (keyword only; None: off): sigma in voxels of
+    a Gaussian filter (`gaussian_filter3d`, truncate 4.0) applied before the median, one number or three in (z, y, x) order --
+    for a sigma in millimetres divide by the spacing of each axis; kept as a tuple of three floats."""
+    __slots__ = ("median", "erode", "roi_level", "min_size", "connectivity", "gaussian")
 
     def __init__(self, median=5, erode=3, roi_level=None, min_size=7, connectivity=1):
         if median is not None and median not in _lib.MEDIAN3D_SIZES:
@@ -1573,6 +1640,7 @@ class VolumePostProcess:
             raise ValueError(f"VolumePostProcess: min_size must be an integer >= 0, got {min_size!r}")
         if connectivity not in (1, 2, 3):
             raise ValueError(f"VolumePostProcess: connectivity must be 1, 2 or 3, got {connectivity!r}")
+        object.__setattr__(self, "gaussian", None)                   # _VolumePostProcessType.__call__ sets it
         for k, v in (("median", median), ("erode", int(erode)), ("roi_level", None if roi_level is None else float(roi_level)),
                      ("min_size", int(min_size)), ("connectivity", int(connectivity))):
             object.__setattr__(self, k, v)
@@ -1583,8 +1651,13 @@ class VolumePostProcess:
     def __delattr__(self, name):
         raise AttributeError("VolumePostProcess is immutable")
 
+    def _settings(self):
+        """The settings that are spelled out: `gaussian` only when it is set, so that key, hash, repr and pickle of everything from
+        before it existed are what they were."""
+        return [k for k in self.__slots__ if k != "gaussian" or self.gaussian is not None]
+
     def _key(self):
-        return tuple(getattr(self, k) for k in self.__slots__)
+        return tuple(getattr(self, k) for k in self._settings())
 
     def __eq__(self, other):
         return isinstance(other, VolumePostProcess) and self._key() == other._key()
@@ -1593,10 +1666,16 @@ class VolumePostProcess:
         return hash(self._key())
 
     def __repr__(self):
-        return "VolumePostProcess(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+        return "VolumePostProcess(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self._settings()) + ")"
 
     def __reduce__(self):
-        return VolumePostProcess, self._key()
+        if self.gaussian is None:
+            return VolumePostProcess, self._key()
+        return _volume_postprocess_from, ({k: getattr(self, k) for k in self.__slots__},)
+
+
+def _volume_postprocess_from(settings):
+    return VolumePostProcess(**settings)
 
 
 def postprocess_volumes(sqerr, pp, real=None, roi=None):
@@ -1606,7 +1685,7 @@ def postprocess_volumes(sqerr, pp, real=None, roi=None):
     and is thresholded and eroded `pp.erode` times in 3-D in ONE launch -- with nothing outside the volume, so the erosion also
     takes `pp.erode` slices off either end of the column.  ONE median launch then applies it.  Returns a
     device tensor shaped like sqerr, no host synchronisation.  With `pp.median` None the region is applied by an elementwise
-    product."""
+    product.  `pp.gaussian` runs first (`gaussian_filter3d`): the median and the region see the smoothed volumes."""
     if not isinstance(pp, VolumePostProcess):
         raise TypeError("postprocess_volumes: pp must be a VolumePostProcess")
     V, D, H, W = _volumes(sqerr, None, "postprocess_volumes", "sqerr")
@@ -1624,11 +1703,14 @@ def postprocess_volumes(sqerr, pp, real=None, roi=None):
             roi = (_f32c(roi, "postprocess_volumes(roi)") > level).float()
         else:                                                        # one plane: the same column through every slice, eroded as that volume
             roi = erode_mask3d(roi.reshape(1, H, W).expand(D, H, W) if roi.numel() == H * W else roi.reshape((-1, D, H, W)), pp.erode, level)
+    smoothed = pp.gaussian is not None
+    if smoothed:
+        sqerr = gaussian_filter3d(sqerr, pp.gaussian)
     if pp.median is not None:
         return median_filter3d(sqerr, pp.median, roi=roi)
     out = _f32c(sqerr, "postprocess_volumes(sqerr)")
     if roi is None:
-        return out.clone()
+        return out if smoothed else out.clone()
     shape = (1, 1, H, W) if roi.numel() == H * W else ((1, D, H, W) if roi.numel() == D * H * W else (V, D, H, W))
     return (out.reshape(V, D, H, W) * roi.reshape(shape)).reshape(out.shape)
 

@@ -32,7 +32,7 @@ extern "C" {
  * constants and prototypes from this file, compares the two at load time.  It moves whenever a struct or a prototype below changes.
  * The binding reads the restricted C written here: scalar and pointer fields, enum entries and macros with integer values,
  * plain prototypes.  It refuses anything else (arrays, nested structs, bit-fields, function pointers) at import. */
-#define ANODDPM_ABI_VERSION 42
+#define ANODDPM_ABI_VERSION 43
 
 int anoddpm_abi_version(void);          /* ANODDPM_ABI_VERSION of the header the library was built from */
 const char *anoddpm_last_error(void);   /* [host] text of the last failure on this thread */
@@ -1175,6 +1175,48 @@ typedef struct anoddpm_map_scores_args {
 
 int anoddpm_gauss2d(const anoddpm_gauss_args *a, void *stream);
 int anoddpm_map_scores(const anoddpm_map_scores_args *a, void *stream);
+
+/* ------------------------------------------------------------------ Gaussian smoothing of whole volumes
+ * The smoothing the volume-wise protocols apply before the median, the cut and the distances; the reference has no counterpart.
+ * csrc/gauss3d.hip.
+ *
+ * anoddpm_gauss3d replaces scipy.ndimage.gaussian_filter(vol, (sz, sy, sx), truncate=t) with scipy's defaults (order 0,
+ *   mode="reflect", fp32 in, fp32 out) on S volumes of D x H x W fp32, volume v at src + v * src_stride (src_stride >= D*H*W, the
+ *   slices of a volume contiguous); dst is contiguous [S][D][H][W].  Bit for bit scipy's for finite inputs:
+ *     rz, ry, rx   the radius int(t * sigma + 0.5) of each axis, 0 ... ANODDPM_GAUSS_MAX_RADIUS.  An axis of radius 0 is SKIPPED
+ *                  (scipy skips it for sigma <= 1e-15 and otherwise applies the one-tap kernel [1.0], the identity on fp32).
+ *     wz, wy, wx   [dev] the taps of each axis in anoddpm_gauss2d's format: radius + 1 fp64 values, the outermost first, the centre
+ *                  last.  The kernel only reads them; the table of an axis of radius 0 is not read and may be NULL.
+ *     order        the axes run in scipy's order: D, then H, then W.
+ *     a line       anoddpm_gauss2d's statement:  acc = v[i] * w[r];  for j = -r ... -1 in that order:  acc += (v[i+j] + v[i-j]) *
+ *                  w[r+j];  v is the line as fp64, every product and sum rounded once, no fused multiply-add; the result is
+ *                  ROUNDED TO fp32 AFTER EACH AXIS.
+ *     border       index i of a line of n:  m = i mod 2n (non-negative);  m >= n -> 2n - 1 - m, as often as it takes: D = 1 and
+ *                  D < rz are legal (as are H, W below their radii).
+ *     tmp          [dev] fp32 workspace of S*D*H*W elements: the volumes after the z pass.  Needed only when two launches run (rz
+ *                  > 0 and ry or rx > 0); NULL is accepted otherwise.
+ *   Launches: one separable tile kernel, a workgroup of 256 threads on a 32 x 32 tile of a plane with independent radii (r0, r1)
+ *   per axis, either of which may be 0 --
+ *     1. the S planes of D x (H*W), radii (rz, 0), src -> tmp: the z pass of a volume IS the axis-0 pass of that plane, and the
+ *        fp32 store is scipy's rounding between axis 0 and axis 1;
+ *     2. the S*D planes of H x W, radii (ry, rx), tmp -> dst (anoddpm_gauss2d's structure).
+ *   With rz == 0 only launch 2 runs, with ry == rx == 0 only launch 1; either goes src -> dst.  LDS per workgroup:
+ *   ((32 + 2 r0)(32 + 2 r1) + 32 (32 + 2 r1)) * 4 + 528 bytes, 49680 at radius 32 on both axes.
+ *   Refused before anything is launched: a NULL pointer where one is needed, rz == ry == rx == 0, a radius outside 0 ... 32, an
+ *   extent below 1, S*D*H*W >= 2^31, src_stride < D*H*W with S > 1, dst or tmp overlapping src, tmp overlapping dst.
+ *   A non-finite input spreads by IEEE rules within the radii (no status word); no other volume is touched.  No allocation and no
+ *   host synchronisation; capturable. */
+typedef struct anoddpm_gauss3d_args {
+    const float *src;               /* [dev] */
+    float *dst;                     /* [dev] [S][D][H][W] */
+    float *tmp;                     /* [dev] [S][D][H][W], or NULL when one launch runs */
+    const double *wz, *wy, *wx;     /* [dev] [radius + 1] each */
+    int64_t src_stride;
+    int32_t S, D, H, W;
+    int32_t rz, ry, rx;
+} anoddpm_gauss3d_args;
+
+int anoddpm_gauss3d(const anoddpm_gauss3d_args *a, void *stream);
 
 /* ------------------------------------------------------------------ operating thresholds from a pooled segment, scores at them
  * The evaluation protocol of unsupervised anomaly segmentation (the reference has no counterpart: it cuts every map at 0.5): the
